@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the batched DDP hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5] [--dump-outputs DIR] [--full]
 
 With N > 1 and no RANK / WORLD_SIZE in the environment (i.e. not under torch.distributed.run) the script starts its
 own N ranks, one process per GPU (launch_ranks); under torch.distributed.run it is one of the ranks.
@@ -17,12 +17,23 @@ iterations of the solve; the next K are timed between barrier + torch.cuda.synch
 maximum over ranks is taken.  value = knot-steps/s = (sum over ranks of B) * T * K / time.  Inputs are
 resident in HBM before the timed region.
 
-Extra objects on the JSON line:
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs) and print the line.
+
+--dump-outputs DIR  after the timed steps, what they leave a caller (the last accepted step committed, as
+                aslr_solve does on exit): xs [B, T+1, nx], us [B, T, nu], the feed-forward gains k [B, T, nu]
+                of the last backward pass, and the per-trajectory cost and stop [B], as DIR/<name>.npy in
+                float64.  Inputs are seeded, so the same arguments give the same inputs on every run.  Files
+                larger than 64 MB in all are cut to a seed-0 sample of trajectories (the same rows in every
+                file).  With N > 1 every rank writes its own shard as DIR/<name>_rank<r>.npy.
+
+--full adds the figures that take work of their own, after the timed steps:
+  kernel_ms     per-kernel durations: 10 more iterations with whole-shard launches timed by HIP events.
   roofline      the dominant kernel of the iteration: ALGORITHMIC bytes per launch (SURVEY.md 8(d)'s
                 per-knot-step figure for that phase x the B*T knot-steps one launch processes)
                 / its mean launch duration measured here with HIP events on the launch stream.
+  roofline_iteration, line_search_trials_per_iteration, solver_state  (the solver state is read back and reduced).
   cpu_baseline  the CPU oracle (oracle/, a port -- Crocoddyl itself cannot be installed here) solving a
-                bounded sample of the same batch on the host cores, rank 0 at N = 1 only.
+                bounded sample of the same batch on the host cores, rank 0 at N = 1 only (--no-cpu-baseline: off).
 """
 import argparse
 import json
@@ -134,6 +145,61 @@ def cpu_baseline(w, nthreads):
             "single_thread_note": "the reference forces nthreads = 1 (examples/double_pendulum.py:54)"}
 
 
+def full_figures(w, workload, e, Bg, T, world, value, k_ms, stats):
+    """--full: per-kernel durations, roofline figures and solver state of the run (see the module docstring)."""
+    p1, p2, p3 = algorithmic_bytes(e.nx, e.nu)
+    names = ["calc_kernel", "backward_kernel", "forward (rollout + trial_cost + sum_cost + select kernels)"]
+    if workload == "c5":
+        names = ["calcDiff (dyn_team_kernel x 2 + calc_kernel)", "backward_blk_kernel",
+                 "forward (rollout_team + trial_cost + sum_cost + select kernels)"]
+    # the sequential line search of the algorithm needs (accepted index + 1) trials; the kernel evaluates
+    # all 10 step lengths at once, but only the required ones count as algorithmic traffic
+    trials = stats["trials_sum"] / max(stats["iters_sum"], 1)
+    phase_bytes = [p1, p2, p3 * trials]
+    dom = max(range(3), key=lambda i: k_ms[i])
+    launch_bytes = phase_bytes[dom] * Bg * T
+    achieved = launch_bytes / (k_ms[dom] * 1e-3) / 1e9
+    traffic, traffic_note = pmc_traffic(w["kernels"][dom], workload)
+    return {
+        "line_search_trials_per_iteration": trials,
+        "kernel_ms": dict(zip(names, k_ms)),
+        "kernel_ms_note": "whole-shard launches on one stream (sub-shards off), HIP events; their sum is the "
+                          "iteration without overlap, ms_per_step the iteration with the sub-shard streams",
+        "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
+                     "kernel_instantiation": w["kernels"][dom],
+                     "algorithmic_bytes_per_launch": launch_bytes,
+                     "algorithmic_bytes_per_knot_step": phase_bytes[dom],
+                     "knot_steps_per_launch": Bg * T},
+        "roofline_iteration": {"algorithmic_bytes_per_knot_step": p1 + p2 + p3,
+                               "achieved": (p1 + p2 + p3) * value / world / 1e9, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s per GPU", "frac": (p1 + p2 + p3) * value / world / 1e9 / HBM_PEAK_GBS,
+                               "note": "SURVEY.md 8(d) whole-iteration figure (%d B per knot-step at nx=%d, nu=%d)" % (p1 + p2 + p3, e.nx, e.nu)},
+        "solver_state": stats,
+    }
+
+
+DUMP_BYTES = 63 * 10 ** 6  # --dump-outputs: the array data of all files of all ranks (headers fit in the last MB of 64)
+
+
+def dump_outputs(e, outdir, rank, world):
+    """--dump-outputs (see the module docstring); the caller has committed the last step (e.finalize()) and synchronised."""
+    import numpy as np
+    from aslr_to_amd import _abi
+    arrays = {"xs": e.xs, "us": e.cut_u(e.us), "k": e.cut_u(e.region(_abi.R_KFF), axis=2).transpose(0, 1),
+              "cost": e.traj_f(_abi.TF_COST), "stop": e.traj_f(_abi.TF_STOP)}
+    arrays = {name: v.cpu().numpy().astype(np.float64) for name, v in arrays.items()}
+    per_traj = sum(a.nbytes for a in arrays.values()) // e.B
+    keep = min(e.B, DUMP_BYTES // world // per_traj)
+    if keep < e.B:
+        rows = np.sort(np.random.default_rng(0).choice(e.B, keep, replace=False))
+        arrays = {name: a[rows] for name, a in arrays.items()}
+    os.makedirs(outdir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def rank_env(rank, world, port, base=None):
     """Environment of one child rank (the variables torch.distributed.run would set)."""
     env = dict(os.environ if base is None else base)
@@ -182,7 +248,11 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3",
                     help="c3: 2-DoF VSA BoxDDP, 4096 per GPU (headline); c2: 2-DoF SEA DDP, 1024; c5: 7-DoF SEA DDP, T=150, 512 per GPU")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="trajectories per GPU (default: the workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel durations, roofline figures, solver state and CPU baseline (extra work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--subshards", type=int, default=4,
                     help="iterate each GPU's shard as this many sub-shards on internal streams (1 = off)")
     ap.add_argument("--converge-mode", action="store_true",
@@ -190,6 +260,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -249,17 +321,23 @@ def main():
     elapsed = dist.max_over_ranks(mine, dev)
     per_rank_ms = [v / args.steps * 1e3 for v in dist.gather_floats(mine, dev)]  # (a slow GPU shows in the line)
 
-    # per-kernel durations: HIP events on the launch stream around each phase, with the whole shard as ONE launch per
-    # kernel (aslr_iterate_timed does not use the sub-shard streams), a few more iterations of the same solve
-    nprobe = 10
-    acc = [0.0, 0.0, 0.0]
-    for _ in range(nprobe):
-        ms = e.iterate_timed(sp)
-        acc = [a + m for a, m in zip(acc, ms)]
-    k_ms = [a / nprobe for a in acc]
-    e.finalize()
-    torch.cuda.synchronize(dev)
-    stats = dist.all_reduce_stats(dist.local_stats(e))  # the ONE collective of a solve (RCCL over xGMI)
+    if args.dump_outputs:
+        e.finalize()
+        torch.cuda.synchronize(dev)
+        dump_outputs(e, args.dump_outputs, rank, world)
+
+    if args.full:
+        # per-kernel durations: HIP events on the launch stream around each phase, with the whole shard as ONE launch
+        # per kernel (aslr_iterate_timed does not use the sub-shard streams), a few more iterations of the same solve
+        nprobe = 10
+        acc = [0.0, 0.0, 0.0]
+        for _ in range(nprobe):
+            ms = e.iterate_timed(sp)
+            acc = [a + m for a, m in zip(acc, ms)]
+        k_ms = [a / nprobe for a in acc]
+        e.finalize()
+        torch.cuda.synchronize(dev)
+        stats = dist.all_reduce_stats(dist.local_stats(e))  # the ONE collective of a solve (RCCL over xGMI)
 
     # converge mode (--converge-mode): the example's own solve -- th_stop 1e-7, maxiter 400, exit when
     # every trajectory of the shard has stopped -- timed once, outside the figure of merit above (off by default so
@@ -306,19 +384,6 @@ def main():
         return
     knot_steps = Bg * world * T * args.steps
     value = knot_steps / elapsed
-    p1, p2, p3 = algorithmic_bytes(e.nx, e.nu)
-    names = ["calc_kernel", "backward_kernel", "forward (rollout + trial_cost + sum_cost + select kernels)"]
-    if args.workload == "c5":
-        names = ["calcDiff (dyn_team_kernel x 2 + calc_kernel)", "backward_blk_kernel",
-                 "forward (rollout_team + trial_cost + sum_cost + select kernels)"]
-    # the sequential line search of the algorithm needs (accepted index + 1) trials; the kernel evaluates
-    # all 10 step lengths at once, but only the required ones count as algorithmic traffic
-    trials = stats["trials_sum"] / max(stats["iters_sum"], 1)
-    phase_bytes = [p1, p2, p3 * trials]
-    dom = max(range(3), key=lambda i: k_ms[i])
-    launch_bytes = phase_bytes[dom] * Bg * T
-    achieved = launch_bytes / (k_ms[dom] * 1e-3) / 1e9
-    traffic, traffic_note = pmc_traffic(w["kernels"][dom], args.workload)
     out = {
         "metric": w["metric"] if Bg == w["batch"] else w["metric"].replace("%d trajectories per GPU" % w["batch"], "%d trajectories per GPU" % Bg),
         "value": value, "unit": "knot-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -334,25 +399,12 @@ def main():
                   "note": "world size as torch.distributed reports it after init (nccl = RCCL over xGMI)"},
         "ddp_iterations_per_s": args.steps / elapsed,
         "trajectory_iterations_per_s": Bg * world * args.steps / elapsed,
-        "line_search_trials_per_iteration": trials,
         "line_search_rollouts_per_s": 10 * Bg * world * args.steps / elapsed,   # every step length is rolled out
         "converge_mode": converge,   # --converge-mode
-        "kernel_ms": dict(zip(names, k_ms)),
-        "kernel_ms_note": "whole-shard launches on one stream (sub-shards off), HIP events; their sum is the "
-                          "iteration without overlap, ms_per_step the iteration with the sub-shard streams",
-        "roofline": {"bound": "hbm", "kernel": names[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_note": traffic_note,
-                     "kernel_instantiation": w["kernels"][dom],
-                     "algorithmic_bytes_per_launch": launch_bytes,
-                     "algorithmic_bytes_per_knot_step": phase_bytes[dom],
-                     "knot_steps_per_launch": Bg * T},
-        "roofline_iteration": {"algorithmic_bytes_per_knot_step": p1 + p2 + p3,
-                               "achieved": (p1 + p2 + p3) * value / world / 1e9, "peak": HBM_PEAK_GBS,
-                               "unit": "GB/s per GPU", "frac": (p1 + p2 + p3) * value / world / 1e9 / HBM_PEAK_GBS,
-                               "note": "SURVEY.md 8(d) whole-iteration figure (%d B per knot-step at nx=%d, nu=%d)" % (p1 + p2 + p3, e.nx, e.nu)},
-        "solver_state": stats,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out.update(full_figures(w, args.workload, e, Bg, T, world, value, k_ms, stats))
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             nthreads = len(os.sched_getaffinity(0))
         except AttributeError:
