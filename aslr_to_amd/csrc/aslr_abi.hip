@@ -367,19 +367,20 @@ int backward_hs(const aslr_problem *p) {
   return p->bwd_hs;
 }
 
-// nj = 7 with VSA actuation (nx = 28, nu = 14) is built at the MODEL level only -- calc / calcDiff sweeps, dam_eval,
-// dam_residuals, frame placements: what the reference exercises for that combination
-// (unittest/test_free_placementcost_free_fwddyn.py:12-46) -- not in the solver kernels
-int solver_unsupported(const aslr_problem *p) {
-  if (p->nj == 7 && p->dam == ASLR_DAM_VSA) {
-    snprintf(g_err, sizeof g_err, "the solver kernels are not built for (nj=7, VSA): model-level evaluation only");
+// nj = 7 with VSA actuation (nx = 28, nu = 14): the solver kernels are built for SolverBoxDDP, the solver both VSA
+// examples of the reference use.  Without the box the stiffness commands are unconstrained and go negative, so
+// SolverDDP / SolverFDDP stay at the MODEL level for this combination -- calc / calcDiff sweeps, dam_eval,
+// dam_residuals, frame placements, quasi-static controls -- and their solver entry points decline.
+int solver_unsupported(const aslr_problem *p, int solver) {
+  if (p->nj == 7 && p->dam == ASLR_DAM_VSA && solver != ASLR_SOLVER_BOXDDP) {
+    snprintf(g_err, sizeof g_err, "the solver kernels for (nj=7, VSA) are built for SolverBoxDDP only: model-level evaluation only with SolverDDP / SolverFDDP");
     return ASLR_E_INVALID;
   }
   return ASLR_OK;
 }
 
 int launch_backward(aslr_problem *p, const SolverDev &sd, hipStream_t st, bool all_feasible = false) {
-  if (int rc = solver_unsupported(p)) return rc;
+  if (int rc = solver_unsupported(p, sd.solver)) return rc;
   const int hs = backward_hs(p);
   const ModelLimits lim = make_limits(p);
   if (p->nx == 8) return launch_backward_nx8(p->k, p->nu, hs, sd, lim, all_feasible, st);
@@ -389,7 +390,7 @@ int launch_backward(aslr_problem *p, const SolverDev &sd, hipStream_t st, bool a
 }
 
 int launch_forward(aslr_problem *p, const SolverDev &sd, hipStream_t st) {
-  if (int rc = solver_unsupported(p)) return rc;
+  if (int rc = solver_unsupported(p, sd.solver)) return rc;
   const ModelLimits lim = make_limits(p);
   if (p->nj == 2) return launch_forward_nj2(p->k, p->dam, sd, lim, st);
   if (p->nj == 7) return launch_forward_nj7(p->k, p->dam, sd, lim, st);
@@ -657,7 +658,7 @@ int aslr_set_subshards(aslr_problem_t *p, int32_t n) {
 
 int aslr_iterate_n(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t first, int32_t n, void *stream) {
   if (!p || !sp || n < 0) return ASLR_E_INVALID;
-  if (int rc = solver_unsupported(p)) return rc;
+  if (int rc = solver_unsupported(p, sp->solver)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int B = p->desc.B;
   if (p->pool_maxiter == 0) p->const_pending_full = !p->const_written; // (aslr_solve_pool sets it itself)
@@ -683,7 +684,7 @@ int aslr_iterate(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t firs
 
 int aslr_iterate_timed(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t first, void *stream, float *ms3) {
   if (!p || !sp || !ms3) return ASLR_E_INVALID;
-  if (int rc = solver_unsupported(p)) return rc;
+  if (int rc = solver_unsupported(p, sp->solver)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (!p->have_ev) {
     for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&p->ev[i]));
@@ -767,7 +768,7 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
     snprintf(g_err, sizeof g_err, "aslr_solve_pool: per-problem frame references need a problem created with a frame_ref table");
     return ASLR_E_INVALID;
   }
-  if (int rc = solver_unsupported(p)) return rc;
+  if (int rc = solver_unsupported(p, sp->solver)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int B = p->desc.B;
   if (refill_every <= 0) refill_every = 4;
@@ -909,7 +910,6 @@ int aslr_quasi_static(aslr_problem_t *p, int32_t maxiter, double tol, int32_t *i
   if (!p || maxiter <= 0) return ASLR_E_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (p->nj == 2) return launch_quasi_static_nj2(p->k, p->dam, maxiter, tol, iters_dev, st);
-  if (int rc = solver_unsupported(p)) return rc;
   if (p->nj == 7) return launch_quasi_static_nj7(p->k, p->dam, maxiter, tol, iters_dev, st);
   snprintf(g_err, sizeof g_err, "unsupported nj=%d", p->nj);
   return ASLR_E_INVALID;

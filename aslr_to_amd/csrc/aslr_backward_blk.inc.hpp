@@ -20,14 +20,24 @@
 // SolverBoxDDP (BOX): wave 0 also runs computeGains' box QP for the block's trajectory (lane_gains<NU>: every lane the
 // same nu x nu problem, wave-uniform control flow, the lane's own column of Qux solved with the final free-set factor);
 // the node's u and stored k (the QP's bounds and warm start) come in with the record prefetch.
+//
+// nu = 14 (VSA on the 7-joint arm; record 2590 doubles = 20.7 KB): the controls are padded to NUP = 16 in Qux^T / K (four
+// MFMA contraction steps in the Vxx update, same k-ordered sums as the vector path), pass 2b takes five entries per thread,
+// and gains + box QP are worked by the lanes of wave 0 on LDS operands (aslr_wave_gains.hpp) instead of one lane's
+// registers.  LDS per block: 38.9 KB at nu = 7, 55.0 KB at nu = 14 (two blocks per CU fit in 160 KB); 0 bytes of scratch
+// for every <28, 14, ...> instantiation (profiles/vsa7/kernel_meta.txt).
 #pragma once
 #include "aslr_backward.inc.hpp"
+#include "aslr_wave_gains.hpp"
 
 namespace aslr {
 
 template <int NX, int NU>
 struct BwdBlk {
-  static_assert(NX % 4 == 0 && NX > 16 && NX <= 32 && NU <= 8, "thread map: (16 x 2) rows x 8 groups of 4 columns");
+  static_assert(NX % 4 == 0 && NX > 16 && NX <= 32 && NU <= 16, "thread map: (16 x 2) rows x 8 groups of 4 columns");
+  static constexpr int NUP = NU <= 8 ? 8 : 16;   // controls padded to whole MFMA contraction steps
+  static constexpr int NUG = (NU + 7) / 8;       // vector path: columns g, g + 8, ... of P Fu per thread
+  static constexpr bool WAVEQP = NU > 8;         // gains and box QP by the lanes of wave 0 on LDS operands (aslr_wave_gains.hpp)
   static constexpr int NT = 128;
   static constexpr int NG = NX / 4;
   static constexpr int REC = rec_len_c(NX, NU);
@@ -39,9 +49,10 @@ struct BwdBlk {
   // Vx sits directly behind PT: it is row nx of the left operand of the MFMA pass 1, which then yields Fx^T Vx and
   // Fu^T Vx (for Qx, Qu) along with P Fx and P Fu
   static constexpr int sRec = 0, sPT = sRec + even(REC), sVx = sPT + NX * NX, sA = sVx + even(NX), sB = sA + NX * NX,
-                       sQux = sB + even(NU * NX), sQuxT = sQux + even(NU * NX), sK = sQuxT + NX * 8,
-                       sQuu = sK + 8 * NX, sQu = sQuu + 64, sQx = sQu + 8, sF = sQx + 32,
-                       sRed = sF + 32, sCost = sRed + 64, sFlag = sCost + NT, sUK = sFlag + 2, sEnd = sUK + 16;
+                       sQux = sB + even(NU * NX), sQuxT = sQux + even(NU * NX), sK = sQuxT + NX * NUP,
+                       sQuu = sK + NUP * NX, sQu = sQuu + NUP * NUP, sQx = sQu + NUP, sF = sQx + 32,
+                       sRed = sF + 32, sCost = sRed + 64, sFlag = sCost + NT, sUK = sFlag + 2, sWG = sUK + 2 * NUP,
+                       sQuuk = sWG + (WAVEQP ? WaveGainsLds<NU>::SIZE : 0), sEnd = sQuuk + (WAVEQP ? NUP : 0);
   static constexpr int LDS = even(sEnd);
 };
 
@@ -61,10 +72,13 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
          *QuxT = sm + C::sQuxT, *KL = sm + C::sK, *QuuL = sm + C::sQuu, *QuL = sm + C::sQu, *QxL = sm + C::sQx,
          *VxL = sm + C::sVx, *FL = sm + C::sF, *RedL = sm + C::sRed, *CostL = sm + C::sCost;
   int *FlagL = reinterpret_cast<int *>(sm + C::sFlag);
-  double *UKL = sm + C::sUK; // [u (8) | stored k (8)] of the knot (box nodes)
+  double *UKL = sm + C::sUK; // [u (NUP) | stored k (NUP)] of the knot (box nodes)
+  constexpr int NUP = C::NUP, NUG = C::NUG;
 
   const int tid = threadIdx.x, rr = tid >> 3, g = tid & 7;
-  const int gc = g < NG ? g : NG - 1, gu = g < NU ? g : NU - 1;
+  const int gc = g < NG ? g : NG - 1;
+  int gu[NUG]; // columns of Fu this thread takes in the vector pass 1 (clamped)
+  ASLR_UNROLL for (int w = 0; w < NUG; ++w) gu[w] = g + 8 * w < NU ? g + 8 * w : NU - 1;
   const int row[2] = {rr, rr + 16 < NX ? rr + 16 : NX - 1};               // rows of this thread (second clamped)
   const bool cell[2] = {g < NG, g < NG && rr + 16 < NX};                  // it owns entries (row[h], 4g..4g+3)
   const bool wave0 = tid < 64;
@@ -102,10 +116,10 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
     }
   }
   if (done) return;
-  // zero padding of the 8-long contraction of the MFMA Vxx update (never overwritten: Qux^T and K hold nu < 8 entries)
-  static_assert(NU < 8, "one padding slot per row");
-  ASLR_UNROLL for (int c = NU; c < 8; ++c) {
-    if (tid < NX) { QuxT[tid * 8 + c] = 0.0; KL[c * NX + tid] = 0.0; }
+  // zero padding of the NUP-long contraction of the MFMA Vxx update (never overwritten: Qux^T and K hold nu < NUP entries)
+  static_assert(NU < NUP, "at least one padding slot per row");
+  ASLR_UNROLL for (int c = NU; c < NUP; ++c) {
+    if (tid < NX) { QuxT[tid * NUP + c] = 0.0; KL[c * NX + tid] = 0.0; }
   }
   bool need = true;
   double xreg = TF[ASLR_TF_XREG * B + b];
@@ -113,15 +127,20 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
   const bool gaps_on = GAPS && !feasible;
   const bool box = BOX && sp.solver == ASLR_SOLVER_BOXDDP && feasible; // (SolverBoxDDP::computeGains: plain gains while infeasible)
 
-  // pass-2b tasks: entries e of [Qux (nu x nx) | Quu (nu x nu)], e = tid and tid + NT (compile-time strides on
-  // each path: a per-thread stride makes the compiler keep one LDS address per contraction step)
-  constexpr int NQX = NU * NX, NQ = NQX + NU * NU;
-  static_assert(NT < NQX && NQ <= 2 * NT, "two tasks per thread, the first always in Qux");
-  const int e1 = tid + NT;
-  const bool e1x = e1 < NQX, e1u = !e1x && e1 < NQ;
-  const int k2a = tid / NX, c2a = tid % NX;
-  const int k2b = e1x ? e1 / NX : 0, c2b = e1x ? e1 % NX : 0;
-  const int k3 = e1u ? (e1 - NQX) / NU : 0, c3 = e1u ? (e1 - NQX) % NU : 0;
+  // pass-2b tasks: entries e of [Qux (nu x nx) | Quu (nu x nu)], e = tid + NT w for w < NTASK (compile-time strides on
+  // each path: a per-thread stride makes the compiler keep one LDS address per contraction step).  The first NXT
+  // tasks of every thread lie in Qux; a later one is in Qux (kx), in Quu (ku) or past the end.
+  constexpr int NQX = NU * NX, NQ = NQX + NU * NU, NTASK = (NQ + NT - 1) / NT, NXT = NQX / NT;
+  static_assert(NXT >= 1, "the first task always in Qux");
+  bool ex[NTASK], eu[NTASK];
+  int k2[NTASK], c2[NTASK];
+  ASLR_UNROLL for (int w = 0; w < NTASK; ++w) {
+    const int e = tid + NT * w;
+    ex[w] = e < NQX;
+    eu[w] = !ex[w] && e < NQ;
+    k2[w] = ex[w] ? e / NX : (eu[w] ? (e - NQX) / NU : 0);
+    c2[w] = ex[w] ? e % NX : (eu[w] ? (e - NQX) % NU : 0);
+  }
 
   double d1 = 0.0, d2 = 0.0, stop = 0.0, dgf = 0.0, dqf = 0.0;
   while (need) {
@@ -172,7 +191,7 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
         if (C::NPRE * NT == REC / 2 || idx < REC / 2) { const nt_double2 v2 = __builtin_nontemporal_load(src + idx); prx[q] = v2.x; pry[q] = v2.y; } \
       }                                                                                                \
       if (gaps_on && tid < NX) pre_f = a.gaps[tbp * NX + tid];                                         \
-      if (box && tid < 16) pre_uk = (tid & 7) < NU ? (tid < 8 ? a.us[tbp * NU + tid] : a.kff[tbp * NU + tid - 8]) : 0.0; \
+      if (box && tid < 2 * NUP) pre_uk = (tid % NUP) < NU ? (tid < NUP ? a.us[tbp * NU + tid] : a.kff[tbp * NU + tid - NUP]) : 0.0; \
       pre_m = node_model_at(a, tt);                                                                    \
     } while (0)
     ASLR_PROF_DECL;
@@ -189,7 +208,7 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
           if (C::NPRE * NT == REC / 2 || idx < REC / 2) { double2 v2; v2.x = prx[q]; v2.y = pry[q]; dst[idx] = v2; }
         }
         if (gaps_on && tid < NX) FL[tid] = pre_f;
-        if (box && tid < 16) UKL[tid] = pre_uk;
+        if (box && tid < 2 * NUP) UKL[tid] = pre_uk;
       }
       const int mi = pre_m;
       __syncthreads();
@@ -230,7 +249,8 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
       } else {
       // ---- pass 1: C(r, 4g..) = sum_l P(r,l) Fx(l, 4g..)  [= A(4g.., r)],  (P Fu)(r, g) [= B(g, r)] ----
         {
-          double c[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, bu[2] = {0.0, 0.0};
+          double c[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, bu[2][NUG];
+          ASLR_UNROLL for (int w = 0; w < NUG; ++w) { bu[0][w] = 0.0; bu[1][w] = 0.0; }
           const double2 *prow0 = reinterpret_cast<const double2 *>(PT + row[0] * NX);
           const double2 *prow1 = reinterpret_cast<const double2 *>(PT + row[1] * NX);
           _Pragma("unroll 2") for (int l = 0; l < NX; l += 2) {
@@ -238,17 +258,19 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
             const double2 *f0 = reinterpret_cast<const double2 *>(rec + C::oFx + l * NX + 4 * gc);
             const double2 *f1 = reinterpret_cast<const double2 *>(rec + C::oFx + (l + 1) * NX + 4 * gc);
             const double2 f0a = f0[0], f0b = f0[1], f1a = f1[0], f1b = f1[1];
-            const double u0 = rec[C::oFu + l * NU + gu], u1 = rec[C::oFu + (l + 1) * NU + gu];
+            double u0[NUG], u1[NUG];
+            ASLR_UNROLL for (int w = 0; w < NUG; ++w) { u0[w] = rec[C::oFu + l * NU + gu[w]]; u1[w] = rec[C::oFu + (l + 1) * NU + gu[w]]; }
             ASLR_UNROLL for (int h = 0; h < 2; ++h) {
               c[h][0] += p[h].x * f0a.x; c[h][1] += p[h].x * f0a.y; c[h][2] += p[h].x * f0b.x; c[h][3] += p[h].x * f0b.y;
-              bu[h] += p[h].x * u0;
+              ASLR_UNROLL for (int w = 0; w < NUG; ++w) bu[h][w] += p[h].x * u0[w];
               c[h][0] += p[h].y * f1a.x; c[h][1] += p[h].y * f1a.y; c[h][2] += p[h].y * f1b.x; c[h][3] += p[h].y * f1b.y;
-              bu[h] += p[h].y * u1;
+              ASLR_UNROLL for (int w = 0; w < NUG; ++w) bu[h][w] += p[h].y * u1[w];
             }
           }
           ASLR_UNROLL for (int h = 0; h < 2; ++h) {
             if (cell[h]) { ASLR_UNROLL for (int q = 0; q < 4; ++q) AL[(4 * g + q) * NX + row[h]] = c[h][q]; }
-            if (g < NU && (h == 0 || rr + 16 < NX)) BL[g * NX + row[h]] = bu[h];
+            ASLR_UNROLL for (int w = 0; w < NUG; ++w)
+              if (g + 8 * w < NU && (h == 0 || rr + 16 < NX)) BL[(g + 8 * w) * NX + row[h]] = bu[h][w];
           }
         }
       }
@@ -318,49 +340,70 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
           if (gq < NU && col < NX) {
             const double v = rec[C::oLxu + col * NU + gq] + x0[q];
             QuxL[gq * NX + col] = v;
-            QuxT[col * 8 + gq] = v;
+            QuxT[col * NUP + gq] = v;
           }
           if (wv == 1 && gq < NU && li < NU) QuuL[gq * NU + li] = rec[C::oLuu + gq * NU + li] + u0[q] + (gq == li ? xr : 0.0);
         }
       } else {
-      {
-        double s = 0.0;
-        const double2 *brow = reinterpret_cast<const double2 *>(BL + k2a * NX);
-        _Pragma("unroll 2") for (int l = 0; l < NX; l += 2) {
-          const double2 p = brow[l / 2];
-          s += p.x * rec[C::oFx + l * NX + c2a];
-          s += p.y * rec[C::oFx + (l + 1) * NX + c2a];
+      ASLR_UNROLL for (int w = 0; w < NTASK; ++w) {
+        if (w < NXT || ex[w]) {
+          double s = 0.0;
+          const double2 *brow = reinterpret_cast<const double2 *>(BL + k2[w] * NX);
+          _Pragma("unroll 2") for (int l = 0; l < NX; l += 2) {
+            const double2 p = brow[l / 2];
+            s += p.x * rec[C::oFx + l * NX + c2[w]];
+            s += p.y * rec[C::oFx + (l + 1) * NX + c2[w]];
+          }
+          const double v = rec[C::oLxu + c2[w] * NU + k2[w]] + s;
+          QuxL[k2[w] * NX + c2[w]] = v;
+          QuxT[c2[w] * NUP + k2[w]] = v;
+        } else if (eu[w]) {
+          double s = 0.0;
+          const double2 *brow = reinterpret_cast<const double2 *>(BL + k2[w] * NX);
+          _Pragma("unroll 2") for (int l = 0; l < NX; l += 2) {
+            const double2 p = brow[l / 2];
+            s += p.x * rec[C::oFu + l * NU + c2[w]];
+            s += p.y * rec[C::oFu + (l + 1) * NU + c2[w]];
+          }
+          QuuL[k2[w] * NU + c2[w]] = rec[C::oLuu + k2[w] * NU + c2[w]] + s + (k2[w] == c2[w] ? xr : 0.0);
         }
-        const double v = rec[C::oLxu + c2a * NU + k2a] + s;
-        QuxL[k2a * NX + c2a] = v;
-        QuxT[c2a * 8 + k2a] = v;
-      }
-      if (e1x) {
-        double s = 0.0;
-        const double2 *brow = reinterpret_cast<const double2 *>(BL + k2b * NX);
-        _Pragma("unroll 2") for (int l = 0; l < NX; l += 2) {
-          const double2 p = brow[l / 2];
-          s += p.x * rec[C::oFx + l * NX + c2b];
-          s += p.y * rec[C::oFx + (l + 1) * NX + c2b];
-        }
-        const double v = rec[C::oLxu + c2b * NU + k2b] + s;
-        QuxL[k2b * NX + c2b] = v;
-        QuxT[c2b * 8 + k2b] = v;
-      } else if (e1u) {
-        double s = 0.0;
-        const double2 *brow = reinterpret_cast<const double2 *>(BL + k3 * NX);
-        _Pragma("unroll 2") for (int l = 0; l < NX; l += 2) {
-          const double2 p = brow[l / 2];
-          s += p.x * rec[C::oFu + l * NU + c3];
-          s += p.y * rec[C::oFu + (l + 1) * NU + c3];
-        }
-        QuuL[k3 * NU + c3] = rec[C::oLuu + k3 * NU + c3] + s + (k3 == c3 ? xr : 0.0);
       }
       }
       __syncthreads();
       ASLR_PROF(3);
       // ---- gains (wave 0): K = Quu^-1 Qux (one column per lane), k = Quu^-1 Qu, Quu k, Vx, d1, d2, stop ----
-      if (wave0) {
+      if constexpr (C::WAVEQP) {
+        // wide control vectors: the lanes of wave 0 share the knot's problem, every operand in LDS (aslr_wave_gains.hpp)
+        if (wave0) {
+          using WG = WaveGainsLds<NU>;
+          double *WL = sm + C::sWG, *QuukL = sm + C::sQuuk;
+          const double *kvL = WL + WG::oKv;
+          const bool boxed = BOX && box && lim.has[mi]; // block-uniform
+          if (BOX && boxed && tid < NU) { // bounds of the step: the model's limits minus the node's u
+            WL[WG::oLb + tid] = lim.lb[mi][tid] - UKL[tid];
+            WL[WG::oUb + tid] = lim.ub[mi][tid] - UKL[tid];
+          }
+          wave_sync();
+          const WaveQPParams qp{sp.boxqp_maxiter, sp.boxqp_th_acceptstep, sp.boxqp_th_grad, sp.boxqp_reg, ASLR_NALPHA};
+          const bool bad = wave_gains<NU, NX, BOX>(QuuL, QuL, QuxL, KL, WL, boxed, UKL + NUP, qp, nullptr);
+          if (tid < NU) {
+            double s = 0.0;
+            ASLR_UNROLL for (int e = 0; e < NU; ++e) s += QuuL[tid * NU + e] * kvL[e];
+            QuukL[tid] = s;
+          }
+          wave_sync();
+          const int col = tid < NX ? tid : NX - 1;
+          double s = 0.0, s2 = 0.0;
+          ASLR_UNROLL for (int c = 0; c < NU; ++c) {
+            const double kc = kvL[c], qc = QuL[c], qk = QuukL[c], Kc = KL[c * NX + col];
+            d1 += qc * kc; d2 -= kc * qk; stop += qc * qc;
+            s += Kc * qk; s2 += Kc * qc;
+          }
+          Vx_own = QxL[col] + s - 2.0 * s2;
+          if (tid == 0) FlagL[0] = bad ? 1 : 0;
+          if (!bad && tid < NU) { a.kff[tb * NU + tid] = kvL[tid]; a.qu[tb * NU + tid] = QuL[tid]; }
+        }
+      } else if (wave0) {
         double qu[NU], kv[NU], Kc[NU], Quuk[NU];
         const int col = tid < NX ? tid : NX - 1;
         bool bad;
@@ -371,7 +414,7 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
             ASLR_UNROLL for (int e = 0; e < NU; ++e) Quu[c][e] = QuuL[c * NU + e];
             qu[c] = QuL[c]; Kc[c] = QuxL[c * NX + col];
             const double ut = UKL[c];
-            k0[c] = UKL[8 + c];
+            k0[c] = UKL[NUP + c];
             lb[c] = lim.lb[mi][c] - ut;
             ub[c] = lim.ub[mi][c] - ut;
           }
@@ -414,11 +457,11 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
       // ---- Vxx (unsymmetrised, state regularisation on the diagonal), K to HBM ----
       {
         if constexpr (MFMA) {
-          // Qux^T K on the matrix unit too: contraction over the nu controls, padded to 8 with the zeros set at the top
+          // Qux^T K on the matrix unit too: contraction over the nu controls, padded to NUP with the zeros set at the top
           // (rows / columns >= nx read neighbouring LDS: unused results)
           double4_t a0 = {0.0, 0.0, 0.0, 0.0}, a1 = a0;
-          const double *qrow = QuxT + (16 * wv + li) * 8 + lk;
-          ASLR_UNROLL for (int ks = 0; ks < 2; ++ks) {
+          const double *qrow = QuxT + (16 * wv + li) * NUP + lk;
+          ASLR_UNROLL for (int ks = 0; ks < NUP / 4; ++ks) {
             const double pa = qrow[4 * ks];
             const double *krow = KL + (4 * ks + lk) * NX + li;
             a0 = __builtin_amdgcn_mfma_f64_16x16x4f64(pa, krow[0], a0, 0, 0, 0);
@@ -432,10 +475,10 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
               if (rw < NX && cw < NX) AL[rw * NX + cw] = (qxx[ct][q] - acc[ct][q]) + (rw == cw ? xr : 0.0);
             }
         } else {
-          double acc[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, k8[2][8];
+          double acc[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}}, k8[2][NUP];
           ASLR_UNROLL for (int h = 0; h < 2; ++h) {
-            const double2 *qt = reinterpret_cast<const double2 *>(QuxT + row[h] * 8);
-            ASLR_UNROLL for (int c = 0; c < 8; c += 2) { const double2 v = qt[c / 2]; k8[h][c] = v.x; k8[h][c + 1] = v.y; }
+            const double2 *qt = reinterpret_cast<const double2 *>(QuxT + row[h] * NUP);
+            ASLR_UNROLL for (int c = 0; c < NUP; c += 2) { const double2 v = qt[c / 2]; k8[h][c] = v.x; k8[h][c + 1] = v.y; }
           }
           ASLR_UNROLL for (int c = 0; c < NU; ++c) {
             const double2 *kr = reinterpret_cast<const double2 *>(KL + c * NX + 4 * gc);
@@ -456,8 +499,8 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
             }
           }
         }
-        a.kgain[tb * NU * NX + tid] = KL[tid];
-        if (tid + NT < NU * NX) a.kgain[tb * NU * NX + tid + NT] = KL[tid + NT];
+        ASLR_UNROLL for (int w = 0; w < (NU * NX + NT - 1) / NT; ++w)
+          if (NT * (w + 1) <= NU * NX || tid + NT * w < NU * NX) a.kgain[tb * NU * NX + tid + NT * w] = KL[tid + NT * w];
       }
       __syncthreads();
       ASLR_PROF(5);

@@ -1,4 +1,4 @@
-// backward pass instantiated for nx = 28 (7-DoF SEA, nu = 7)
+// backward pass instantiated for nx = 28 (7-DoF arm: SEA, nu = 7; VSA, nu = 14)
 #include "aslr_backward_blk.inc.hpp"
 
 namespace aslr {
@@ -9,6 +9,11 @@ int launch_backward_nx28(const KArgs &k, int nu, int hs, const SolverDev &sd, co
     if (hs <= 0) return launch_backward_blk<28, 7>(k, sd, lim, all_feasible, hs == 0, st); // (-1: vector-FMA products)
     if (hs == 0) hs = k.B <= 8192 ? 2 : 1;
     return hs == 2 ? launch_backward_t<28, 7, 2>(k, sd, lim, all_feasible, st) : launch_backward_t<28, 7, 1>(k, sd, lim, all_feasible, st);
+  }
+  if (nu == 14) { // VSA: the block kernel only (wave-cooperative gains / box QP, aslr_wave_gains.hpp)
+    if (hs <= 0) return launch_backward_blk<28, 14>(k, sd, lim, all_feasible, hs == 0, st);
+    snprintf(err_buf(), kErrLen, "backward: the register-column kernel (ASLR_BWD_HS=%d) is not built for (nx=28, nu=14)", hs);
+    return ASLR_E_INVALID;
   }
   snprintf(err_buf(), kErrLen, "backward: unsupported (nx=28, nu=%d)", nu);
   return ASLR_E_INVALID;

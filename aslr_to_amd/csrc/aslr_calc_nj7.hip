@@ -65,6 +65,7 @@ int launch_quasi_static_nj7(const KArgs &k, int dam, int maxiter, double tol, in
     HIP_TRY(hipGetLastError());
     return ASLR_OK;
   }
+  if (dam == ASLR_DAM_VSA) return launch_quasi_static_nj7_vsa(k, maxiter, tol, iters, st);
   snprintf(err_buf(), kErrLen, "quasi_static: unsupported (nj=7, dam=%d)", dam);
   return ASLR_E_INVALID;
 }

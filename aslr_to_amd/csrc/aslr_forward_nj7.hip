@@ -19,6 +19,7 @@ int launch_forward_nj7(const KArgs &k, int dam, const SolverDev &sd, const Model
     HIP_TRY(hipGetLastError());
     return ASLR_OK;
   }
+  if (dam == ASLR_DAM_VSA) return launch_forward_nj7_vsa(k, sd, lim, st); // (aslr_forward_nj7_vsa.hip)
   snprintf(err_buf(), kErrLen, "forward: unsupported (nj=7, dam=%d)", dam);
   return ASLR_E_INVALID;
 }

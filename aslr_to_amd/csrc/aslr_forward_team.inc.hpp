@@ -1,4 +1,4 @@
-// aslr_forward_team.inc.hpp -- rollout of the larger chain (7-DoF SEA): A TEAM OF 8 LANES PER (trajectory, alpha).
+// aslr_forward_team.inc.hpp -- rollout of the larger chain (7-DoF SEA / VSA): A TEAM OF 8 LANES PER (trajectory, alpha).
 //
 // Same arithmetic as rollout_kernel (aslr_forward.inc.hpp) -- SolverDDP / FDDP / BoxDDP forwardPass, SURVEY.md
 // B.2, B.4, B.5 -- but the knot evaluation, which for a 7-joint chain is 8 recursive Newton-Euler sweeps (one
@@ -9,6 +9,10 @@
 //                 e_c, no velocity, no gravity: adding the exact zeros of the general recursion changes no
 //                 bit), column c of M^-1, entry c of the accelerations and of the Euler step;
 //   lane NJ     : the nonlinear effects (RNEA with the velocity and gravity, zero acceleration).
+//
+// VSA actuation (DAM = ASLR_DAM_VSA, nu = 2 NJ: motor torques, then joint stiffnesses): lane c < NJ takes rows c and
+// NJ + c of the control law and of the box, and the coupling torque of joint c uses the stiffness commanded at the knot
+// (free_fwddyn_vsa.py:34-47; the arithmetic of knot_eval<..., ASLR_DAM_VSA>).
 //
 // All 8 lanes therefore run ONE instruction stream (the general RNEA) on different inputs.  Team-shared data
 // (state, control, joint rotations, M, M^-1) lives in LDS; the teams of a wave never interact, so a
@@ -84,23 +88,25 @@ ASLR_DEV void spd_inverse_col(const double (&A)[N][N], int jc, double (&e)[N]) {
   }
 }
 
-template <int NJ>
+template <int NJ, int DAM = ASLR_DAM_SEA>
 struct FwdTeam {
   static_assert(NJ >= 2 && NJ <= 7, "team of 8 lanes: NJ inertia columns + the nonlinear effects");
-  static constexpr int NX = 4 * NJ, NU = NJ; // SEA
+  static constexpr bool VSA = DAM == ASLR_DAM_VSA;
+  static constexpr int NX = 4 * NJ, NU = VSA ? 2 * NJ : NJ;
   // per-wave stage (doubles): K, us, k, xs, gaps, Vxx f of the current knot
   static constexpr int oK = 0, oU = oK + NU * NX, oKf = oU + NU, oXr = oKf + NU, oFg = oXr + NX, oVf = oFg + NX,
                        STG = (oVf + NX + 1) / 2 * 2;
   static constexpr int NSLOT = (STG + 63) / 64;
   // per-team arrays (doubles)
-  static constexpr int tX = 0, tU = tX + NX, tTc = tU + 8, tTm = tTc + 8, tR = tTm + 8, tM = tR + (NJ * 9 + 1) / 2 * 2,
+  static constexpr int tX = 0, tU = tX + NX, tTc = tU + (VSA ? 16 : 8), tTm = tTc + 8, tR = tTm + 8, tM = tR + (NJ * 9 + 1) / 2 * 2,
                        tMi = tM + 8 * 8, TEAM_LDS = tMi + 8 * 8;
 };
 
-template <int NJ, bool FDDP>
+template <int NJ, bool FDDP, int DAM = ASLR_DAM_SEA>
 __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp, ModelLimits lim) {
-  using C = FwdTeam<NJ>;
+  using C = FwdTeam<NJ, DAM>;
   constexpr int NX = C::NX, NU = C::NU, NSLOT = C::NSLOT;
+  constexpr bool VSA = C::VSA;
   __shared__ double sm[2 * C::STG + 16 * C::TEAM_LDS];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, team = tid >> 3, c = tid & 7;
   const int B = a.B, T = a.T, b = a.b0 + blockIdx.x;
@@ -148,7 +154,7 @@ __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp
   };
 
   // model rows of this lane (reloaded when the node's model changes; wave-uniform)
-  double Krow[NJ], Srow[NJ], Brow[NJ], dt = 0.0, lb_c = 0.0, ub_c = 0.0;
+  double Krow[NJ], Srow[NJ], Brow[NJ], dt = 0.0, lb_c = 0.0, ub_c = 0.0, lb_s = 0.0, ub_s = 0.0; // (lb_s / ub_s: the stiffness row, VSA)
   bool has_lim = false;
   int m_loaded = -1;
   // joint placements and axes: constants of the chain, staged once in LDS (as global loads inside the knot loop they
@@ -199,14 +205,17 @@ __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp
     if (mi != m_loaded) {
       dt = dm.m.dt;
       ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
-        Krow[j] = dm.m.K[cj * NJ + j]; Srow[j] = dm.m.S[cj * NU + j]; Brow[j] = dm.Binv[cj * NJ + j];
+        if (!VSA) { Krow[j] = dm.m.K[cj * NJ + j]; Srow[j] = dm.m.S[cj * NU + j]; }
+        Brow[j] = dm.Binv[cj * NJ + j];
       }
       has_lim = lim.has[mi] != 0;
       lb_c = lim.lb[mi][cj];
       ub_c = lim.ub[mi][cj];
+      if (VSA) { lb_s = lim.lb[mi][NJ + cj]; ub_s = lim.ub[mi][NJ + cj]; }
       // the values are consumed HERE, so the wait for these loads sits inside this rarely-taken branch and not at
       // the join, where it would drain the prefetch of every knot
-      ASLR_UNROLL for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(Krow[j]), "+v"(Srow[j]), "+v"(Brow[j]));
+      if (VSA) { ASLR_UNROLL for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(Brow[j])); asm volatile("" : "+v"(lb_s), "+v"(ub_s)); }
+      else { ASLR_UNROLL for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(Krow[j]), "+v"(Srow[j]), "+v"(Brow[j])); }
       asm volatile("" : "+v"(dt), "+v"(lb_c), "+v"(ub_c));
       m_loaded = mi;
     }
@@ -218,6 +227,13 @@ __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp
       if (box && has_lim) s = fmin(fmax(s, lb_c), ub_c);
       if (jl) uT[c] = s;
       if (team_on && jl) a.us_try[((size_t)ai * TB + tb) * NU + c] = s;
+      if constexpr (VSA) { // row NJ + cj: the stiffness command of joint cj
+        double s2 = stg[C::oU + NJ + cj] - stg[C::oKf + NJ + cj] * alpha;
+        ASLR_UNROLL for (int jx = 0; jx < NX; ++jx) s2 -= stg[C::oK + (NJ + cj) * NX + jx] * (xT[jx] - stg[C::oXr + jx]);
+        if (box && has_lim) s2 = fmin(fmax(s2, lb_s), ub_s);
+        if (jl) uT[NJ + c] = s2;
+        if (team_on && jl) a.us_try[((size_t)ai * TB + tb) * NU + NJ + c] = s2;
+      }
     }
     ASLR_PROF(1);
     // ---- rotation of joint cj ----
@@ -230,7 +246,12 @@ __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp
     // ---- coupling and motor torques, entry cj ----
     if (jl) {
       double s = 0.0, s2 = 0.0;
-      ASLR_UNROLL for (int j = 0; j < NJ; ++j) { s += Krow[j] * (xT[j] - xT[NJ + j]); s2 += Srow[j] * uT[j]; }
+      if constexpr (VSA) { // K = diag(stiffness commands), tau_m = the torque commands (the sum over the zeros of K included)
+        ASLR_UNROLL for (int j = 0; j < NJ; ++j) s += (j == c ? uT[NJ + c] : 0.0) * (xT[j] - xT[NJ + j]);
+        s2 = uT[c];
+      } else {
+        ASLR_UNROLL for (int j = 0; j < NJ; ++j) { s += Krow[j] * (xT[j] - xT[NJ + j]); s2 += Srow[j] * uT[j]; }
+      }
       tcL[c] = s;
       tmL[c] = s2;
     }

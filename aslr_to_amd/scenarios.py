@@ -73,6 +73,28 @@ SPECS = {
                  ("uReg", "control", 1e-2, None)],
         terminal=[("gripperPose", "reach", 1e4, None)],
         stiffness=None, motor_inertia=None, dt=1e-2, solver="SolverDDP", maxiter=100, th_stop=1e-7, T=150),
+    # 7-DoF arm + VSA actuation (nx = 28, nu = 14: seven motor torques, seven joint stiffnesses), SolverBoxDDP.  No
+    # example script in the reference: the cost stack, motor inertia and step are those of examples/two_dof_vsa_boxddp.py
+    # (:29-52) on C5's robot, frame and target.  Two constants differ from that script on purpose: with its terminal
+    # weight 4e4 and a stiffness floor below 1 (0 there; 0.05 tried) trajectories of the seeded batch stop at maxiter or
+    # with the forward-error bit on the CPU restatement, so the terminal weight is 1e3 and the stiffness is boxed to
+    # [1, 50]; with these all 64 trajectories of (B = 64, T = 50, seed = 3) converge there in 5 - 44 iterations.
+    "talos_arm_vsa": dict(
+        robot="talos_arm", gravity=None, actuator="vsa", frame="gripper_left_joint", target=(0.15, 0.35, -0.25),
+        running=[("gripperPose", "reach", 1e0, None), ("xReg", "state", 1e-1, (1.0, 1.0, 1.0, 1.0)),
+                 ("uReg", "control", 1e-1, (1.0,) * 14)],
+        terminal=[("gripperPose", "reach", 1e3, None)],
+        motor_inertia=1e-3, dt=1e-2, u_lb=(-100,) * 7 + (1,) * 7, u_ub=(100,) * 7 + (50,) * 7,
+        solver="SolverBoxDDP", maxiter=300, th_stop=1e-7, T=50),
+    # the same with the torques boxed to +-1 and a control weight of 1e-2: both halves of the box become active (torque
+    # and stiffness commands on their bounds).  Used by the tests only.
+    "talos_arm_vsa_tight": dict(
+        robot="talos_arm", gravity=None, actuator="vsa", frame="gripper_left_joint", target=(0.15, 0.35, -0.25),
+        running=[("gripperPose", "reach", 1e0, None), ("xReg", "state", 1e-1, (1.0, 1.0, 1.0, 1.0)),
+                 ("uReg", "control", 1e-2, (1.0,) * 14)],
+        terminal=[("gripperPose", "reach", 1e3, None)],
+        motor_inertia=1e-3, dt=1e-2, u_lb=(-1,) * 7 + (1,) * 7, u_ub=(1,) * 7 + (50,) * 7,
+        solver="SolverBoxDDP", maxiter=300, th_stop=1e-7, T=50),
 }
 
 
@@ -181,9 +203,16 @@ def talos_arm_sea(B=1, T=150, seed=0):
     return _build("talos_arm_sea", B, T, seed)
 
 
+def talos_arm_vsa(B=1, T=50, seed=0, tight=False):
+    """7-DoF arm with variable-stiffness actuation, SolverBoxDDP (nx = 28, nu = 14); tight: the test variant whose torque
+    bounds are active as well."""
+    return _build("talos_arm_vsa_tight" if tight else "talos_arm_vsa", B, T, seed)
+
+
 SCENARIOS = {"two_dof_vsa_boxddp": two_dof_vsa_boxddp, "two_dof_vsa_modified": two_dof_vsa_modified,
              "two_dof_sea": two_dof_sea,
-             "double_pendulum": double_pendulum, "double_pendulum_nu1": double_pendulum_nu1, "talos_arm_sea": talos_arm_sea}
+             "double_pendulum": double_pendulum, "double_pendulum_nu1": double_pendulum_nu1, "talos_arm_sea": talos_arm_sea,
+             "talos_arm_vsa": talos_arm_vsa}
 
 
 def lower(sc):

@@ -39,6 +39,10 @@ extern "C" {
 #define ASLR_MAX_NJ     7   /* link-side DoF (2-DoF arm, 7-DoF arm)          */
 #define ASLR_MAX_NX     28  /* 4 * ASLR_MAX_NJ                                */
 #define ASLR_MAX_NU     14  /* 2 * ASLR_MAX_NJ (VSA)                          */
+/* Sizes the solver entry points (aslr_backward_pass, aslr_forward_pass, aslr_iterate*, aslr_solve, aslr_solve_pool)
+ * accept: nj = 2 (SEA / VSA / pendulum actuation) and nj = 7 with SEA, every solver; nj = 7 with VSA (nu = 14) with
+ * ASLR_SOLVER_BOXDDP only -- the other solvers return ASLR_E_INVALID for it (model-level entry points and
+ * aslr_quasi_static work for every combination). */
 #define ASLR_MAX_COSTS  6   /* cost terms per CostModelSum                    */
 #define ASLR_MAX_MODELS 4   /* distinct action models per shooting problem    */
 #define ASLR_NALPHA     10  /* Crocoddyl line-search step lengths 2^-j, j<10  */
