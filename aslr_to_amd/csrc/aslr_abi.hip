@@ -17,7 +17,8 @@ char *err_buf() { return g_err_storage; }
 
 namespace {
 
-// per-trajectory solver state at solve() entry
+// per-trajectory solver state at solve() entry (pool_refill_kernel repeats these stores for a refilled slot; sharing
+// them through a device function changes the register allocation and the schedule of both kernels)
 __global__ void init_state_kernel(KArgs a, double reg0, int is_feasible) {
   const int b = a.b0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.b1) return;
@@ -138,12 +139,16 @@ constexpr int kMaxSub = 8;
 struct aslr_problem {
   aslr_problem_desc_t desc; // host copy (pointers nulled)
   int nj, nx, nu, dam, rec;
+  const KernelSet *ks; // the launchers of this size (kKernelSets)
   char *ws;
   int64_t ws_bytes;
   aslr_region_t regions[ASLR_R_COUNT];
   KArgs k;
   int32_t *h_done; // pinned staging for count_active
-  int bwd_hs, blk_mfma; // launch-path switches (ASLR_BWD_HS, ASLR_BLK_MFMA), read from the environment at create time
+  // launch-path switches, read from the environment at create time.  ASLR_BWD_HS: 0 = each size picks its default
+  // decomposition, > 0 forces the register-column kernel with that many lanes per column (tests and comparisons);
+  // ASLR_BLK_MFMA=0: vector-FMA products in the block kernel of nx = 28
+  int bwd_hs, blk_mfma;
   hipEvent_t ev[4];
   bool have_ev;
   // sub-shards (aslr_set_subshards): contiguous trajectory ranges [sub_b[s], sub_b[s + 1]) iterated on their own
@@ -339,16 +344,31 @@ SolverDev to_dev(const aslr_solver_params_t *sp, int standalone, int store_v) {
   return s;
 }
 
-// ---- launch helpers: dispatch to the per-size translation units ----
+// ---- the supported sizes: one row each; aslr_problem_create looks the row up and is the only place that refuses a size ----
+template <int NJ, int DAM>
+constexpr KernelSet kernel_set() {
+  return {NJ, DAM, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
+          launch_quasi_static<NJ, DAM>, launch_forward<NJ, DAM>, launch_backward<NJ, DAM>};
+}
+constexpr KernelSet kKernelSets[] = {
+    kernel_set<2, ASLR_DAM_SEA>(),
+    kernel_set<2, ASLR_DAM_VSA>(),
+    kernel_set<7, ASLR_DAM_SEA>(),
+    kernel_set<7, ASLR_DAM_VSA>(),
+};
+const KernelSet *find_kernel_set(int nj, int dam) {
+  for (const KernelSet &ks : kKernelSets)
+    if (ks.nj == nj && ks.dam == dam) return &ks;
+  return nullptr;
+}
+
+// ---- launch helpers: the handle's state in front of the launchers of its size ----
 int launch_calc(aslr_problem *p, bool diff, int mode, double th_gaptol, hipStream_t st, bool all_computed = false) {
   if (diff && p->const_ok && !(mode & kModeNoCompute)) {
     if (p->const_written) mode |= kModeSkipConst;
     else if (all_computed) p->const_written = true; // this launch writes them
   }
-  if (p->nj == 2) return launch_calc_nj2(p->k, p->dam, diff, mode, th_gaptol, st);
-  if (p->nj == 7) return launch_calc_nj7(p->k, p->dam, diff, mode, th_gaptol, st);
-  snprintf(g_err, sizeof g_err, "unsupported nj=%d", p->nj);
-  return ASLR_E_INVALID;
+  return p->ks->calc(p->k, diff, mode, th_gaptol, st);
 }
 
 ModelLimits make_limits(const aslr_problem *p) {
@@ -361,42 +381,29 @@ ModelLimits make_limits(const aslr_problem *p) {
   return lim;
 }
 
-int backward_hs(const aslr_problem *p) {
-  // 0: each size picks its default decomposition; ASLR_BWD_HS forces the register-column kernel with that
-  // many lanes per column (tests and comparisons).  Read once, when the handle is created.
-  return p->bwd_hs;
-}
-
 // nj = 7 with VSA actuation (nx = 28, nu = 14): the solver kernels are built for SolverBoxDDP, the solver both VSA
 // examples of the reference use.  Without the box the stiffness commands are unconstrained and go negative, so
 // SolverDDP / SolverFDDP stay at the MODEL level for this combination -- calc / calcDiff sweeps, dam_eval,
 // dam_residuals, frame placements, quasi-static controls -- and their solver entry points decline.
 int solver_unsupported(const aslr_problem *p, int solver) {
-  if (p->nj == 7 && p->dam == ASLR_DAM_VSA && solver != ASLR_SOLVER_BOXDDP) {
-    snprintf(g_err, sizeof g_err, "the solver kernels for (nj=7, VSA) are built for SolverBoxDDP only: model-level evaluation only with SolverDDP / SolverFDDP");
+  if (p->ks->boxddp_only && solver != ASLR_SOLVER_BOXDDP) {
+    snprintf(g_err, sizeof g_err, "the solver kernels for (nj=%d, VSA) are built for SolverBoxDDP only: model-level evaluation only with SolverDDP / SolverFDDP", p->nj);
     return ASLR_E_INVALID;
   }
   return ASLR_OK;
 }
 
-int launch_backward(aslr_problem *p, const SolverDev &sd, hipStream_t st, bool all_feasible = false) {
+int launch_backward(aslr_problem *p, const SolverDev &sd, hipStream_t st) {
   if (int rc = solver_unsupported(p, sd.solver)) return rc;
-  const int hs = backward_hs(p);
-  const ModelLimits lim = make_limits(p);
-  if (p->nx == 8) return launch_backward_nx8(p->k, p->nu, hs, sd, lim, all_feasible, st);
-  if (p->nx == 28) return launch_backward_nx28(p->k, p->nu, (hs == 0 && !p->blk_mfma) ? -1 : hs, sd, lim, all_feasible, st);
-  snprintf(g_err, sizeof g_err, "unsupported (nx=%d, nu=%d)", p->nx, p->nu);
-  return ASLR_E_INVALID;
+  return p->ks->backward(p->k, p->bwd_hs, p->blk_mfma != 0, sd, make_limits(p), st);
 }
 
 int launch_forward(aslr_problem *p, const SolverDev &sd, hipStream_t st) {
   if (int rc = solver_unsupported(p, sd.solver)) return rc;
-  const ModelLimits lim = make_limits(p);
-  if (p->nj == 2) return launch_forward_nj2(p->k, p->dam, sd, lim, st);
-  if (p->nj == 7) return launch_forward_nj7(p->k, p->dam, sd, lim, st);
-  snprintf(g_err, sizeof g_err, "unsupported nj=%d", p->nj);
-  return ASLR_E_INVALID;
+  return p->ks->forward(p->k, sd, make_limits(p), st);
 }
+
+double reg_start(const aslr_solver_params_t *sp) { return std::isnan(sp->reg_init) ? sp->reg_min : sp->reg_init; }
 
 } // namespace
 
@@ -459,8 +466,9 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   if (!desc->node_model || !desc->x0) return ASLR_E_INVALID;
   for (int t = 0; t <= desc->T; ++t)
     if (desc->node_model[t] < 0 || desc->node_model[t] >= desc->nmodels) return ASLR_E_INVALID;
-  if (!(nj == 2 || nj == 7)) {
-    snprintf(g_err, sizeof g_err, "unsupported nj=%d: built for nj=2 and nj=7 (SEA / VSA)", nj);
+  const KernelSet *ks = find_kernel_set(nj, dam);
+  if (!ks) {
+    snprintf(g_err, sizeof g_err, "unsupported (nj=%d, dam=%d): built for nj=2 and nj=7 (SEA / VSA)", nj, dam);
     return ASLR_E_INVALID;
   }
   int ndev = 0;
@@ -475,6 +483,7 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   p->desc = *desc;
   p->desc.node_model = nullptr; p->desc.x0 = nullptr; p->desc.frame_ref = nullptr;
   p->nj = nj; p->nx = nx; p->nu = nu; p->dam = dam; p->rec = rec_len_c(nx, nu);
+  p->ks = ks;
   p->const_written = false;
   p->const_ok = true; // every cost type but the pendulum cost has a knot-independent diagonal Hessian outside Lqq
   for (int i = 0; i < desc->nmodels; ++i)
@@ -598,8 +607,7 @@ int iterate_range(aslr_problem *p, const aslr_solver_params_t *sp, int first, in
   p->k.b0 = b0; p->k.b1 = b1; // (the launch helpers read p->k; restored below)
   int rc = ASLR_OK;
   if (first) {
-    const double reg0 = std::isnan(sp->reg_init) ? sp->reg_min : sp->reg_init;
-    hipLaunchKernelGGL(init_state_kernel, dim3((b1 - b0 + 255) / 256), dim3(256), 0, st, p->k, reg0, sp->is_feasible);
+    hipLaunchKernelGGL(init_state_kernel, dim3((b1 - b0 + 255) / 256), dim3(256), 0, st, p->k, reg_start(sp), sp->is_feasible);
     if (hipGetLastError() != hipSuccess) rc = ASLR_E_HIP;
   }
   SolverDev sd = to_dev(sp, 0, 0);
@@ -691,8 +699,7 @@ int aslr_iterate_timed(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_
     p->have_ev = true;
   }
   if (first) {
-    const double reg0 = std::isnan(sp->reg_init) ? sp->reg_min : sp->reg_init;
-    hipLaunchKernelGGL(init_state_kernel, dim3((p->desc.B + 255) / 256), dim3(256), 0, st, p->k, reg0, sp->is_feasible);
+    hipLaunchKernelGGL(init_state_kernel, dim3((p->desc.B + 255) / 256), dim3(256), 0, st, p->k, reg_start(sp), sp->is_feasible);
     HIP_TRY(hipGetLastError());
   }
   const SolverDev sd = to_dev(sp, 0, 0); // (whole shard on the caller's stream, whatever aslr_set_subshards says)
@@ -779,7 +786,7 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
   pl.x0 = pool->x0; pl.frame_ref = pool->frame_ref; pl.xs_out = pool->xs_out; pl.us_out = pool->us_out;
   pl.xs_init = pool->xs_init; pl.us_init = pool->us_init;
   pl.stat_f = pool->stat_f; pl.stat_i = pool->stat_i; pl.slot_problem = pool->slot_problem; pl.counters = pool->counters;
-  const double reg0 = std::isnan(sp->reg_init) ? sp->reg_min : sp->reg_init;
+  const double reg0 = reg_start(sp);
   // every slot starts idle; the first refill hands out the first B problems
   HIP_TRY(hipMemsetAsync(pool->slot_problem, 0xFF, sizeof(int32_t) * B, st));
   HIP_TRY(hipMemsetAsync(pool->counters, 0, sizeof(int32_t) * 2, st));
@@ -800,9 +807,18 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
   // the slowest possible schedule: every problem takes maxiter iterations, one wave of B problems after the other
   const long long cap = ((long long)(pool->P + B - 1) / B + 1) * (long long)(sp->maxiter + refill_every);
   bool first = true;
-  while (it < cap) {
+  auto refill = [&] { // flush the stopped slots and hand them their next problems
     hipLaunchKernelGGL(pool_refill_kernel, dim3(B), dim3(64), 0, st, p->k, pl, reg0, sp->is_feasible);
-    if (hipGetLastError() != hipSuccess) { rc = ASLR_E_HIP; break; }
+    return hipGetLastError() == hipSuccess;
+  };
+  auto flush_and_count = [&](int32_t *fin) { // ... and read how many problems have been written out so far
+    if (!refill() || hipMemcpyAsync(p->h_done, pool->counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) return false;
+    *fin = p->h_done[0];
+    return true;
+  };
+  while (it < cap) {
+    if (!refill()) { rc = ASLR_E_HIP; break; }
     // (the first sweep covers every slot when the pool fills them all: it puts the model-only record chunks in place)
     p->const_pending_full = first && pool->P >= B && !p->const_written;
     rc = aslr_iterate_n(p, &spi, 0, refill_every, stream);
@@ -812,22 +828,13 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
     if (it % poll_every < refill_every) {
       int32_t fin = 0;
       // (flush before counting: the kernel above ran before these iterations)
-      hipLaunchKernelGGL(pool_refill_kernel, dim3(B), dim3(64), 0, st, p->k, pl, reg0, sp->is_feasible);
-      if (hipGetLastError() != hipSuccess ||
-          hipMemcpyAsync(p->h_done, pool->counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) { rc = ASLR_E_HIP; break; }
-      fin = p->h_done[0];
+      if (!flush_and_count(&fin)) { rc = ASLR_E_HIP; break; }
       if (fin >= pool->P) break;
     }
   }
   int32_t fin_total = -1;
-  if (!rc) { // one more flush, then every problem must have been written out
-    hipLaunchKernelGGL(pool_refill_kernel, dim3(B), dim3(64), 0, st, p->k, pl, reg0, sp->is_feasible);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(p->h_done, pool->counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) rc = ASLR_E_HIP;
-    else fin_total = p->h_done[0];
-  }
+  // one more flush, then every problem must have been written out
+  if (!rc && !flush_and_count(&fin_total)) rc = ASLR_E_HIP;
   p->pool_maxiter = 0;
   p->k = saved;
   {
@@ -851,10 +858,7 @@ int aslr_dam_eval(aslr_problem_t *p, int32_t model_index, int32_t n, const doubl
                   void *stream) {
   if (!p || n <= 0 || model_index < 0 || model_index >= p->desc.nmodels || !x || !u) return ASLR_E_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (p->nj == 2) return launch_dam_eval_nj2(p->k, p->dam, model_index, n, x, u, xout, cost, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu, st);
-  if (p->nj == 7) return launch_dam_eval_nj7(p->k, p->dam, model_index, n, x, u, xout, cost, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu, st);
-  snprintf(g_err, sizeof g_err, "unsupported nj=%d", p->nj);
-  return ASLR_E_INVALID;
+  return p->ks->dam_eval(p->k, model_index, n, x, u, xout, cost, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu, st);
 }
 
 int32_t aslr_residual_len(const aslr_model_t *m, int32_t nj) {
@@ -879,10 +883,7 @@ int aslr_dam_residuals(aslr_problem_t *p, int32_t model_index, int32_t n, const 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nr = aslr_residual_len(&p->desc.models[model_index], p->nj);
   if (nr <= 0) return nr < 0 ? nr : ASLR_OK;
-  if (p->nj == 2) return launch_dam_residuals_nj2(p->k, p->dam, model_index, n, x, u, r, nr, st);
-  if (p->nj == 7) return launch_dam_residuals_nj7(p->k, p->dam, model_index, n, x, u, r, nr, st);
-  snprintf(g_err, sizeof g_err, "unsupported nj=%d", p->nj);
-  return ASLR_E_INVALID;
+  return p->ks->dam_residuals(p->k, model_index, n, x, u, r, nr, st);
 }
 
 int aslr_frame_placement(aslr_problem_t *p, int32_t frame_joint, const double *frame_R, const double *frame_p, int32_t n,
@@ -893,10 +894,7 @@ int aslr_frame_placement(aslr_problem_t *p, int32_t frame_joint, const double *f
   FrameArg F;
   for (int i = 0; i < 9; ++i) F.R[i] = frame_R[i];
   for (int i = 0; i < 3; ++i) F.p[i] = frame_p[i];
-  if (p->nj == 2) return launch_frame_placement_nj2(p->k, frame_joint, F, n, x, x_stride, oMf, st);
-  if (p->nj == 7) return launch_frame_placement_nj7(p->k, frame_joint, F, n, x, x_stride, oMf, st);
-  snprintf(g_err, sizeof g_err, "unsupported nj=%d", p->nj);
-  return ASLR_E_INVALID;
+  return p->ks->frame_placement(p->k, frame_joint, F, n, x, x_stride, oMf, st);
 }
 
 int aslr_set_iteration_log(aslr_problem_t *p, double *log, int32_t capacity) {
@@ -909,10 +907,7 @@ int aslr_set_iteration_log(aslr_problem_t *p, double *log, int32_t capacity) {
 int aslr_quasi_static(aslr_problem_t *p, int32_t maxiter, double tol, int32_t *iters_dev, void *stream) {
   if (!p || maxiter <= 0) return ASLR_E_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (p->nj == 2) return launch_quasi_static_nj2(p->k, p->dam, maxiter, tol, iters_dev, st);
-  if (p->nj == 7) return launch_quasi_static_nj7(p->k, p->dam, maxiter, tol, iters_dev, st);
-  snprintf(g_err, sizeof g_err, "unsupported nj=%d", p->nj);
-  return ASLR_E_INVALID;
+  return p->ks->quasi_static(p->k, maxiter, tol, iters_dev, st);
 }
 
 const char *aslr_last_error(void) { return g_err; }

@@ -847,19 +847,47 @@ __global__ void __launch_bounds__(64, (HS >= 4 ? ASLR_BWD_WAVES : (BwdCfg<NX, NU
 #endif
 }
 
-// `all_feasible`: the caller knows every trajectory of the shard is feasible (no gap terms needed)
+// (GAPS = true always: a solve starts from an infeasible candidate unless the caller proves otherwise, and no caller does)
 template <int NX, int NU, int HS, int TPWA = 0>
-int launch_backward_t(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, bool all_feasible, hipStream_t st) {
+int launch_backward_t(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st) {
   using C = BwdCfg<NX, NU, HS, TPWA>;
   const int blocks = (k.b1 - k.b0 + C::TPW - 1) / C::TPW;
   const size_t lds = C::DMA ? 0 : (size_t)C::TPW * C::LDS_TEAM * sizeof(double); // (DMA: allocated statically)
-  const bool box = sd.solver == ASLR_SOLVER_BOXDDP;
-  if (box && !all_feasible) hipLaunchKernelGGL((backward_kernel<NX, NU, HS, TPWA, true, true>), dim3(blocks), dim3(64), lds, st, k, sd, lim);
-  else if (box) hipLaunchKernelGGL((backward_kernel<NX, NU, HS, TPWA, true, false>), dim3(blocks), dim3(64), lds, st, k, sd, lim);
-  else if (!all_feasible) hipLaunchKernelGGL((backward_kernel<NX, NU, HS, TPWA, false, true>), dim3(blocks), dim3(64), lds, st, k, sd, lim);
-  else hipLaunchKernelGGL((backward_kernel<NX, NU, HS, TPWA, false, false>), dim3(blocks), dim3(64), lds, st, k, sd, lim);
+  with_bool(sd.solver == ASLR_SOLVER_BOXDDP, [&](auto BOX) {
+    hipLaunchKernelGGL((backward_kernel<NX, NU, HS, TPWA, decltype(BOX)::value, true>), dim3(blocks), dim3(64), lds, st, k, sd, lim);
+  });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
+}
+
+// =================================================================================================
+// launcher (declared in aslr_common.hpp): the default decomposition of each size
+// =================================================================================================
+template <int NX, int NU>
+int launch_backward_blk(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, bool mfma, hipStream_t st); // aslr_backward_blk.inc.hpp (nx = 28)
+
+template <int NJ, int DAM>
+int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, const ModelLimits &lim, hipStream_t st) {
+  constexpr int NX = 4 * NJ, NU = ModelDims<NJ, DAM>::nu;
+  if constexpr (NX == 8) {
+    // wider teams when the batch cannot fill the chip: 1024 trajectories (C2) are 256 waves with 16 lanes each and 512 with 32
+    // (measured at nu = 2: 148 -> 134 us per sweep).  At nu = 4 two 32-lane teams per wave win as long as ALL sub-shards
+    // together stay at one wave per SIMD (whole shard <= 2048 trajectories: 345 -> 334 us BoxDDP, 184 -> 161 us DDP at 1024) and
+    // lose beyond (two waves per SIMD: the gains phase is per-wave work)
+    if (hs == 0) hs = ((NU == 2 && k.b1 - k.b0 <= 2048) || k.B <= 2048) ? 4 : (k.B <= 8192 ? 2 : 1);
+    if (hs == 4) return launch_backward_t<NX, NU, 4>(k, sd, lim, st);
+    return hs == 2 ? launch_backward_t<NX, NU, 2>(k, sd, lim, st) : launch_backward_t<NX, NU, 1>(k, sd, lim, st);
+  } else {
+    // hs: 0 = default (block-per-trajectory LDS kernel, all three solvers; vector-FMA products without mfma, as for hs < 0),
+    //     1 / 2 = force the register-column kernel with that many lanes per column (tests, comparisons)
+    if (hs <= 0) return launch_backward_blk<NX, NU>(k, sd, lim, mfma && hs == 0, st);
+    if constexpr (SizeTraits<NJ, DAM>::reg_column) {
+      return hs == 2 ? launch_backward_t<NX, NU, 2>(k, sd, lim, st) : launch_backward_t<NX, NU, 1>(k, sd, lim, st);
+    } else { // VSA: the block kernel only (wave-cooperative gains / box QP, aslr_wave_gains.hpp)
+      snprintf(err_buf(), kErrLen, "backward: the register-column kernel (ASLR_BWD_HS=%d) is not built for (nx=%d, nu=%d)", hs, NX, NU);
+      return ASLR_E_INVALID;
+    }
+  }
 }
 
 } // namespace aslr

@@ -597,20 +597,15 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
 }
 
 template <int NX, int NU>
-int launch_backward_blk(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, bool all_feasible, bool mfma, hipStream_t st) {
+int launch_backward_blk(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, bool mfma, hipStream_t st) {
   // mfma = false (ASLR_BLK_MFMA=0 when the handle was created) selects the vector-FMA products (comparison runs; both
-  // paths give the same bits)
+  // paths give the same bits).  Gap terms are compiled in for every solver: a cold-started solve is infeasible at first.
   const dim3 grid(k.b1 - k.b0), block(BwdBlk<NX, NU>::NT);
-  if (sd.solver == ASLR_SOLVER_BOXDDP) { // (gap terms compiled in: a cold-started BoxDDP solve is infeasible at first)
-    if (mfma) hipLaunchKernelGGL((backward_blk_kernel<NX, NU, true, true, true>), grid, block, 0, st, k, sd, lim);
-    else hipLaunchKernelGGL((backward_blk_kernel<NX, NU, true, false, true>), grid, block, 0, st, k, sd, lim);
-  } else if (mfma) {
-    if (all_feasible) hipLaunchKernelGGL((backward_blk_kernel<NX, NU, false, true>), grid, block, 0, st, k, sd, lim);
-    else hipLaunchKernelGGL((backward_blk_kernel<NX, NU, true, true>), grid, block, 0, st, k, sd, lim);
-  } else {
-    if (all_feasible) hipLaunchKernelGGL((backward_blk_kernel<NX, NU, false, false>), grid, block, 0, st, k, sd, lim);
-    else hipLaunchKernelGGL((backward_blk_kernel<NX, NU, true, false>), grid, block, 0, st, k, sd, lim);
-  }
+  with_bool(mfma, [&](auto MFMA) {
+    with_bool(sd.solver == ASLR_SOLVER_BOXDDP, [&](auto BOX) {
+      hipLaunchKernelGGL((backward_blk_kernel<NX, NU, true, decltype(MFMA)::value, decltype(BOX)::value>), grid, block, 0, st, k, sd, lim);
+    });
+  });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -372,21 +372,75 @@ __global__ void __launch_bounds__(64) frame_placement_kernel(const DevDesc *desc
   o[9] = oMf.p.x; o[10] = oMf.p.y; o[11] = oMf.p.z;
 }
 
-template <int NJ>
-int launch_frame_placement_t(const KArgs &k, int fj, const FrameArg &F, int n, const double *x, int64_t stride, double *out,
-                             hipStream_t st) {
-  dim3 grid((n + 63) / 64), block(64);
-  if (k.planar) hipLaunchKernelGGL((frame_placement_kernel<NJ, true>), grid, block, 0, st, k.desc, fj, F, n, x, (long long)stride, out);
-  else hipLaunchKernelGGL((frame_placement_kernel<NJ, false>), grid, block, 0, st, k.desc, fj, F, n, x, (long long)stride, out);
+// =================================================================================================
+// launchers (declared in aslr_common.hpp; SizeTraits there says what differs between the sizes)
+// =================================================================================================
+template <int NJ, int PHASE> __global__ void dyn_team_kernel(KArgs a, int mode); // aslr_calc_team.inc.hpp (SizeTraits::team_dyn)
+
+template <int NJ, int DAM>
+int launch_calc(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st) {
+  using S = SizeTraits<NJ, DAM>;
+  const dim3 grid((k.b1 - k.b0 + 63) / 64, k.T + 1), block(64);
+  with_planar<NJ>(k, [&](auto P) {
+    constexpr bool PLANAR = decltype(P)::value, PRE = S::team_dyn;
+    if (!diff) {
+      hipLaunchKernelGGL((calc_kernel<NJ, DAM, false, PLANAR>), grid, block, 0, st, k, mode, th_gaptol);
+      return;
+    }
+    if constexpr (PRE) { // rigid-body part by 8-lane teams (aslr_calc_team.inc.hpp), then products + costs + record per lane
+      const dim3 tgrid((k.b1 - k.b0 + 7) / 8, k.T + 1);
+      hipLaunchKernelGGL((dyn_team_kernel<NJ, 0>), tgrid, block, 0, st, k, mode);
+      hipLaunchKernelGGL((dyn_team_kernel<NJ, 1>), tgrid, block, 0, st, k, mode);
+    }
+    if constexpr (S::skip_const) {
+      if (mode & kModeSkipConst) {
+        hipLaunchKernelGGL((calc_kernel<NJ, DAM, true, PLANAR, PRE, true>), grid, block, 0, st, k, mode, th_gaptol);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((calc_kernel<NJ, DAM, true, PLANAR, PRE>), grid, block, 0, st, k, mode, th_gaptol);
+  });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }
 
 template <int NJ, int DAM>
-int launch_dam_residuals_t(const KArgs &k, int mi, int n, const double *x, const double *u, double *r, int nr, hipStream_t st) {
-  dim3 grid((n + 63) / 64), block(64);
-  if (k.planar) hipLaunchKernelGGL((dam_residual_kernel<NJ, DAM, true>), grid, block, 0, st, k.desc, mi, k.frame_ref, n, x, u, r, nr);
-  else hipLaunchKernelGGL((dam_residual_kernel<NJ, DAM, false>), grid, block, 0, st, k.desc, mi, k.frame_ref, n, x, u, r, nr);
+int launch_dam_eval(const KArgs &k, int mi, int n, const double *x, const double *u, double *xout, double *cost, double *Fx,
+                    double *Fu, double *Lx, double *Lu, double *Lxx, double *Lxu, double *Luu, hipStream_t st) {
+  const dim3 grid((n + 63) / 64), block(64);
+  with_planar<NJ>(k, [&](auto P) {
+    hipLaunchKernelGGL((dam_eval_kernel<NJ, DAM, decltype(P)::value>), grid, block, 0, st, k.desc, mi, k.frame_ref, n, x, u, xout, cost, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu);
+  });
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
+
+template <int NJ, int DAM>
+int launch_dam_residuals(const KArgs &k, int mi, int n, const double *x, const double *u, double *r, int nr, hipStream_t st) {
+  const dim3 grid((n + 63) / 64), block(64);
+  with_planar<NJ>(k, [&](auto P) {
+    hipLaunchKernelGGL((dam_residual_kernel<NJ, DAM, decltype(P)::value>), grid, block, 0, st, k.desc, mi, k.frame_ref, n, x, u, r, nr);
+  });
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
+
+template <int NJ>
+int launch_frame_placement(const KArgs &k, int fj, const FrameArg &F, int n, const double *x, int64_t stride, double *out, hipStream_t st) {
+  const dim3 grid((n + 63) / 64), block(64);
+  with_planar<NJ>(k, [&](auto P) {
+    hipLaunchKernelGGL((frame_placement_kernel<NJ, decltype(P)::value>), grid, block, 0, st, k.desc, fj, F, n, x, (long long)stride, out);
+  });
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
+
+template <int NJ, int DAM>
+int launch_quasi_static(const KArgs &k, int maxiter, double tol, int32_t *iters, hipStream_t st) {
+  const dim3 grid((k.B + 63) / 64, k.T), block(64);
+  with_planar<NJ>(k, [&](auto P) {
+    hipLaunchKernelGGL((quasi_static_kernel<NJ, DAM, decltype(P)::value>), grid, block, 0, st, k, maxiter, tol, iters);
+  });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "aslr_device.hpp"
 
@@ -128,31 +129,72 @@ constexpr int kModeSolver = 2;    // honour RECALC/DONE flags and compute gaps
 constexpr int kModeNoCompute = 4;
 constexpr int kModeSkipConst = 8; // record chunks that depend on the model only are in place already: do not rewrite them
 
-// launchers, one translation unit per (kernel family, size)
-int launch_calc_nj2(const KArgs &k, int dam, bool diff, int mode, double th_gaptol, hipStream_t st);
-int launch_calc_nj7(const KArgs &k, int dam, bool diff, int mode, double th_gaptol, hipStream_t st);
-int launch_dam_eval_nj2(const KArgs &k, int dam, int mi, int n, const double *x, const double *u, double *xout,
-                        double *cost, double *Fx, double *Fu, double *Lx, double *Lu, double *Lxx, double *Lxu,
-                        double *Luu, hipStream_t st);
-int launch_dam_eval_nj7(const KArgs &k, int dam, int mi, int n, const double *x, const double *u, double *xout,
-                        double *cost, double *Fx, double *Fu, double *Lx, double *Lu, double *Lxx, double *Lxu,
-                        double *Luu, hipStream_t st);
-int launch_dam_residuals_nj2(const KArgs &k, int dam, int mi, int n, const double *x, const double *u, double *r, int nr, hipStream_t st);
-int launch_dam_residuals_nj7(const KArgs &k, int dam, int mi, int n, const double *x, const double *u, double *r, int nr, hipStream_t st);
 struct FrameArg { double R[9], p[3]; }; // local placement of a frame on its joint, by value
-int launch_frame_placement_nj2(const KArgs &k, int fj, const FrameArg &F, int n, const double *x, int64_t stride, double *out, hipStream_t st);
-int launch_frame_placement_nj7(const KArgs &k, int fj, const FrameArg &F, int n, const double *x, int64_t stride, double *out, hipStream_t st);
-int launch_calc_nj7_vsa(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st);
-int launch_dam_eval_nj7_vsa(const KArgs &k, int mi, int n, const double *x, const double *u, double *xout, double *cost,
-                            double *Fx, double *Fu, double *Lx, double *Lu, double *Lxx, double *Lxu, double *Luu, hipStream_t st);
-int launch_dam_residuals_nj7_vsa(const KArgs &k, int mi, int n, const double *x, const double *u, double *r, int nr, hipStream_t st);
-int launch_quasi_static_nj7_vsa(const KArgs &k, int maxiter, double tol, int32_t *iters, hipStream_t st);
-int launch_forward_nj7_vsa(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
-int launch_quasi_static_nj2(const KArgs &k, int dam, int maxiter, double tol, int32_t *iters, hipStream_t st);
-int launch_quasi_static_nj7(const KArgs &k, int dam, int maxiter, double tol, int32_t *iters, hipStream_t st);
-int launch_backward_nx8(const KArgs &k, int nu, int hs, const SolverDev &sd, const ModelLimits &lim, bool all_feasible, hipStream_t st);
-int launch_backward_nx28(const KArgs &k, int nu, int hs, const SolverDev &sd, const ModelLimits &lim, bool all_feasible, hipStream_t st);
-int launch_forward_nj2(const KArgs &k, int dam, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
-int launch_forward_nj7(const KArgs &k, int dam, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
+
+// ---- the launch layer ----
+// What differs between the supported sizes (nj joints, DAM actuation: nx = 4 nj, nu = nj or 2 nj), as compile-time facts.
+// Everything else about a launch is written once per kernel family, in the launcher at the end of its .inc.hpp.
+template <int NJ, int DAM>
+struct SizeTraits {
+  static constexpr bool big_vsa = NJ == 7 && DAM == ASLR_DAM_VSA;
+  // calcDiff: rigid-body part by 8-lane teams (dyn_team_kernel phases 0 and 1), then calc_kernel with PRE
+  static constexpr bool team_dyn = NJ == 7 && DAM == ASLR_DAM_SEA;
+  static constexpr bool skip_const = NJ == 2 || team_dyn; // a calcDiff variant without the model-only record chunks is built
+  static constexpr bool team_rollout = NJ == 7;           // forward: one block of 8-lane teams per trajectory
+  // (7, VSA): the solver kernels are built for SolverBoxDDP only (aslr_abi.hip, solver_unsupported): no FDDP rollout
+  static constexpr bool boxddp_only = big_vsa;
+  static constexpr int cost_tag = big_vsa ? 14 : NJ;      // instantiation tag of sum_cost_kernel / select_kernel
+  static constexpr bool reg_column = !big_vsa;            // backward: the register-column kernel (ASLR_BWD_HS > 0) is built
+};
+
+// a run-time bool as a template argument: f(std::true_type) or f(std::false_type)
+template <class F>
+void with_bool(bool b, F &&f) {
+  if (b) f(std::true_type{}); else f(std::false_type{});
+}
+// the PLANAR argument of a launch: planar kernels exist for nj = 2 only (picked when k.planar); nj = 7 always launches
+// PLANAR = false, whatever k.planar says
+template <int NJ, class F>
+void with_planar(const KArgs &k, F &&f) {
+  if constexpr (NJ == 2) with_bool(k.planar != 0, f); else f(std::false_type{});
+}
+
+// One launcher per kernel family, defined in the family's .inc.hpp and explicitly instantiated in the translation unit
+// of the size.  frame_placement does not depend on the actuation: one instantiation per nj.
+template <int NJ, int DAM> int launch_calc(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st);
+template <int NJ, int DAM> int launch_dam_eval(const KArgs &k, int mi, int n, const double *x, const double *u, double *xout, double *cost,
+                                               double *Fx, double *Fu, double *Lx, double *Lu, double *Lxx, double *Lxu, double *Luu, hipStream_t st);
+template <int NJ, int DAM> int launch_dam_residuals(const KArgs &k, int mi, int n, const double *x, const double *u, double *r, int nr, hipStream_t st);
+template <int NJ> int launch_frame_placement(const KArgs &k, int fj, const FrameArg &F, int n, const double *x, int64_t stride, double *out, hipStream_t st);
+template <int NJ, int DAM> int launch_quasi_static(const KArgs &k, int maxiter, double tol, int32_t *iters, hipStream_t st);
+template <int NJ, int DAM> int launch_forward(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
+// hs: ASLR_BWD_HS (0: the size's default decomposition); mfma: ASLR_BLK_MFMA (block kernel of nx = 28 only)
+template <int NJ, int DAM> int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
+
+// the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
+struct KernelSet {
+  int nj, dam;
+  bool boxddp_only;
+  decltype(&launch_calc<2, 0>) calc;
+  decltype(&launch_dam_eval<2, 0>) dam_eval;
+  decltype(&launch_dam_residuals<2, 0>) dam_residuals;
+  decltype(&launch_frame_placement<2>) frame_placement;
+  decltype(&launch_quasi_static<2, 0>) quasi_static;
+  decltype(&launch_forward<2, 0>) forward;
+  decltype(&launch_backward<2, 0>) backward;
+};
+
+#ifdef ASLR_BWD_PROFILE
+// profile builds only: read / reset the region table of THIS translation unit (static like the table itself; each unit
+// exports it under its own name: aslr_debug_bwd_prof, _bwd_prof28, _calc_prof, _fwd_prof7, tools/*_regions*.py)
+static int prof_table(unsigned long long *out32, int reset) {
+  if (out32 && hipMemcpyFromSymbol(out32, HIP_SYMBOL(aslr_bwd_prof_dev), 32 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long z[32] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(aslr_bwd_prof_dev), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#endif
 
 } // namespace aslr

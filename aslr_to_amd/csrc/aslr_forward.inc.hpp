@@ -358,4 +358,68 @@ __global__ void __launch_bounds__(64) select_kernel(KArgs a, SolverDev sp) {
   ASLR_STAMP_NEXT();
 }
 
+// =================================================================================================
+// launcher (declared in aslr_common.hpp; SizeTraits there says what differs between the sizes)
+// =================================================================================================
+template <int NJ, bool FDDP, int DAM> __global__ void rollout_team_kernel(KArgs a, SolverDev sp, ModelLimits lim); // aslr_forward_team.inc.hpp (SizeTraits::team_rollout)
+
+template <int NJ, int DAM>
+int launch_forward(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st) {
+  using S = SizeTraits<NJ, DAM>;
+  const int nb = k.b1 - k.b0; // trajectories of this launch
+  const int T = k.T, cgx = (nb + 63) / 64;
+  const dim3 block(64), sgrid(cgx), ugrid(cgx, ASLR_NALPHA);
+  const bool fddp = sd.solver == ASLR_SOLVER_FDDP;
+  if constexpr (S::team_rollout) {
+    // one block of 16 eight-lane teams per trajectory (aslr_forward_team.inc.hpp)
+    if constexpr (S::boxddp_only) hipLaunchKernelGGL((rollout_team_kernel<NJ, false, DAM>), dim3(nb), dim3(128), 0, st, k, sd, lim);
+    else if (fddp) hipLaunchKernelGGL((rollout_team_kernel<NJ, true, DAM>), dim3(nb), dim3(128), 0, st, k, sd, lim);
+    else hipLaunchKernelGGL((rollout_team_kernel<NJ, false, DAM>), dim3(nb), dim3(128), 0, st, k, sd, lim);
+    hipLaunchKernelGGL((trial_cost_kernel<NJ, DAM, false>), dim3(cgx, T + 1, ASLR_NALPHA), block, 0, st, k, sd);
+  } else with_planar<NJ>(k, [&](auto P) {
+    constexpr bool PLANAR = decltype(P)::value, CANFAST = PLANAR;
+    const dim3 grid((nb + ASLR_ROLLOUT_TPW - 1) / ASLR_ROLLOUT_TPW);
+    const bool fast = CANFAST && k.planar_reach;
+    auto rollout = [&](const KArgs &a) {
+      if (fddp) hipLaunchKernelGGL((rollout_kernel<NJ, DAM, PLANAR, true>), grid, block, 0, st, a, sd, lim);
+      else hipLaunchKernelGGL((rollout_kernel<NJ, DAM, PLANAR, false>), grid, block, 0, st, a, sd, lim);
+    };
+    auto costs = [&](const KArgs &a) { // knots [a.seg_t0, a.seg_t1]
+      const dim3 cgrid(cgx, a.seg_t1 - a.seg_t0 + 1, ASLR_NALPHA);
+      if constexpr (CANFAST) {
+        if (fast) { hipLaunchKernelGGL((trial_cost_kernel<NJ, DAM, PLANAR, true>), cgrid, block, 0, st, a, sd); return; }
+      }
+      hipLaunchKernelGGL((trial_cost_kernel<NJ, DAM, PLANAR, false>), cgrid, block, 0, st, a, sd);
+    };
+    const int nseg = k.pipeline >= 2 ? (k.pipeline <= 4 ? k.pipeline : 4) : (k.pipeline == 1 ? 2 : 1); // (1: two segments, n >= 2: n)
+    if (PLANAR && nseg > 1 && !fast && T >= 16) {
+      // rollout of the first segment; then launches in which the rollout continues over the next segment while the trial costs
+      // of the previous one are evaluated next to it; then the trial costs of the last segment
+      int lo = 0, hi = T / nseg;
+      KArgs a = k;
+      a.seg_t0 = lo; a.seg_t1 = hi;
+      rollout(a);
+      for (int sgm = 1; sgm < nseg; ++sgm) {
+        const int nlo = hi, nhi = sgm == nseg - 1 ? T : (T * (sgm + 1)) / nseg; // rollout [nlo, nhi], costs of the knots [lo, nlo)
+        const int ncost = cgx * (nlo - lo) * ASLR_NALPHA;
+        const dim3 fgrid(grid.x + ncost);
+        if constexpr (PLANAR) {
+          if (fddp) hipLaunchKernelGGL((rollout_and_cost_kernel<NJ, DAM, true, true, false>), fgrid, block, 0, st, k, sd, lim, (int)grid.x, nlo, nhi, cgx, lo, nlo - lo);
+          else hipLaunchKernelGGL((rollout_and_cost_kernel<NJ, DAM, true, false, false>), fgrid, block, 0, st, k, sd, lim, (int)grid.x, nlo, nhi, cgx, lo, nlo - lo);
+        }
+        lo = nlo; hi = nhi;
+      }
+      a.seg_t0 = lo; a.seg_t1 = T;
+      costs(a);
+    } else {
+      rollout(k);
+      costs(k);
+    }
+  });
+  hipLaunchKernelGGL((sum_cost_kernel<S::cost_tag>), ugrid, block, 0, st, k, sd);
+  hipLaunchKernelGGL((select_kernel<S::cost_tag>), sgrid, block, 0, st, k, sd);
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
+
 } // namespace aslr
