@@ -13,7 +13,7 @@ MAX_NU = 14
 MAX_COSTS = 6
 MAX_MODELS = 4
 NALPHA = 10
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 OK, E_INVALID, E_HIP, E_NODEVICE, E_WORKSPACE = 0, -1, -2, -3, -4
 DAM_SEA, DAM_VSA = 0, 1
@@ -23,7 +23,7 @@ ST_CONVERGED, ST_REG_MAX, ST_BACKWARD_ERR, ST_FORWARD_ERR = 1, 2, 4, 8
 
 (R_XS, R_US, R_XNEXT, R_COST, R_DERIV, R_GAPS, R_KGAIN, R_KFF, R_QU, R_VX, R_VXX, R_XS_TRY,
  R_US_TRY, R_TRAJ_F, R_TRAJ_I, R_X0, R_FRAME_REF, R_VXXF, R_DESC, R_NODE_MODEL, R_COST_TRY, R_DYN, R_POOL_SAVE,
- R_COUNT) = range(24)
+ R_TRAJ_PARAMS, R_COUNT) = range(25)
 
 (TF_COST, TF_STOP, TF_XREG, TF_D1, TF_D2, TF_STEP, TF_DV, TF_DVEXP, TF_DG, TF_DQ,
  TF_COST_TRY0) = range(11)
@@ -81,6 +81,12 @@ class Pool(C.Structure):
     _fields_ = [("P", _i), ("_pad0", _i), ("x0", C.c_void_p), ("frame_ref", C.c_void_p), ("xs_out", C.c_void_p),
                 ("us_out", C.c_void_p), ("stat_f", C.c_void_p), ("stat_i", C.c_void_p), ("slot_problem", C.c_void_p),
                 ("counters", C.c_void_p), ("xs_init", C.c_void_p), ("us_init", C.c_void_p)]
+
+
+class TrajParams(C.Structure):
+    """aslr_traj_params_t: nullable HOST pointers of a per-trajectory parameter table (aslr_set_trajectory_params)."""
+    _fields_ = [("stiffness", C.POINTER(_d)), ("motor_inertia", C.POINTER(_d)), ("u_lb", C.POINTER(_d)),
+                ("u_ub", C.POINTER(_d))]
 
 
 class Region(C.Structure):
@@ -147,7 +153,7 @@ EXPORTED_SYMBOLS = [
     "aslr_calc", "aslr_calc_diff", "aslr_backward_pass", "aslr_forward_pass", "aslr_solve",
     "aslr_iterate", "aslr_iterate_timed", "aslr_finalize", "aslr_count_active", "aslr_dam_eval", "aslr_quasi_static", "aslr_last_error",
     "aslr_dam_residuals", "aslr_residual_len", "aslr_frame_placement", "aslr_set_iteration_log",
-    "aslr_iterate_n", "aslr_set_subshards", "aslr_solve_pool",
+    "aslr_iterate_n", "aslr_set_subshards", "aslr_solve_pool", "aslr_set_trajectory_params",
 ]
 
 
@@ -215,11 +221,13 @@ def load_library():
     lib.aslr_solve_pool.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Pool), i32, i32, vp, C.POINTER(i32)]
     lib.aslr_set_subshards.restype = C.c_int
     lib.aslr_set_subshards.argtypes = [vp, i32]
+    lib.aslr_set_trajectory_params.restype = C.c_int
+    lib.aslr_set_trajectory_params.argtypes = [vp, C.POINTER(TrajParams), vp]
     lib.aslr_set_iteration_log.restype = C.c_int
     lib.aslr_set_iteration_log.argtypes = [vp, vp, i32]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
-    for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool)):
+    for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams)):
         if lib.aslr_sizeof(which) != C.sizeof(st):
             raise ImportError("aslr_to_amd: struct %s size mismatch (C %d, Python %d)"
                               % (st.__name__, lib.aslr_sizeof(which), C.sizeof(st)))

@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 from . import _abi
-from .lowering import lower_problem, shard_rows
+from .lowering import lower_problem, lower_traj_params, shard_rows
 from .models import (ActivationModelQuad, ActivationModelWeightedQuad, CostModelResidual,  # noqa: F401
                      CostModelSum, Jcomponent, ResidualModelControl, ResidualModelState)
 
@@ -113,10 +113,12 @@ class ShootingProblem(object):
     Batched form: `ShootingProblem(x0s[B, nx], runningModels, terminalModel, frame_refs=...)`.
     With `rank`/`world_size` the batch is sharded in contiguous blocks, one shard per GPU
     (SURVEY.md 8(e)); every trajectory is solved independently, so results do not depend on the
-    sharding.
+    sharding.  `stiffness` / `motor_inertia` ([B, nj]) and `u_lb` / `u_ub` ([B, nu]) give every trajectory its own
+    diagonal K and B and its own control box (a design sweep in one batch); sharded like x0s and frame_refs.
     """
 
-    def __init__(self, x0, runningModels, terminalModel, frame_refs=None, rank=0, world_size=1, device=None):
+    def __init__(self, x0, runningModels, terminalModel, frame_refs=None, rank=0, world_size=1, device=None,
+                 stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
         x0 = np.atleast_2d(np.asarray(x0, dtype=np.float64))
         self._x0_all = x0
         self.batch_total = x0.shape[0]
@@ -128,11 +130,34 @@ class ShootingProblem(object):
         self.T = len(self.runningModels)
         self.nthreads = 1
         fr = None if frame_refs is None else list(frame_refs)[lo:hi]
-        self._lowered = lower_problem(x0[lo:hi], self.runningModels, terminalModel, fr)
+        tp = self._shard_params(stiffness, motor_inertia, u_lb, u_ub)
+        self._lowered = lower_problem(x0[lo:hi], self.runningModels, terminalModel, fr, **tp)
         self.batch = hi - lo
         self.nx, self.nu = self._lowered.nx, self._lowered.nu_user
         self._device = device
         self._engine = None
+
+    def _shard_params(self, stiffness, motor_inertia, u_lb, u_ub):
+        """rows of this rank out of whole-batch parameter arrays"""
+        lo, hi = self.rows
+        out = {}
+        for name, v in (("stiffness", stiffness), ("motor_inertia", motor_inertia), ("u_lb", u_lb), ("u_ub", u_ub)):
+            if v is not None:
+                v = np.array(v, dtype=np.float64, ndmin=2)
+                if v.shape[0] != self.batch_total:
+                    raise ValueError("%s needs one row per trajectory (%d), got %d" % (name, self.batch_total, v.shape[0]))
+                v = v[lo:hi]
+            out[name] = v
+        return out
+
+    def set_trajectory_params(self, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
+        """Replace the per-trajectory parameter table between solves (whole-batch arrays, as in the constructor; all
+        None: back to the models' constants)."""
+        tp = self._shard_params(stiffness, motor_inertia, u_lb, u_ub)
+        low = self._lowered
+        low.traj_params = lower_traj_params(low.desc, low.nj, low.nu, low.nu_user, low.dam, **tp)
+        if self._engine is not None:
+            self._engine.upload_traj_params(low.traj_params)
 
     @property
     def x0(self):

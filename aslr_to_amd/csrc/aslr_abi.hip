@@ -219,6 +219,7 @@ void carve(const aslr_problem_desc_t *d, int nx, int nu, aslr_region_t *r, int64
   sizes[ASLR_R_COST_TRY] = (int64_t)ASLR_NALPHA * T1 * B * D;
   sizes[ASLR_R_DYN] = T1 * B * dyn_len_c(nx / 4) * D;
   sizes[ASLR_R_POOL_SAVE] = B * (nx + 12) * D;
+  sizes[ASLR_R_TRAJ_PARAMS] = B * traj_params_rows_c(nx / 4, nu) * D;
   int64_t off = 0;
   for (int i = 0; i < ASLR_R_COUNT; ++i) {
     r[i].offset = off;
@@ -345,20 +346,26 @@ SolverDev to_dev(const aslr_solver_params_t *sp, int standalone, int store_v) {
 }
 
 // ---- the supported sizes: one row each; aslr_problem_create looks the row up and is the only place that refuses a size ----
-template <int NJ, int DAM>
+// (TP: the row a handle switches to while a per-trajectory parameter table is set; dam_eval / dam_residuals / frame
+//  placements keep the models' constants and are shared by both rows)
+template <int NJ, int DAM, bool TP = false>
 constexpr KernelSet kernel_set() {
-  return {NJ, DAM, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
-          launch_quasi_static<NJ, DAM>, launch_forward<NJ, DAM>, launch_backward<NJ, DAM>};
+  return {NJ, DAM, TP, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM, TP>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
+          launch_quasi_static<NJ, DAM, TP>, launch_forward<NJ, DAM, TP>, launch_backward<NJ, DAM, TP>};
 }
 constexpr KernelSet kKernelSets[] = {
     kernel_set<2, ASLR_DAM_SEA>(),
     kernel_set<2, ASLR_DAM_VSA>(),
     kernel_set<7, ASLR_DAM_SEA>(),
     kernel_set<7, ASLR_DAM_VSA>(),
+    kernel_set<2, ASLR_DAM_SEA, true>(),
+    kernel_set<2, ASLR_DAM_VSA, true>(),
+    kernel_set<7, ASLR_DAM_SEA, true>(),
+    kernel_set<7, ASLR_DAM_VSA, true>(),
 };
-const KernelSet *find_kernel_set(int nj, int dam) {
+const KernelSet *find_kernel_set(int nj, int dam, bool traj_params = false) {
   for (const KernelSet &ks : kKernelSets)
-    if (ks.nj == nj && ks.dam == dam) return &ks;
+    if (ks.nj == nj && ks.dam == dam && ks.traj_params == traj_params) return &ks;
   return nullptr;
 }
 
@@ -420,6 +427,7 @@ int64_t aslr_sizeof(int which) {
   case 4: return sizeof(aslr_solver_params_t);
   case 5: return sizeof(aslr_region_t);
   case 6: return sizeof(aslr_pool_t);
+  case 7: return sizeof(aslr_traj_params_t);
   default: return -1;
   }
 }
@@ -516,6 +524,7 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
       return ASLR_E_INVALID;
     }
   }
+  hd->traj_params = reinterpret_cast<const double *>(reg(ASLR_R_TRAJ_PARAMS));
   hipError_t e = hipMemcpyAsync(reg(ASLR_R_DESC), hd, sizeof(DevDesc), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(reg(ASLR_R_NODE_MODEL), desc->node_model, sizeof(int32_t) * (desc->T + 1), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(reg(ASLR_R_X0), desc->x0, sizeof(double) * desc->B * nx, hipMemcpyHostToDevice, st);
@@ -577,6 +586,72 @@ int aslr_problem_destroy(aslr_problem_t *p) {
 int aslr_problem_region(const aslr_problem_t *p, int32_t region_id, aslr_region_t *out) {
   if (!p || !out || region_id < 0 || region_id >= ASLR_R_COUNT) return ASLR_E_INVALID;
   *out = p->regions[region_id];
+  return ASLR_OK;
+}
+
+namespace {
+bool is_diagonal(int n, const double *A) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) if (i != j && A[i * n + j] != 0.0) return false;
+  return true;
+}
+} // namespace
+
+int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, void *stream) {
+  if (!p) return ASLR_E_INVALID;
+  // either way the model-only record chunks (SEA: Fu = dt B^-1 S, the motor rows of Fx) must be rewritten by the next sweep
+  const auto switch_to = [&](bool on) {
+    p->ks = find_kernel_set(p->nj, p->dam, on);
+    p->const_written = false;
+  };
+  if (!tp) { switch_to(false); return ASLR_OK; }
+  const int B = p->desc.B, nj = p->nj, nu = p->nu, nm = p->desc.nmodels;
+  const aslr_model_t *M = p->desc.models;
+  auto fail = [&](const char *msg) { snprintf(g_err, sizeof g_err, "aslr_set_trajectory_params: %s", msg); return ASLR_E_INVALID; };
+  if (tp->stiffness && p->dam == ASLR_DAM_VSA) return fail("a VSA model takes its stiffness from u: no stiffness table");
+  bool any_limits = false;
+  for (int i = 0; i < nm; ++i) {
+    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail("K and B of every model must be diagonal");
+    any_limits = any_limits || M[i].has_u_limits;
+  }
+  if ((tp->u_lb || tp->u_ub) && !any_limits) return fail("u_lb / u_ub given, but no model of the problem has control limits");
+  // a field left out keeps the models' constant: one value per column, so the models must agree on it
+  const aslr_model_t *ML = nullptr; // a model with limits (their source when a bound is left out)
+  for (int i = 0; i < nm; ++i) {
+    for (int j = 0; j < nj; ++j) {
+      if (!tp->stiffness && p->dam == ASLR_DAM_SEA && M[i].K[j * nj + j] != M[0].K[j * nj + j]) return fail("the models differ in K: give the stiffness table");
+      if (!tp->motor_inertia && M[i].B[j * nj + j] != M[0].B[j * nj + j]) return fail("the models differ in B: give the motor_inertia table");
+    }
+    if (!M[i].has_u_limits) continue;
+    if (!ML) ML = &M[i];
+    for (int c = 0; c < nu; ++c) {
+      if (!tp->u_lb && M[i].u_lb[c] != ML->u_lb[c]) return fail("the models differ in u_lb: give the u_lb table");
+      if (!tp->u_ub && M[i].u_ub[c] != ML->u_ub[c]) return fail("the models differ in u_ub: give the u_ub table");
+    }
+  }
+  const int rows = traj_params_rows_c(nj, nu);
+  std::vector<double> h((size_t)rows * B);
+  for (int b = 0; b < B; ++b) {
+    for (int j = 0; j < nj; ++j) {
+      const double k = p->dam == ASLR_DAM_VSA ? 0.0 : (tp->stiffness ? tp->stiffness[(size_t)b * nj + j] : M[0].K[j * nj + j]);
+      const double bi = tp->motor_inertia ? tp->motor_inertia[(size_t)b * nj + j] : M[0].B[j * nj + j];
+      if (!std::isfinite(k)) return fail("stiffness entries must be finite");
+      if (!(std::isfinite(bi) && bi > 0.0)) return fail("motor_inertia entries must be finite and > 0");
+      h[(size_t)j * B + b] = k;
+      h[(size_t)(nj + j) * B + b] = 1.0 / bi;
+    }
+    for (int c = 0; c < nu; ++c) {
+      const double lb = tp->u_lb ? tp->u_lb[(size_t)b * nu + c] : (ML ? ML->u_lb[c] : 0.0);
+      const double ub = tp->u_ub ? tp->u_ub[(size_t)b * nu + c] : (ML ? ML->u_ub[c] : 0.0);
+      if (!(lb <= ub)) return fail("u_lb <= u_ub must hold in every entry (no NaN)");
+      h[(size_t)(2 * nj + c) * B + b] = lb;
+      h[(size_t)(2 * nj + nu + c) * B + b] = ub;
+    }
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  HIP_TRY(hipMemcpyAsync(p->ws + p->regions[ASLR_R_TRAJ_PARAMS].offset, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st)); // (the staging buffer dies here)
+  switch_to(true);
   return ASLR_OK;
 }
 
@@ -773,6 +848,10 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
     return ASLR_E_INVALID;
   if (pool->frame_ref && !p->k.frame_ref) {
     snprintf(g_err, sizeof g_err, "aslr_solve_pool: per-problem frame references need a problem created with a frame_ref table");
+    return ASLR_E_INVALID;
+  }
+  if (p->ks->traj_params) {
+    snprintf(g_err, sizeof g_err, "aslr_solve_pool: the handle has a per-trajectory parameter table set (a pool problem would inherit its slot's parameters); clear it with aslr_set_trajectory_params(p, NULL, stream)");
     return ASLR_E_INVALID;
   }
   if (int rc = solver_unsupported(p, sp->solver)) return rc;

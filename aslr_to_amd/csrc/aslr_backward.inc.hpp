@@ -293,7 +293,10 @@ ASLR_DEV void dma_record(const char *g, unsigned recD_addr, int lt, std::integer
 #ifndef ASLR_BWD_WAVES
 #define ASLR_BWD_WAVES 2 // waves per SIMD the HS = 4 variant (two 32-lane teams per wave) must fit
 #endif
-template <int NX, int NU, int HS, int TPWA, bool BOX, bool GAPS>
+// TP: the control box is the trajectory's row of the parameter table (aslr_set_trajectory_params) instead of the models'
+// limits in `lim` (whose has[] flags still say which models are boxed): read once before the sweep, per lane -- the lanes of a
+// wave serve different trajectories, so the per-model LDS table of the DPP-row gains gives way to two registers per lane.
+template <int NX, int NU, int HS, int TPWA, bool BOX, bool GAPS, bool TP = false>
 __global__ void __launch_bounds__(64, (HS >= 4 ? ASLR_BWD_WAVES : (BwdCfg<NX, NU, HS, TPWA>::TEAMQP ? ASLR_BWD_WAVES_TEAMQP : 1))) backward_kernel(KArgs a, SolverDev sp, ModelLimits lim) {
   using C = BwdCfg<NX, NU, HS, TPWA>;
   constexpr int NXP = C::NXP, TEAM = C::TEAM, TPW = C::TPW, RPL = C::RPL, REC = C::REC;
@@ -378,8 +381,14 @@ __global__ void __launch_bounds__(64, (HS >= 4 ? ASLR_BWD_WAVES : (BwdCfg<NX, NU
   const int qr = lt & 3;
   double oh4[4];
   ASLR_UNROLL for (int c = 0; c < 4; ++c) oh4[c] = (c == qr) ? 1.0 : 0.0;
-  __shared__ double limL[C::TEAMQP && BOX ? ASLR_MAX_MODELS * 8 : 1];
-  if (C::TEAMQP && BOX) {
+  __shared__ double limL[C::TEAMQP && BOX && !TP ? ASLR_MAX_MODELS * 8 : 1];
+  double tp_lbr = 0.0, tp_ubr = 0.0, tp_lb[TP && BOX && !C::TEAMQP ? NU : 1], tp_ub[TP && BOX && !C::TEAMQP ? NU : 1];
+  if constexpr (TP && BOX) {
+    const double *tp = traj_params_at(*a.desc, b) + (size_t)(NX / 2) * B; // (rows 2 nj ..: u_lb, then u_ub)
+    if constexpr (C::TEAMQP) { tp_lbr = tp[(size_t)qr * B]; tp_ubr = tp[(size_t)(NU + qr) * B]; }
+    else { ASLR_UNROLL for (int c = 0; c < NU; ++c) { tp_lb[c] = tp[(size_t)c * B]; tp_ub[c] = tp[(size_t)(NU + c) * B]; } }
+  }
+  if (C::TEAMQP && BOX && !TP) {
     ASLR_UNROLL for (int m = 0; m < ASLR_MAX_MODELS; ++m)
       ASLR_UNROLL for (int c = 0; c < 4; ++c) {
         limL[m * 8 + c] = lim.lb[m][c]; // (every lane writes the same values)
@@ -598,8 +607,8 @@ __global__ void __launch_bounds__(64, (HS >= 4 ? ASLR_BWD_WAVES : (BwdCfg<NX, NU
         if (BOX) {
           const double utr = auxT[qr];
           k0r = auxT[NU + qr];
-          lbr = limL[mi * 8 + qr] - utr;
-          ubr = limL[mi * 8 + 4 + qr] - utr;
+          lbr = (TP ? tp_lbr : limL[mi * 8 + qr]) - utr;
+          ubr = (TP ? tp_ubr : limL[mi * 8 + 4 + qr]) - utr;
         }
         ASLR_PROF(4);
         TeamFactor<DevTeamOps> F;
@@ -640,8 +649,8 @@ __global__ void __launch_bounds__(64, (HS >= 4 ? ASLR_BWD_WAVES : (BwdCfg<NX, NU
       double gnorm0 = 0.0, g0[NU];
       if (boxed) {
         ASLR_UNROLL for (int c = 0; c < NU; ++c) {
-          lb[c] = lim.lb[mi][c] - ut[c];
-          ub[c] = lim.ub[mi][c] - ut[c];
+          lb[c] = (TP ? tp_lb[TP ? c : 0] : lim.lb[mi][c]) - ut[c];
+          ub[c] = (TP ? tp_ub[TP ? c : 0] : lim.ub[mi][c]) - ut[c];
           x0[c] = fmax(fmin(k0[c], ub[c]), lb[c]);
         }
         ASLR_UNROLL for (int c = 0; c < NU; ++c) {
@@ -848,13 +857,13 @@ __global__ void __launch_bounds__(64, (HS >= 4 ? ASLR_BWD_WAVES : (BwdCfg<NX, NU
 }
 
 // (GAPS = true always: a solve starts from an infeasible candidate unless the caller proves otherwise, and no caller does)
-template <int NX, int NU, int HS, int TPWA = 0>
+template <int NX, int NU, int HS, bool TP, int TPWA = 0>
 int launch_backward_t(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st) {
   using C = BwdCfg<NX, NU, HS, TPWA>;
   const int blocks = (k.b1 - k.b0 + C::TPW - 1) / C::TPW;
   const size_t lds = C::DMA ? 0 : (size_t)C::TPW * C::LDS_TEAM * sizeof(double); // (DMA: allocated statically)
   with_bool(sd.solver == ASLR_SOLVER_BOXDDP, [&](auto BOX) {
-    hipLaunchKernelGGL((backward_kernel<NX, NU, HS, TPWA, decltype(BOX)::value, true>), dim3(blocks), dim3(64), lds, st, k, sd, lim);
+    hipLaunchKernelGGL((backward_kernel<NX, NU, HS, TPWA, decltype(BOX)::value, true, TP>), dim3(blocks), dim3(64), lds, st, k, sd, lim);
   });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
@@ -863,10 +872,10 @@ int launch_backward_t(const KArgs &k, const SolverDev &sd, const ModelLimits &li
 // =================================================================================================
 // launcher (declared in aslr_common.hpp): the default decomposition of each size
 // =================================================================================================
-template <int NX, int NU>
+template <int NX, int NU, bool TP>
 int launch_backward_blk(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, bool mfma, hipStream_t st); // aslr_backward_blk.inc.hpp (nx = 28)
 
-template <int NJ, int DAM>
+template <int NJ, int DAM, bool TP>
 int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, const ModelLimits &lim, hipStream_t st) {
   constexpr int NX = 4 * NJ, NU = ModelDims<NJ, DAM>::nu;
   if constexpr (NX == 8) {
@@ -875,14 +884,14 @@ int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, cons
     // together stay at one wave per SIMD (whole shard <= 2048 trajectories: 345 -> 334 us BoxDDP, 184 -> 161 us DDP at 1024) and
     // lose beyond (two waves per SIMD: the gains phase is per-wave work)
     if (hs == 0) hs = ((NU == 2 && k.b1 - k.b0 <= 2048) || k.B <= 2048) ? 4 : (k.B <= 8192 ? 2 : 1);
-    if (hs == 4) return launch_backward_t<NX, NU, 4>(k, sd, lim, st);
-    return hs == 2 ? launch_backward_t<NX, NU, 2>(k, sd, lim, st) : launch_backward_t<NX, NU, 1>(k, sd, lim, st);
+    if (hs == 4) return launch_backward_t<NX, NU, 4, TP>(k, sd, lim, st);
+    return hs == 2 ? launch_backward_t<NX, NU, 2, TP>(k, sd, lim, st) : launch_backward_t<NX, NU, 1, TP>(k, sd, lim, st);
   } else {
     // hs: 0 = default (block-per-trajectory LDS kernel, all three solvers; vector-FMA products without mfma, as for hs < 0),
     //     1 / 2 = force the register-column kernel with that many lanes per column (tests, comparisons)
-    if (hs <= 0) return launch_backward_blk<NX, NU>(k, sd, lim, mfma && hs == 0, st);
+    if (hs <= 0) return launch_backward_blk<NX, NU, TP>(k, sd, lim, mfma && hs == 0, st);
     if constexpr (SizeTraits<NJ, DAM>::reg_column) {
-      return hs == 2 ? launch_backward_t<NX, NU, 2>(k, sd, lim, st) : launch_backward_t<NX, NU, 1>(k, sd, lim, st);
+      return hs == 2 ? launch_backward_t<NX, NU, 2, TP>(k, sd, lim, st) : launch_backward_t<NX, NU, 1, TP>(k, sd, lim, st);
     } else { // VSA: the block kernel only (wave-cooperative gains / box QP, aslr_wave_gains.hpp)
       snprintf(err_buf(), kErrLen, "backward: the register-column kernel (ASLR_BWD_HS=%d) is not built for (nx=%d, nu=%d)", hs, NX, NU);
       return ASLR_E_INVALID;

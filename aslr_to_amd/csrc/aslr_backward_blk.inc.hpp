@@ -63,7 +63,9 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 // column l & 15).  The instruction accumulates exactly like the k-ordered fma chain of the vector path
 // (tools/ubench/mfma_f64_layout.hip: 256 / 256 entries bit-equal), so both paths give the same bits.  It has the
 // vector unit's FP64 rate; what it saves is issue slots: 35 MFMAs per wave and knot replace 504 FMAs + 196 LDS reads.
-template <int NX, int NU, bool GAPS, bool MFMA, bool BOX = false>
+// TP: the control box of a boxed node is the trajectory's row of the parameter table (aslr_set_trajectory_params), not the
+// models' limits: its 2 nu words are staged in LDS once, before the sweep (one block = one trajectory).
+template <int NX, int NU, bool GAPS, bool MFMA, bool BOX = false, bool TP = false>
 __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp, ModelLimits lim) {
   using C = BwdBlk<NX, NU>;
   constexpr int REC = C::REC, NG = C::NG, NT = C::NT;
@@ -87,6 +89,14 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
   const int B = a.B, T = a.T, b = a.b0 + blockIdx.x;
   int32_t *TI = a.traj_i;
   double *TF = a.traj_f;
+  // u_lb / u_ub entry c of this trajectory (TP: [lb | ub] in LDS, ordered with the sweep by the barriers of the prologue
+  // below and of the first knot) or of model mi
+  __shared__ double tpLimL[TP && BOX ? 2 * NU : 1];
+  if constexpr (TP && BOX) {
+    if (tid < 2 * NU) tpLimL[tid] = (traj_params_at(*a.desc, b) + (size_t)(NX / 2) * B)[(size_t)tid * B];
+  }
+  auto lb_of = [&](int mi, int c) -> double { if constexpr (TP && BOX) return tpLimL[c]; else return lim.lb[mi][c]; };
+  auto ub_of = [&](int mi, int c) -> double { if constexpr (TP && BOX) return tpLimL[NU + c]; else return lim.ub[mi][c]; };
 
   // ---- prologue: solver-state bookkeeping that Crocoddyl does inside calcDiff ----
   int done = 0, feasible = TI[ASLR_TI_FEASIBLE * B + b], status = TI[ASLR_TI_STATUS * B + b];
@@ -380,8 +390,8 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
           const double *kvL = WL + WG::oKv;
           const bool boxed = BOX && box && lim.has[mi]; // block-uniform
           if (BOX && boxed && tid < NU) { // bounds of the step: the model's limits minus the node's u
-            WL[WG::oLb + tid] = lim.lb[mi][tid] - UKL[tid];
-            WL[WG::oUb + tid] = lim.ub[mi][tid] - UKL[tid];
+            WL[WG::oLb + tid] = lb_of(mi, tid) - UKL[tid];
+            WL[WG::oUb + tid] = ub_of(mi, tid) - UKL[tid];
           }
           wave_sync();
           const WaveQPParams qp{sp.boxqp_maxiter, sp.boxqp_th_acceptstep, sp.boxqp_th_grad, sp.boxqp_reg, ASLR_NALPHA};
@@ -415,8 +425,8 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
             qu[c] = QuL[c]; Kc[c] = QuxL[c * NX + col];
             const double ut = UKL[c];
             k0[c] = UKL[NUP + c];
-            lb[c] = lim.lb[mi][c] - ut;
-            ub[c] = lim.ub[mi][c] - ut;
+            lb[c] = lb_of(mi, c) - ut;
+            ub[c] = ub_of(mi, c) - ut;
           }
 #ifdef ASLR_BWD_PROFILE
           bad = lane_gains<NU>(Quu, qu, Kc, kv, true, lb, ub, k0, sp, prof_acc, prof_last);
@@ -596,14 +606,14 @@ __global__ void __launch_bounds__(128) backward_blk_kernel(KArgs a, SolverDev sp
   }
 }
 
-template <int NX, int NU>
+template <int NX, int NU, bool TP>
 int launch_backward_blk(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, bool mfma, hipStream_t st) {
   // mfma = false (ASLR_BLK_MFMA=0 when the handle was created) selects the vector-FMA products (comparison runs; both
   // paths give the same bits).  Gap terms are compiled in for every solver: a cold-started solve is infeasible at first.
   const dim3 grid(k.b1 - k.b0), block(BwdBlk<NX, NU>::NT);
   with_bool(mfma, [&](auto MFMA) {
     with_bool(sd.solver == ASLR_SOLVER_BOXDDP, [&](auto BOX) {
-      hipLaunchKernelGGL((backward_blk_kernel<NX, NU, true, decltype(MFMA)::value, decltype(BOX)::value>), grid, block, 0, st, k, sd, lim);
+      hipLaunchKernelGGL((backward_blk_kernel<NX, NU, true, decltype(MFMA)::value, decltype(BOX)::value, TP>), grid, block, 0, st, k, sd, lim);
     });
   });
   HIP_TRY(hipGetLastError());

@@ -18,7 +18,10 @@ constexpr int kLdsStride = kChunk + 1; // odd stride: conflict-free ds_write_b64
 // PRE: the rigid-body part of the knot was computed by dyn_team_kernel (aslr_calc_team.inc.hpp) into DYN
 // SKIPC: the model-only record chunks are in place (kModeSkipConst, known at launch): compiled out, and with them the
 // parts of the compact derivative set only they read (the steady-state sweeps of a solve run this variant)
-template <int NJ, int DAM, bool DIFF, bool PLANAR, bool PRE = false, bool SKIPC = false>
+// TP: K and B^-1 are the diagonals of the trajectory's row of the parameter table (aslr_set_trajectory_params).  With PRE they
+// only reach the record through Bk / Fum, which the first group of chunks flushes before the cost stack starts: nothing of
+// them is live across it (and nothing at all with SKIPC)
+template <int NJ, int DAM, bool DIFF, bool PLANAR, bool PRE = false, bool SKIPC = false, bool TP = false>
 __global__ void __launch_bounds__(64, ASLR_CALC_WAVES) calc_kernel(KArgs a, int mode, double th_gaptol) {
   constexpr int NX = 4 * NJ, NU = ModelDims<NJ, DAM>::nu;
   using RL = RecLayout<NJ, NU>;
@@ -102,7 +105,7 @@ __global__ void __launch_bounds__(64, ASLR_CALC_WAVES) calc_kernel(KArgs a, int 
     using CH = std::conditional_t<PLANAR, ChainPlanar<NJ>, Chain3D<NJ>>;
     const typename CH::Consts cc(D);
     ModelRegs<NJ, NU> mr;
-    mr.load(dm);
+    mr.template load_for<TP>(dm, D, b, B);
     // PRE (large chain): the evaluation is split -- dynamics derivatives first, their part of the record streamed
     // out, then the cost stack -- so that the ~400 doubles of the compact derivative set are never all live
     constexpr int what = (DIFF ? kEvalDiff : (kEvalDyn | kEvalCost)) | (PRE ? (kEvalPre | kEvalSkipCost) : 0);
@@ -216,7 +219,7 @@ __global__ void __launch_bounds__(64, ASLR_CALC_WAVES) calc_kernel(KArgs a, int 
 // until |du| <= tol or maxiter.  One lane per (trajectory, node).  pinv(Fu) acts through the normal equations
 // and a thresholded eigen-decomposition (pinv_normal_solve), so a rank-deficient Fu -- VSA at q_l = q_m, where
 // the stiffness columns vanish -- gets the minimum-norm update Crocoddyl's SVD pseudo-inverse gives.
-template <int NJ, int DAM, bool PLANAR>
+template <int NJ, int DAM, bool PLANAR, bool TP = false>
 __global__ void __launch_bounds__(64) quasi_static_kernel(KArgs a, int maxiter, double tol, int32_t *iters_out) {
   constexpr int NX = 4 * NJ, NU = ModelDims<NJ, DAM>::nu, NV = 2 * NJ;
   using CH = std::conditional_t<PLANAR, ChainPlanar<NJ>, Chain3D<NJ>>;
@@ -229,7 +232,7 @@ __global__ void __launch_bounds__(64) quasi_static_kernel(KArgs a, int maxiter, 
   const double *fref = a.frame_ref ? a.frame_ref + 12 * (size_t)b : nullptr;
   const typename CH::Consts cc(D);
   ModelRegs<NJ, NU> mr;
-  mr.load(dm);
+  mr.template load_for<TP>(dm, D, b, B);
   double x[NX], u[NU];
   ASLR_UNROLL for (int i = 0; i < NX; ++i) x[i] = a.xs[tb * NX + i];
   ASLR_UNROLL for (int i = 0; i < NU; ++i) u[i] = 0.0;
@@ -375,30 +378,30 @@ __global__ void __launch_bounds__(64) frame_placement_kernel(const DevDesc *desc
 // =================================================================================================
 // launchers (declared in aslr_common.hpp; SizeTraits there says what differs between the sizes)
 // =================================================================================================
-template <int NJ, int PHASE> __global__ void dyn_team_kernel(KArgs a, int mode); // aslr_calc_team.inc.hpp (SizeTraits::team_dyn)
+template <int NJ, int PHASE, bool TP> __global__ void dyn_team_kernel(KArgs a, int mode); // aslr_calc_team.inc.hpp (SizeTraits::team_dyn)
 
-template <int NJ, int DAM>
+template <int NJ, int DAM, bool TP>
 int launch_calc(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st) {
   using S = SizeTraits<NJ, DAM>;
   const dim3 grid((k.b1 - k.b0 + 63) / 64, k.T + 1), block(64);
   with_planar<NJ>(k, [&](auto P) {
     constexpr bool PLANAR = decltype(P)::value, PRE = S::team_dyn;
     if (!diff) {
-      hipLaunchKernelGGL((calc_kernel<NJ, DAM, false, PLANAR>), grid, block, 0, st, k, mode, th_gaptol);
+      hipLaunchKernelGGL((calc_kernel<NJ, DAM, false, PLANAR, false, false, TP>), grid, block, 0, st, k, mode, th_gaptol);
       return;
     }
     if constexpr (PRE) { // rigid-body part by 8-lane teams (aslr_calc_team.inc.hpp), then products + costs + record per lane
       const dim3 tgrid((k.b1 - k.b0 + 7) / 8, k.T + 1);
-      hipLaunchKernelGGL((dyn_team_kernel<NJ, 0>), tgrid, block, 0, st, k, mode);
-      hipLaunchKernelGGL((dyn_team_kernel<NJ, 1>), tgrid, block, 0, st, k, mode);
+      hipLaunchKernelGGL((dyn_team_kernel<NJ, 0, TP>), tgrid, block, 0, st, k, mode);
+      hipLaunchKernelGGL((dyn_team_kernel<NJ, 1, TP>), tgrid, block, 0, st, k, mode);
     }
     if constexpr (S::skip_const) {
       if (mode & kModeSkipConst) {
-        hipLaunchKernelGGL((calc_kernel<NJ, DAM, true, PLANAR, PRE, true>), grid, block, 0, st, k, mode, th_gaptol);
+        hipLaunchKernelGGL((calc_kernel<NJ, DAM, true, PLANAR, PRE, true, TP>), grid, block, 0, st, k, mode, th_gaptol);
         return;
       }
     }
-    hipLaunchKernelGGL((calc_kernel<NJ, DAM, true, PLANAR, PRE>), grid, block, 0, st, k, mode, th_gaptol);
+    hipLaunchKernelGGL((calc_kernel<NJ, DAM, true, PLANAR, PRE, false, TP>), grid, block, 0, st, k, mode, th_gaptol);
   });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
@@ -435,11 +438,11 @@ int launch_frame_placement(const KArgs &k, int fj, const FrameArg &F, int n, con
   return ASLR_OK;
 }
 
-template <int NJ, int DAM>
+template <int NJ, int DAM, bool TP>
 int launch_quasi_static(const KArgs &k, int maxiter, double tol, int32_t *iters, hipStream_t st) {
   const dim3 grid((k.B + 63) / 64, k.T), block(64);
   with_planar<NJ>(k, [&](auto P) {
-    hipLaunchKernelGGL((quasi_static_kernel<NJ, DAM, decltype(P)::value>), grid, block, 0, st, k, maxiter, tol, iters);
+    hipLaunchKernelGGL((quasi_static_kernel<NJ, DAM, decltype(P)::value, TP>), grid, block, 0, st, k, maxiter, tol, iters);
   });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;

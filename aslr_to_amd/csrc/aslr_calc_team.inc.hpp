@@ -129,7 +129,9 @@ struct CalcTeam {
 // PHASE 0: M, nonlinear effects, M^-1, accelerations; PHASE 1: the kept sweep, dtau/dq and dtau/dv.  Two launches of
 // the same body: each phase gets its own register allocation (262 and 436 VGPRs, no scratch; in one kernel the first
 // part would run at the occupancy of the second: measured 706 vs 684 us for the whole calcDiff).
-template <int NJ, int PHASE>
+// TP: row cj of K and of B^-1 (and column cj of K) come from the trajectory's row of the parameter table: one entry on the
+// diagonal, literal zeros elsewhere.
+template <int NJ, int PHASE, bool TP = false>
 __global__ void __launch_bounds__(64) dyn_team_kernel(KArgs a, int mode) {
   using C = CalcTeam<NJ>;
   constexpr int NX = C::NX, NU = C::NU, DL = dyn_len_c(NJ);
@@ -171,8 +173,16 @@ __global__ void __launch_bounds__(64) dyn_team_kernel(KArgs a, int mode) {
   }
   wave_sync();
   double Krow[NJ], Srow[NJ], Brow[NJ];
-  ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
-    Krow[j] = dm.m.K[cj * NJ + j]; Srow[j] = dm.m.S[cj * NU + j]; Brow[j] = dm.Binv[cj * NJ + j];
+  double k_cj = 0.0; // TP: K[cj][cj] of this trajectory
+  if constexpr (TP) {
+    const double *tp = traj_params_at(D, b);
+    k_cj = tp[(size_t)cj * B];
+    const double b_cj = tp[(size_t)(NJ + cj) * B];
+    ASLR_UNROLL for (int j = 0; j < NJ; ++j) { Krow[j] = (j == cj) ? k_cj : 0.0; Srow[j] = dm.m.S[cj * NU + j]; Brow[j] = (j == cj) ? b_cj : 0.0; }
+  } else {
+    ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
+      Krow[j] = dm.m.K[cj * NJ + j]; Srow[j] = dm.m.S[cj * NU + j]; Brow[j] = dm.Binv[cj * NJ + j];
+    }
   }
   if (jl) {
     const M3 R = mul(m3(ch.joint_R[cj]), axis_angle(v3(ch.axis[cj]), xT[cj]));
@@ -236,7 +246,7 @@ __global__ void __launch_bounds__(64) dyn_team_kernel(KArgs a, int mode) {
     rnea_tangent_lds<NJ, 0>(chc, RL, WS, xT + 2 * NJ, cj, colL);
     {
       double Kcol[NJ];
-      ASLR_UNROLL for (int l = 0; l < NJ; ++l) Kcol[l] = dm.m.K[l * NJ + cj];
+      ASLR_UNROLL for (int l = 0; l < NJ; ++l) Kcol[l] = TP ? ((l == cj) ? k_cj : 0.0) : dm.m.K[l * NJ + cj];
       ASLR_UNROLL for (int i = 0; i < NJ; ++i) {
         double sq = 0.0, sk = 0.0;
         ASLR_UNROLL for (int l = 0; l < NJ; ++l) {

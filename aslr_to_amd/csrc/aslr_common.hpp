@@ -161,19 +161,23 @@ void with_planar(const KArgs &k, F &&f) {
 
 // One launcher per kernel family, defined in the family's .inc.hpp and explicitly instantiated in the translation unit
 // of the size.  frame_placement does not depend on the actuation: one instantiation per nj.
-template <int NJ, int DAM> int launch_calc(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st);
+// TP: the per-trajectory parameter table (aslr_set_trajectory_params) replaces K, B^-1 and the control box in the kernel
+// families that read them -- calc / calcDiff, quasi-static, rollout, backward; the TP = true launchers live in
+// translation units of their own (aslr_*_tp.hip), so the default path's code objects are what they were.
+template <int NJ, int DAM, bool TP = false> int launch_calc(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st);
 template <int NJ, int DAM> int launch_dam_eval(const KArgs &k, int mi, int n, const double *x, const double *u, double *xout, double *cost,
                                                double *Fx, double *Fu, double *Lx, double *Lu, double *Lxx, double *Lxu, double *Luu, hipStream_t st);
 template <int NJ, int DAM> int launch_dam_residuals(const KArgs &k, int mi, int n, const double *x, const double *u, double *r, int nr, hipStream_t st);
 template <int NJ> int launch_frame_placement(const KArgs &k, int fj, const FrameArg &F, int n, const double *x, int64_t stride, double *out, hipStream_t st);
-template <int NJ, int DAM> int launch_quasi_static(const KArgs &k, int maxiter, double tol, int32_t *iters, hipStream_t st);
-template <int NJ, int DAM> int launch_forward(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
+template <int NJ, int DAM, bool TP = false> int launch_quasi_static(const KArgs &k, int maxiter, double tol, int32_t *iters, hipStream_t st);
+template <int NJ, int DAM, bool TP = false> int launch_forward(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
 // hs: ASLR_BWD_HS (0: the size's default decomposition); mfma: ASLR_BLK_MFMA (block kernel of nx = 28 only)
-template <int NJ, int DAM> int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
+template <int NJ, int DAM, bool TP = false> int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
 
 // the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
 struct KernelSet {
   int nj, dam;
+  bool traj_params; // the row of the handles that have a per-trajectory parameter table set
   bool boxddp_only;
   decltype(&launch_calc<2, 0>) calc;
   decltype(&launch_dam_eval<2, 0>) dam_eval;

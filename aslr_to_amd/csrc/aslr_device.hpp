@@ -161,6 +161,27 @@ struct DevDesc {
   aslr_chain_t chain;
   DevModel models[ASLR_MAX_MODELS];
   PlanarChain planar;
+  const double *traj_params; // region TRAJ_PARAMS (fixed for the life of the handle); read by the TP kernel variants only
+};
+
+// Per-trajectory parameter table (region TRAJ_PARAMS, aslr_set_trajectory_params), row-major [rows][B] doubles so that
+// lanes on consecutive trajectories read consecutive words:
+//   rows [0, nj) diagonal of the spring stiffness K (SEA; zeros for VSA, which takes its stiffness from u),
+//        [nj, 2 nj) RECIPROCALS of the diagonal of the motor inertia B, [2 nj, 2 nj + nu) u_lb, [2 nj + nu, 2 nj + 2 nu) u_ub.
+// The TP = true instantiations of the kernels read it in place of DevModel::K / Binv and ModelLimits::lb / ub; the host
+// fills every row (a field the caller left out gets the models' constant), so there is no per-field test on the device.
+constexpr int traj_params_rows_c(int nj, int nu) { return 2 * nj + 2 * nu; }
+// the table as seen by trajectory b: row r at [r * B] (scalar load of the base: DevDesc is never written by a kernel)
+ASLR_DEV const double *traj_params_at(const DevDesc &D, int b) {
+  return ((const DevDesc __attribute__((address_space(4))) *)(&D))->traj_params + b;
+}
+// the two diagonals of one trajectory in registers (vector loads, issued once per kernel, outside any knot loop)
+template <int NJ>
+struct TrajDiag {
+  double k[NJ], binv[NJ];
+  ASLR_DEV void load(const double *tp, int B) {
+    ASLR_UNROLL for (int i = 0; i < NJ; ++i) { k[i] = tp[(size_t)i * B]; binv[i] = tp[(size_t)(NJ + i) * B]; }
+  }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -1083,6 +1104,22 @@ struct ModelRegs {
     ASLR_UNROLL for (int i = 0; i < NJ; ++i) {
       ASLR_UNROLL for (int j = 0; j < NJ; ++j) { K[i][j] = dm.m.K[i * NJ + j]; Binv[i][j] = dm.Binv[i * NJ + j]; }
       ASLR_UNROLL for (int j = 0; j < NU; ++j) S[i][j] = dm.m.S[i * NU + j];
+    }
+  }
+  // per-trajectory K and B^-1 (diagonal) over the model's: the off-diagonals are literal zeros under the unrolled loops,
+  // so the compiler folds their terms away and every sum keeps the order of its remaining entries
+  ASLR_DEV void set_traj(const TrajDiag<NJ> &d) {
+    ASLR_UNROLL for (int i = 0; i < NJ; ++i)
+      ASLR_UNROLL for (int j = 0; j < NJ; ++j) { K[i][j] = (i == j) ? d.k[i] : 0.0; Binv[i][j] = (i == j) ? d.binv[i] : 0.0; }
+  }
+  // model constants with the table's diagonals of the trajectory tp points at (TP kernels; load() otherwise)
+  template <bool TP>
+  ASLR_DEV void load_for(const DevModel &dm, const DevDesc &D, int b, int B) {
+    load(dm);
+    if constexpr (TP) {
+      TrajDiag<NJ> d;
+      d.load(traj_params_at(D, b), B);
+      set_traj(d);
     }
   }
 };

@@ -29,7 +29,9 @@ namespace aslr {
 // Knots [s0, s1] of the horizon (the whole of it: [0, T]): a launch that starts at s0 > 0 continues the rollout a previous
 // launch stopped at s0 -- state from the candidate stored there, dv / failure flag from the per-trajectory slots -- and
 // repeats nothing that launch has already accounted for at knot s0 (gap contraction, the dv term).
-template <int NJ, int DAM, bool PLANAR, bool FDDP>
+// TP: the diagonals of K / B^-1 and the control box are the trajectory's row of the parameter table, read once before the
+// knot loop (vector loads; every lane of a team reads the same words); a model change re-reads dt / S only.
+template <int NJ, int DAM, bool PLANAR, bool FDDP, bool TP = false>
 ASLR_DEV void rollout_body(const KArgs &a, const SolverDev &sp, const ModelLimits &lim, int vblock, int s0, int s1) {
   constexpr int NX = 4 * NJ, NU = ModelDims<NJ, DAM>::nu;
   constexpr int TEAM = 16, TPW = ASLR_ROLLOUT_TPW;
@@ -72,6 +74,12 @@ ASLR_DEV void rollout_body(const KArgs &a, const SolverDev &sp, const ModelLimit
   int m_loaded = -1, lim_has = 0;
   double lim_lb[NU], lim_ub[NU]; // control limits of the loaded model (kernel arguments behind a runtime index: scalar loads)
   ASLR_UNROLL for (int i = 0; i < NU; ++i) { lim_lb[i] = 0.0; lim_ub[i] = 0.0; }
+  TrajDiag<NJ> tdiag;
+  if constexpr (TP) {
+    const double *tp = traj_params_at(D, b);
+    tdiag.load(tp, B);
+    ASLR_UNROLL for (int i = 0; i < NU; ++i) { lim_lb[i] = tp[(size_t)(2 * NJ + i) * B]; lim_ub[i] = tp[(size_t)(2 * NJ + NU + i) * B]; }
+  }
   // Per-knot inputs shared by the step lengths of a trajectory -- [K | xs | us | k | gaps | Vxx f] -- are fetched ONCE
   // per team, one knot ahead, straight into LDS (global_load_lds_dwordx4: lane lt fetches the 16-byte pieces lt and
   // lt + 16 of the list; element e of team tm lands at (e / 32) * 128 + 32 tm + e % 32 of the parity buffer).
@@ -140,7 +148,8 @@ ASLR_DEV void rollout_body(const KArgs &a, const SolverDev &sp, const ModelLimit
       mr.load(dm);
       m_loaded = m_now;
       lim_has = lim.has[m_now];
-      ASLR_UNROLL for (int i = 0; i < NU; ++i) { lim_lb[i] = lim.lb[m_now][i]; lim_ub[i] = lim.ub[m_now][i]; }
+      if constexpr (TP) mr.set_traj(tdiag);
+      else { ASLR_UNROLL for (int i = 0; i < NU; ++i) { lim_lb[i] = lim.lb[m_now][i]; lim_ub[i] = lim.ub[m_now][i]; } }
     }
     if (box && lim_has) {
       ASLR_UNROLL for (int i = 0; i < NU; ++i) u[i] = fmin(fmax(u[i], lim_lb[i]), lim_ub[i]);
@@ -160,10 +169,10 @@ ASLR_DEV void rollout_body(const KArgs &a, const SolverDev &sp, const ModelLimit
     TF[(ASLR_TF_DVTRY0 + ai) * B + b] = dv;
   }
 }
-template <int NJ, int DAM, bool PLANAR, bool FDDP>
+template <int NJ, int DAM, bool PLANAR, bool FDDP, bool TP = false>
 __global__ void __launch_bounds__(64) rollout_kernel(KArgs a, SolverDev sp, ModelLimits lim) {
   ASLR_STAMP_BEGIN(a, 2);
-  rollout_body<NJ, DAM, PLANAR, FDDP>(a, sp, lim, blockIdx.x, a.seg_t0, a.seg_t1);
+  rollout_body<NJ, DAM, PLANAR, FDDP, TP>(a, sp, lim, blockIdx.x, a.seg_t0, a.seg_t1);
   ASLR_STAMP_END(2, true);
 }
 
@@ -219,12 +228,12 @@ __global__ void __launch_bounds__(64) trial_cost_kernel(KArgs a, SolverDev sp) {
 // One launch, two roles: blocks [0, nroll) continue the rollout over the knots [r0, r1] while the others evaluate the trial
 // costs of the knots [c0, c0 + cknots) the previous rollout launch has stored (block order = dispatch order: the sweep waves
 // take their SIMDs first, the cost waves fill in next to them).  Cost block v - nroll = (x, knot, step length), x fastest.
-template <int NJ, int DAM, bool PLANAR, bool FDDP, bool FAST>
+template <int NJ, int DAM, bool PLANAR, bool FDDP, bool FAST, bool TP = false>
 __global__ void __launch_bounds__(64) rollout_and_cost_kernel(KArgs a, SolverDev sp, ModelLimits lim, int nroll, int r0, int r1,
                                                               int cgx, int c0, int cknots) {
   ASLR_STAMP_BEGIN(a, 3);
   if ((int)blockIdx.x < nroll) {
-    rollout_body<NJ, DAM, PLANAR, FDDP>(a, sp, lim, blockIdx.x, r0, r1);
+    rollout_body<NJ, DAM, PLANAR, FDDP, TP>(a, sp, lim, blockIdx.x, r0, r1);
     ASLR_STAMP_END(3, true);
   } else {
     const int v = blockIdx.x - nroll, vx = v % cgx, rest = v / cgx;
@@ -361,9 +370,10 @@ __global__ void __launch_bounds__(64) select_kernel(KArgs a, SolverDev sp) {
 // =================================================================================================
 // launcher (declared in aslr_common.hpp; SizeTraits there says what differs between the sizes)
 // =================================================================================================
-template <int NJ, bool FDDP, int DAM> __global__ void rollout_team_kernel(KArgs a, SolverDev sp, ModelLimits lim); // aslr_forward_team.inc.hpp (SizeTraits::team_rollout)
+template <int NJ, bool FDDP, int DAM, bool TP> __global__ void rollout_team_kernel(KArgs a, SolverDev sp, ModelLimits lim); // aslr_forward_team.inc.hpp (SizeTraits::team_rollout)
 
-template <int NJ, int DAM>
+// (the trial costs, their sums and the line search read neither K, B nor the limits: one instantiation serves both)
+template <int NJ, int DAM, bool TP>
 int launch_forward(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, hipStream_t st) {
   using S = SizeTraits<NJ, DAM>;
   const int nb = k.b1 - k.b0; // trajectories of this launch
@@ -372,17 +382,17 @@ int launch_forward(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, 
   const bool fddp = sd.solver == ASLR_SOLVER_FDDP;
   if constexpr (S::team_rollout) {
     // one block of 16 eight-lane teams per trajectory (aslr_forward_team.inc.hpp)
-    if constexpr (S::boxddp_only) hipLaunchKernelGGL((rollout_team_kernel<NJ, false, DAM>), dim3(nb), dim3(128), 0, st, k, sd, lim);
-    else if (fddp) hipLaunchKernelGGL((rollout_team_kernel<NJ, true, DAM>), dim3(nb), dim3(128), 0, st, k, sd, lim);
-    else hipLaunchKernelGGL((rollout_team_kernel<NJ, false, DAM>), dim3(nb), dim3(128), 0, st, k, sd, lim);
+    if constexpr (S::boxddp_only) hipLaunchKernelGGL((rollout_team_kernel<NJ, false, DAM, TP>), dim3(nb), dim3(128), 0, st, k, sd, lim);
+    else if (fddp) hipLaunchKernelGGL((rollout_team_kernel<NJ, true, DAM, TP>), dim3(nb), dim3(128), 0, st, k, sd, lim);
+    else hipLaunchKernelGGL((rollout_team_kernel<NJ, false, DAM, TP>), dim3(nb), dim3(128), 0, st, k, sd, lim);
     hipLaunchKernelGGL((trial_cost_kernel<NJ, DAM, false>), dim3(cgx, T + 1, ASLR_NALPHA), block, 0, st, k, sd);
   } else with_planar<NJ>(k, [&](auto P) {
     constexpr bool PLANAR = decltype(P)::value, CANFAST = PLANAR;
     const dim3 grid((nb + ASLR_ROLLOUT_TPW - 1) / ASLR_ROLLOUT_TPW);
     const bool fast = CANFAST && k.planar_reach;
     auto rollout = [&](const KArgs &a) {
-      if (fddp) hipLaunchKernelGGL((rollout_kernel<NJ, DAM, PLANAR, true>), grid, block, 0, st, a, sd, lim);
-      else hipLaunchKernelGGL((rollout_kernel<NJ, DAM, PLANAR, false>), grid, block, 0, st, a, sd, lim);
+      if (fddp) hipLaunchKernelGGL((rollout_kernel<NJ, DAM, PLANAR, true, TP>), grid, block, 0, st, a, sd, lim);
+      else hipLaunchKernelGGL((rollout_kernel<NJ, DAM, PLANAR, false, TP>), grid, block, 0, st, a, sd, lim);
     };
     auto costs = [&](const KArgs &a) { // knots [a.seg_t0, a.seg_t1]
       const dim3 cgrid(cgx, a.seg_t1 - a.seg_t0 + 1, ASLR_NALPHA);
@@ -404,8 +414,8 @@ int launch_forward(const KArgs &k, const SolverDev &sd, const ModelLimits &lim, 
         const int ncost = cgx * (nlo - lo) * ASLR_NALPHA;
         const dim3 fgrid(grid.x + ncost);
         if constexpr (PLANAR) {
-          if (fddp) hipLaunchKernelGGL((rollout_and_cost_kernel<NJ, DAM, true, true, false>), fgrid, block, 0, st, k, sd, lim, (int)grid.x, nlo, nhi, cgx, lo, nlo - lo);
-          else hipLaunchKernelGGL((rollout_and_cost_kernel<NJ, DAM, true, false, false>), fgrid, block, 0, st, k, sd, lim, (int)grid.x, nlo, nhi, cgx, lo, nlo - lo);
+          if (fddp) hipLaunchKernelGGL((rollout_and_cost_kernel<NJ, DAM, true, true, false, TP>), fgrid, block, 0, st, k, sd, lim, (int)grid.x, nlo, nhi, cgx, lo, nlo - lo);
+          else hipLaunchKernelGGL((rollout_and_cost_kernel<NJ, DAM, true, false, false, TP>), fgrid, block, 0, st, k, sd, lim, (int)grid.x, nlo, nhi, cgx, lo, nlo - lo);
         }
         lo = nlo; hi = nhi;
       }

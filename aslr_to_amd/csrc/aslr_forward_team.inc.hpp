@@ -102,7 +102,9 @@ struct FwdTeam {
                        tMi = tM + 8 * 8, TEAM_LDS = tMi + 8 * 8;
 };
 
-template <int NJ, bool FDDP, int DAM = ASLR_DAM_SEA>
+// TP: this lane's diagonal entries of K / B^-1 and its bounds come from the trajectory's row of the parameter table, read
+// once before the knot loop; a model change re-reads dt / S / has_u_limits only.
+template <int NJ, bool FDDP, int DAM = ASLR_DAM_SEA, bool TP = false>
 __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp, ModelLimits lim) {
   using C = FwdTeam<NJ, DAM>;
   constexpr int NX = C::NX, NU = C::NU, NSLOT = C::NSLOT;
@@ -157,6 +159,15 @@ __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp
   double Krow[NJ], Srow[NJ], Brow[NJ], dt = 0.0, lb_c = 0.0, ub_c = 0.0, lb_s = 0.0, ub_s = 0.0; // (lb_s / ub_s: the stiffness row, VSA)
   bool has_lim = false;
   int m_loaded = -1;
+  double k_cj = 0.0, b_cj = 0.0; // TP: K[cj][cj], 1 / B[cj][cj] of this trajectory
+  if constexpr (TP) {
+    const double *tp = traj_params_at(D, b);
+    k_cj = tp[(size_t)cj * B];
+    b_cj = tp[(size_t)(NJ + cj) * B];
+    lb_c = tp[(size_t)(2 * NJ + cj) * B];
+    ub_c = tp[(size_t)(2 * NJ + NU + cj) * B];
+    if (VSA) { lb_s = tp[(size_t)(3 * NJ + cj) * B]; ub_s = tp[(size_t)(3 * NJ + NU + cj) * B]; }
+  }
   // joint placements and axes: constants of the chain, staged once in LDS (as global loads inside the knot loop they
   // cost a vmcnt(0) per knot, which also waits for the prefetch issued just before; in registers they spill)
   __shared__ double jtab[8][12];
@@ -205,13 +216,15 @@ __global__ void __launch_bounds__(128) rollout_team_kernel(KArgs a, SolverDev sp
     if (mi != m_loaded) {
       dt = dm.m.dt;
       ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
-        if (!VSA) { Krow[j] = dm.m.K[cj * NJ + j]; Srow[j] = dm.m.S[cj * NU + j]; }
-        Brow[j] = dm.Binv[cj * NJ + j];
+        if (!VSA) { Krow[j] = TP ? ((j == cj) ? k_cj : 0.0) : dm.m.K[cj * NJ + j]; Srow[j] = dm.m.S[cj * NU + j]; }
+        Brow[j] = TP ? ((j == cj) ? b_cj : 0.0) : dm.Binv[cj * NJ + j];
       }
       has_lim = lim.has[mi] != 0;
-      lb_c = lim.lb[mi][cj];
-      ub_c = lim.ub[mi][cj];
-      if (VSA) { lb_s = lim.lb[mi][NJ + cj]; ub_s = lim.ub[mi][NJ + cj]; }
+      if constexpr (!TP) {
+        lb_c = lim.lb[mi][cj];
+        ub_c = lim.ub[mi][cj];
+        if (VSA) { lb_s = lim.lb[mi][NJ + cj]; ub_s = lim.ub[mi][NJ + cj]; }
+      }
       // the values are consumed HERE, so the wait for these loads sits inside this rarely-taken branch and not at
       // the join, where it would drain the prefetch of every knot
       if (VSA) { ASLR_UNROLL for (int j = 0; j < NJ; ++j) asm volatile("" : "+v"(Brow[j])); asm volatile("" : "+v"(lb_s), "+v"(ub_s)); }

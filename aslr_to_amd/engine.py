@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .lowering import lower_problem
+from .lowering import lower_problem, lower_traj_params
 
 
 def _torch():
@@ -43,6 +43,26 @@ class Engine(object):
                                                     nbytes, self._stream(), C.byref(self.handle)),
                        "aslr_problem_create")
         self._views = {}
+        if getattr(lowered, "traj_params", None):
+            self.upload_traj_params(lowered.traj_params)
+
+    def set_trajectory_params(self, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
+        """Per-trajectory diagonals of K and B ([B, nj]) and control boxes ([B, nu], or the models' own narrower nu:
+        padded like lower_traj_params says) for the B trajectories of this shard (aslr_set_trajectory_params); every
+        field optional, all None: back to the models' constants.  Callable between solves."""
+        low = self.low
+        self.upload_traj_params(lower_traj_params(low.desc, low.nj, low.nu, self.nu_user, low.dam, stiffness,
+                                                  motor_inertia, u_lb, u_ub))
+
+    def upload_traj_params(self, tp):
+        """tp: what lower_traj_params returned (validated, device-sized), or None: no table"""
+        if tp is None:
+            self._call("aslr_set_trajectory_params", None, self._stream())
+            return
+        st = _abi.TrajParams()
+        for name, a in tp.items():
+            setattr(st, name, a.ctypes.data_as(C.POINTER(C.c_double)))
+        self._call("aslr_set_trajectory_params", C.byref(st), self._stream())  # (synchronous upload: tp may die now)
 
     def _stream(self):
         torch = _torch()

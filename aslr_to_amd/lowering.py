@@ -13,8 +13,10 @@ from . import _abi
 class LoweredProblem(object):
     """Owns the ctypes description and the numpy buffers its pointers refer to."""
 
-    def __init__(self, desc, node_model, x0, frame_ref, nj, nx, nu, dam, nu_user=None):
+    def __init__(self, desc, node_model, x0, frame_ref, nj, nx, nu, dam, nu_user=None, traj_params=None):
         self.desc, self.node_model, self.x0, self.frame_ref = desc, node_model, x0, frame_ref
+        # per-trajectory parameter table: dict of the given fields (device-sized, see lower_traj_params), or None
+        self.traj_params = traj_params
         self.nj, self.nx, self.nu, self.dam = nj, nx, nu, dam
         # nu: control size on the device; nu_user: the models' own nu (smaller for a pendulum actuation with one motor
         # command: the lowered controls are padded, models._DifferentialBase.lower)
@@ -23,10 +25,63 @@ class LoweredProblem(object):
         self.rec = _abi.record_len(nx, nu)
 
 
-def lower_problem(x0s, running_models, terminal_model, frame_refs=None):
+TRAJ_PARAM_FIELDS = ("stiffness", "motor_inertia", "u_lb", "u_ub")
+
+
+def lower_traj_params(desc, nj, nu, nu_user, dam, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
+    """Validate a per-trajectory parameter table against a lowered description (the checks aslr_set_trajectory_params
+    repeats on its side) and bring it to the device's sizes: -> dict of C-contiguous float64 arrays, stiffness /
+    motor_inertia [B, nj] and u_lb / u_ub [B, nu], holding the given fields only; None when no field is given.
+    Bounds of width nu_user < nu (one-command pendulum actuation) are padded with the box the models give their padded
+    commands, [-1, 1] (models._DifferentialBase.lower): the padded commands stay at zero inside it."""
+    given = dict(stiffness=stiffness, motor_inertia=motor_inertia, u_lb=u_lb, u_ub=u_ub)
+    if all(v is None for v in given.values()):
+        return None
+    B = desc.B
+    models = [desc.models[i] for i in range(desc.nmodels)]
+    out = {}
+    for name, v in given.items():
+        if v is None:
+            continue
+        a = np.array(v, dtype=np.float64, ndmin=2)
+        # accepted widths (the first one is named in the messages) and the width on the device
+        widths, width = ((nj,), nj) if name in ("stiffness", "motor_inertia") else ((nu_user, nu), nu)
+        if a.ndim != 2 or a.shape[0] != B:
+            raise ValueError("%s needs one row per trajectory ([%d, %d]), got shape %r" % (name, B, widths[0], a.shape))
+        if a.shape[1] not in widths:
+            raise ValueError("%s must have %d entries per trajectory, got %d" % (name, widths[0], a.shape[1]))
+        if a.shape[1] < width:
+            a = np.concatenate([a, np.full((B, width - a.shape[1]), -1.0 if name == "u_lb" else 1.0)], axis=1)
+        out[name] = np.ascontiguousarray(a)
+    if "stiffness" in out:
+        if dam == _abi.DAM_VSA:
+            raise ValueError("a VSA model takes its stiffness from u: no per-trajectory stiffness")
+        if not (np.all(np.isfinite(out["stiffness"])) and np.all(out["stiffness"] >= 0.0)):
+            raise ValueError("stiffness entries must be finite and >= 0")
+    if "motor_inertia" in out and not (np.all(np.isfinite(out["motor_inertia"])) and np.all(out["motor_inertia"] > 0.0)):
+        raise ValueError("motor_inertia entries must be finite and > 0")
+    if "u_lb" in out or "u_ub" in out:
+        limited = [m for m in models if m.has_u_limits]
+        if not limited:
+            raise ValueError("u_lb / u_ub given, but no action model of the problem has control limits")
+        lb = out["u_lb"] if "u_lb" in out else np.array(limited[0].u_lb[:nu])[None]
+        ub = out["u_ub"] if "u_ub" in out else np.array(limited[0].u_ub[:nu])[None]
+        if not np.all(lb <= ub):  # (also false for NaN)
+            raise ValueError("u_lb <= u_ub must hold for every trajectory and control")
+    for i, m in enumerate(models):
+        for nm in ("K", "B"):
+            M = np.array(getattr(m, nm)[:nj * nj]).reshape(nj, nj)
+            if np.any(M != np.diag(np.diag(M))):
+                raise ValueError("per-trajectory parameters need diagonal K and B: %s of action model %d is not" % (nm, i))
+    return out
+
+
+def lower_problem(x0s, running_models, terminal_model, frame_refs=None, stiffness=None, motor_inertia=None, u_lb=None,
+                  u_ub=None):
     """x0s: [B, nx] (or [nx]); running_models: list of T IntegratedActionModelEulerASR;
     frame_refs: optional [B, 12] (row-major R, p) or list of SE3 overriding every frame-placement
-    reference per trajectory."""
+    reference per trajectory; stiffness / motor_inertia [B, nj], u_lb / u_ub [B, nu]: optional per-trajectory
+    diagonals of K and B and control boxes (lower_traj_params; LoweredProblem.traj_params)."""
     x0 = np.ascontiguousarray(np.atleast_2d(np.asarray(x0s, dtype=np.float64)))
     B = x0.shape[0]
     T = len(running_models)
@@ -72,7 +127,8 @@ def lower_problem(x0s, running_models, terminal_model, frame_refs=None):
         desc.frame_ref = fr.ctypes.data_as(C.POINTER(C.c_double))
     desc.node_model = node_model.ctypes.data_as(C.POINTER(C.c_int32))
     desc.x0 = x0.ctypes.data_as(C.POINTER(C.c_double))
-    return LoweredProblem(desc, node_model, x0, fr, nj, nx, nu, dam, nu_user)
+    tp = lower_traj_params(desc, nj, nu, nu_user, dam, stiffness, motor_inertia, u_lb, u_ub)
+    return LoweredProblem(desc, node_model, x0, fr, nj, nx, nu, dam, nu_user, tp)
 
 
 def shard_rows(B, rank, world_size):

@@ -215,9 +215,55 @@ SCENARIOS = {"two_dof_vsa_boxddp": two_dof_vsa_boxddp, "two_dof_vsa_modified": t
              "talos_arm_vsa": talos_arm_vsa}
 
 
+# Seeded per-trajectory parameter tables for the design sweeps (aslr_set_trajectory_params): factors on the scenario's own
+# constants, log-uniform in the given range, per trajectory and joint.  Defaults: a factor of 2 either way in stiffness,
+# 1.5 in motor inertia; the stiffness FLOOR of a VSA box alternates between the two example scripts' values, 0
+# (examples/two_dof_vsa_boxddp.py:59) and 0.002 (examples/two_dof_vsa_modified.py:56), by halves of the batch.
+def with_traj_params(sc, seed=0, stiffness_range=(0.5, 2.0), inertia_range=(2.0 / 3.0, 1.5), stiffness_floors=None):
+    """-> a copy of scenario `sc` with sc["traj_params"] = dict(stiffness, motor_inertia, u_lb, u_ub) (None where the
+    scenario has nothing to vary: stiffness for VSA, bounds without limits).  Row b equals the models' constants scaled
+    by its factors; stiffness_floors = (f0, f1): the first half of the batch gets stiffness lower bound f0, the second f1."""
+    rng = np.random.default_rng(seed)
+    B = np.atleast_2d(sc["x0"]).shape[0]
+    m = sc["running"][0]
+    low = m.lower()
+    nj, nu = m.state.pinocchio.nv, m.nu
+    Kd = np.array(low.K[:nj * nj]).reshape(nj, nj).diagonal()
+    Bd = np.array(low.B[:nj * nj]).reshape(nj, nj).diagonal()
+    lograng = lambda r, n: np.exp(rng.uniform(np.log(r[0]), np.log(r[1]), (B, n)))
+    tp = dict(stiffness=None, motor_inertia=Bd * lograng(inertia_range, nj), u_lb=None, u_ub=None)
+    if low.dam == 0:
+        tp["stiffness"] = Kd * lograng(stiffness_range, nj)
+    if low.has_u_limits and stiffness_floors is not None:
+        lb = np.tile(np.asarray(m.u_lb, dtype=float), (B, 1))
+        lb[:B // 2, nu // 2:] = stiffness_floors[0]
+        lb[B // 2:, nu // 2:] = stiffness_floors[1]
+        tp["u_lb"] = lb
+        tp["u_ub"] = np.tile(np.asarray(m.u_ub, dtype=float), (B, 1))
+    out = dict(sc)
+    out["traj_params"] = tp
+    return out
+
+
+def constant_traj_params(sc):
+    """the table whose every row repeats the scenario's own constants (a table that must change nothing)"""
+    B = np.atleast_2d(sc["x0"]).shape[0]
+    m = sc["running"][0]
+    low = m.lower()
+    nj = m.state.pinocchio.nv
+    tp = dict(stiffness=None, u_lb=None, u_ub=None,
+              motor_inertia=np.tile(np.array(low.B[:nj * nj]).reshape(nj, nj).diagonal(), (B, 1)))
+    if low.dam == 0:
+        tp["stiffness"] = np.tile(np.array(low.K[:nj * nj]).reshape(nj, nj).diagonal(), (B, 1))
+    if low.has_u_limits:
+        tp["u_lb"] = np.tile(np.asarray(m.u_lb, dtype=float), (B, 1))
+        tp["u_ub"] = np.tile(np.asarray(m.u_ub, dtype=float), (B, 1))
+    return tp
+
+
 def lower(sc):
     from .lowering import lower_problem
-    return lower_problem(sc["x0"], sc["running"], sc["terminal"], sc["frame_refs"])
+    return lower_problem(sc["x0"], sc["running"], sc["terminal"], sc["frame_refs"], **(sc.get("traj_params") or {}))
 
 
 def solver_params(sc, **overrides):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define ASLR_ABI_VERSION 2
+#define ASLR_ABI_VERSION 3
 
 #define ASLR_MAX_NJ     7   /* link-side DoF (2-DoF arm, 7-DoF arm)          */
 #define ASLR_MAX_NX     28  /* 4 * ASLR_MAX_NJ                                */
@@ -198,6 +198,9 @@ typedef struct aslr_solver_params {
  *   TRAJ_F  [ASLR_TF_COUNT][B]  per-trajectory doubles (ASLR_TF_*)
  *   TRAJ_I  [ASLR_TI_COUNT][B]  per-trajectory int32   (ASLR_TI_*)
  *   POOL_SAVE [B][nx + 12]      scratch of aslr_solve_pool (the handle's x0 / frame_ref while pool problems occupy the slots)
+ *   TRAJ_PARAMS [2nj + 2nu][B]  per-trajectory parameter table (aslr_set_trajectory_params), row-major so that consecutive
+ *                               trajectories are consecutive words: nj rows diag(K), nj rows 1 / diag(B), nu rows u_lb, nu rows
+ *                               u_ub; always carved, read only while a table is set
  */
 enum aslr_region_id {
   ASLR_R_XS = 0, ASLR_R_US, ASLR_R_XNEXT, ASLR_R_COST, ASLR_R_DERIV, ASLR_R_GAPS,
@@ -205,6 +208,7 @@ enum aslr_region_id {
   ASLR_R_TRAJ_F, ASLR_R_TRAJ_I, ASLR_R_X0, ASLR_R_FRAME_REF, ASLR_R_VXXF, ASLR_R_DESC,
   ASLR_R_NODE_MODEL, ASLR_R_COST_TRY, ASLR_R_DYN,
   ASLR_R_POOL_SAVE /* [B][nx + 12]: the handle's own x0 / frame_ref columns while aslr_solve_pool streams problems through the slots */,
+  ASLR_R_TRAJ_PARAMS /* [2nj + 2nu][B]: per-trajectory stiffness, motor inertia (reciprocals) and control box */,
   ASLR_R_COUNT
 };
 
@@ -257,7 +261,7 @@ typedef struct aslr_problem aslr_problem_t; /* opaque */
 /* ---- ABI self-description (callable without a GPU) ------------------------------------ */
 int aslr_abi_version(void);
 /* sizeof() of the POD structs above as compiled, so a binding can check its mirror:
- * which = 0 chain, 1 cost, 2 model, 3 problem_desc, 4 solver_params, 5 region, 6 pool */
+ * which = 0 chain, 1 cost, 2 model, 3 problem_desc, 4 solver_params, 5 region, 6 pool, 7 traj_params */
 int64_t aslr_sizeof(int which);
 /* record length in doubles (padded) for given nx, nu */
 int32_t aslr_record_len(int32_t nx, int32_t nu);
@@ -275,6 +279,32 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
                         void *stream, aslr_problem_t **out);
 int aslr_problem_destroy(aslr_problem_t *p);
 int aslr_problem_region(const aslr_problem_t *p, int32_t region_id, aslr_region_t *out);
+
+/* Per-trajectory physical parameters: what the reference's example scripts change between runs -- the spring stiffness
+ * and the motor inertia (examples/two_dof_sea.py:50-51, examples/two_dof_vsa_boxddp.py:50) and the stiffness bounds
+ * (examples/two_dof_vsa_boxddp.py:59-60 against examples/two_dof_vsa_modified.py:56) -- one row per trajectory of the shard,
+ * so that a design sweep is ONE batched solve instead of B handles.  HOST pointers, row-major, each optional (NULL: every
+ * trajectory keeps the models' constant for that field, which the models of the problem must then agree on):
+ *   stiffness     [B][nj]  diagonal of K.  SEA only: a VSA model takes its stiffness from u (ASLR_E_INVALID);
+ *   motor_inertia [B][nj]  diagonal of B, finite and > 0 (the kernels use the reciprocals);
+ *   u_lb, u_ub    [B][nu]  the control box of every model with has_u_limits set, lb <= ub, no NaN (ASLR_E_INVALID
+ *                          when no model of the problem has limits).
+ * Diagonal because every use in the reference is `c * np.eye(nj)`; a table is accepted only if K and B of every model of
+ * the problem are diagonal themselves. */
+typedef struct aslr_traj_params {
+  const double *stiffness;
+  const double *motor_inertia;
+  const double *u_lb;
+  const double *u_ub;
+} aslr_traj_params_t;
+/* Upload the table (on `stream`; the host arrays may be released on return) and switch the handle to the kernels that
+ * read it; tp == NULL switches back to the models' constants.  Callable between solves.  Honoured by aslr_calc,
+ * aslr_calc_diff, aslr_backward_pass, aslr_forward_pass, aslr_iterate*, aslr_solve and aslr_quasi_static, sub-shards
+ * included.  aslr_dam_eval / aslr_dam_residuals keep the MODELS' constants (they evaluate a model at arbitrary points,
+ * not a trajectory), and aslr_solve_pool declines a handle with a table set (ASLR_E_INVALID: a pool problem would inherit
+ * the parameters of whatever slot it lands in).  Returns ASLR_E_INVALID with a message (aslr_last_error) for a bad table;
+ * the handle is then left as it was. */
+int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, void *stream);
 
 /* ---- the hot path ---------------------------------------------------------------------- */
 /* ShootingProblem.calc(xs, us): IntegratedActionModelEulerASR.calc on every node
@@ -367,7 +397,8 @@ int aslr_count_active(aslr_problem_t *p, void *stream, int32_t *active);
  * unittest/test_vsa_freefwddyn.py:26-38).  All pointers are DEVICE pointers; x [n][nx], u [n][nu];
  * outputs (row-major, any may be NULL): xout [n][2nj], cost [n], Fx [n][2nj*nx], Fu [n][2nj*nu],
  * Lx [n][nx], Lu [n][nu], Lxx [n][nx*nx], Lxu [n][nx*nu], Luu [n][nu*nu].  Trajectory 0's
- * frame_ref override (if any) applies. */
+ * frame_ref override (if any) applies.  K and B are the MODEL's, whatever aslr_set_trajectory_params has set (and so
+ * for aslr_dam_residuals). */
 int aslr_dam_eval(aslr_problem_t *p, int32_t model_index, int32_t n, const double *x,
                   const double *u, double *xout, double *cost, double *Fx, double *Fu, double *Lx,
                   double *Lu, double *Lxx, double *Lxu, double *Luu, void *stream);

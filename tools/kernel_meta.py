@@ -2,7 +2,9 @@
 of its instruction text: tools/kernel_meta.py file.s [name-filter]
 The hash covers the lines from the kernel's label to .end_amdhsa_kernel without comments and with the function
 index taken out of local labels (.LBB<k>_<n>, .Lfunc_end<k>: it only counts the kernels of the file), so that two builds
-can be compared kernel by kernel (profiles/launch_table/)."""
+can be compared kernel by kernel (profiles/launch_table/).  With a third argument the kernel's own mangled name is taken out
+of the hashed text too, so that a kernel whose template argument list grew compares equal when its instructions did not
+change (profiles/traj_params/)."""
 import hashlib, re, subprocess, sys
 s = open(sys.argv[1]).read()
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
@@ -14,6 +16,8 @@ def text_hash(name):
     lines = [l.split(';')[0].rstrip() for l in body.split('\n')]  # (comments: whole lines and the loop notes behind labels)
     lines = [l for l in lines if l]
     body = re.sub(r'\.L(BB|func_begin|func_end|tmp)\d+', r'.L\1', '\n'.join(lines))
+    if len(sys.argv) > 3:
+        body = body.replace(name, 'KERNEL')
     return hashlib.sha1(body.encode()).hexdigest()[:16]
 
 
