@@ -10,6 +10,8 @@ from aslr_to_amd import _abi, scenarios
 
 import _geometry_chains as gc
 import _parity
+from _forward_case import (forward_inputs as _forward_inputs, random_candidate as _random_candidate,
+                           run_forward as _run_forward)
 
 pytestmark = pytest.mark.gpu
 
@@ -40,15 +42,6 @@ def _bits(t):
     return t.view(torch.int64) if t.dtype == torch.float64 else t
 
 
-def _random_candidate(low, seed):
-    rng = np.random.default_rng(seed)
-    xs = rng.uniform(-0.8, 0.8, (low.T + 1, low.B, low.nx))
-    us = rng.uniform(-1.0, 1.0, (low.T, low.B, low.nu))
-    if low.dam == _abi.DAM_VSA:
-        us[..., low.nu // 2:] = rng.uniform(0.1, 5.0, (low.T, low.B, low.nu // 2))
-    return xs, us
-
-
 def _check_calc_and_calc_diff(oracle, low, seed=1):
     """Both sweeps of test_gpu_parity.test_calc_and_calcdiff_match_oracle: calcDiff, calc alone, and calcDiff at a second
     point (the variant that skips the record chunks the first sweep already holds)."""
@@ -72,29 +65,6 @@ def _check_calc_and_calc_diff(oracle, low, seed=1):
             _sync()
             assert _relerr(_np(e.region(_abi.R_XNEXT)), xnext) < 1e-11
             assert _relerr(_np(e.region(_abi.R_COST)), cost) < 1e-11
-    return e
-
-
-def _forward_inputs(oracle, low, sp, seed, fddp):
-    xs, us = _random_candidate(low, seed)
-    _, _, deriv = oracle.calc_diff(low, xs, us)
-    rng = np.random.default_rng(seed + 7)
-    gaps = rng.uniform(-0.05, 0.05, (low.T + 1, low.B, low.nx))
-    ref_b = oracle.backward_pass(low, sp, deriv, gaps, us, 1e-3, 0 if fddp else 1)
-    return xs, us, 0.05 * ref_b["K"], 0.05 * ref_b["k"], gaps   # mild gains keep every alpha's rollout finite
-
-
-def _run_forward(low, sp, xs, us, K, k, gaps, feasible):
-    import torch
-    e = _engine(low)
-    e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-    e.region(_abi.R_US).copy_(torch.as_tensor(us))
-    e.region(_abi.R_KGAIN).copy_(torch.as_tensor(K))
-    e.region(_abi.R_KFF).copy_(torch.as_tensor(k))
-    e.region(_abi.R_GAPS).copy_(torch.as_tensor(gaps))
-    e.region(_abi.R_TRAJ_I)[_abi.TI_FEASIBLE].fill_(feasible)
-    e.forward_pass(sp)
-    _sync()
     return e
 
 

@@ -142,3 +142,68 @@ def test_ddp_solves_an_lq_like_problem_in_few_iterations_and_openmp_matches_seri
     b = oracle.solve(low, sp, nthreads=4)
     np.testing.assert_array_equal(a["xs"], b["xs"])
     np.testing.assert_array_equal(a["traj_i"], b["traj_i"])
+
+
+@pytest.mark.parametrize("name,kw", [("two_dof_sea", dict(B=3, T=6)), ("talos_arm_sea", dict(B=3, T=6))])
+def test_fddp_rollout_contracts_the_gaps_by_one_minus_alpha(oracle, name, kw):
+    """SolverFDDP's forwardPass from an infeasible candidate: the trial's own gaps -- x0 - xs_try[0] and
+    xnext(xs_try[t-1], us_try[t-1]) - xs_try[t], recomputed by calc on the trial -- are (1 - alpha) times the gaps the
+    rollout was given, for every alpha = 2^-a; from a feasible candidate, or with alpha = 1, they are closed.  Both sides
+    evaluate the same knots on the same bits, so what is left is the rounding of xs_try = xnext + (alpha - 1) f and of
+    the difference: a few eps of the state, held to 1e-12 of the largest gap of the knot (0.05 here) and to 1e-12
+    absolute where the gaps close."""
+    sc = scenarios.SCENARIOS[name](**kw)
+    low = scenarios.lower(sc)
+    sp = scenarios.solver_params(sc, solver="SolverFDDP")
+    T, B, nx, nu = low.T, low.B, low.nx, low.nu
+    rng = np.random.default_rng(2)
+    xs = rng.uniform(-0.8, 0.8, (T + 1, B, nx))
+    us = rng.uniform(-1.0, 1.0, (T, B, nu))
+    gaps = rng.uniform(-0.05, 0.05, (T + 1, B, nx))
+    _, _, deriv = oracle.calc_diff(low, xs, us)
+    ref_b = oracle.backward_pass(low, sp, deriv, gaps, us, 1e-3, 0)
+    K, k = 0.05 * ref_b["K"], 0.05 * ref_b["k"]   # mild gains keep every alpha's rollout finite
+
+    def trial_gaps(alpha, feasible):
+        xs_try, us_try, _, fail = oracle.forward_pass(low, sp, alpha, xs, us, K, k, gaps, feasible)
+        assert not fail.any()
+        xnext_try, _, _ = oracle.calc_diff(low, xs_try, us_try, diff=False)
+        return np.concatenate([(np.asarray(sc["x0"]) - xs_try[0])[None], xnext_try[:-1] - xs_try[1:]])
+
+    worst = 0.0
+    for a in range(_abi.NALPHA):
+        alpha = 0.5 ** a
+        new = trial_gaps(alpha, 0)
+        if a == 0:
+            assert np.abs(new).max() < 1e-12
+        else:
+            err = np.abs(new - (1.0 - alpha) * gaps).max(axis=2) / np.abs((1.0 - alpha) * gaps).max(axis=2)
+            worst = max(worst, err.max())
+            assert err.max() < 1e-12, (a, err.max())
+        assert np.abs(trial_gaps(alpha, 1)).max() < 1e-12
+    print("%s: gap contraction, worst relative error %.2e" % (name, worst))
+
+
+def test_feasible_warm_start_runs_ddp_and_fddp_identically(oracle):
+    """From a candidate declared feasible (is_feasible = 1: the oracle's own iterate after three cold iterations)
+    SolverFDDP has no gap terms left -- dv = 0, d1 = dg, d2 = dq, and its acceptance test is SolverDDP's -- so both
+    solvers take the same steps: the same iteration counts and bit-identical iterates, all 16 converged."""
+    sc = scenarios.two_dof_sea(B=16, T=40)
+    low = scenarios.lower(sc)
+    cold = oracle.solve(low, scenarios.solver_params(sc, solver="SolverDDP", maxiter=3))
+    assert (cold["traj_i"][_abi.TI_ITER] == 3).all()
+    out = {}
+    for solver in ("SolverDDP", "SolverFDDP"):
+        sp = scenarios.solver_params(sc, solver=solver, is_feasible=1)
+        out[solver] = oracle.solve(low, sp, xs=cold["xs"], us=cold["us"], log_cap=sp.maxiter)
+    d, f = out["SolverDDP"], out["SolverFDDP"]
+    assert ((d["traj_i"][_abi.TI_STATUS] & _abi.ST_CONVERGED) != 0).all()
+    np.testing.assert_array_equal(d["traj_i"][_abi.TI_ITER], f["traj_i"][_abi.TI_ITER])
+    np.testing.assert_array_equal(d["traj_i"][_abi.TI_STATUS], f["traj_i"][_abi.TI_STATUS])
+    np.testing.assert_array_equal(d["xs"], f["xs"])
+    np.testing.assert_array_equal(d["us"], f["us"])
+    on = ~np.isnan(d["log"][:, _abi.LOG_COST])
+    assert (f["log"][:, _abi.LOG_FEASIBLE][on] == 1).all()
+    for row in (_abi.LOG_ACCEPTED, _abi.LOG_XREG, _abi.LOG_COST):
+        np.testing.assert_array_equal(d["log"][:, row], f["log"][:, row])
+    print("feasible warm start: iterations %s" % d["traj_i"][_abi.TI_ITER])
