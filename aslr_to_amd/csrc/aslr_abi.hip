@@ -1,5 +1,6 @@
 // aslr_abi.hip -- the C ABI of include/aslr_to_amd.h: handle, workspace carving, solver driver.
 // The kernels live in aslr_calc_*.hip / aslr_backward_*.hip / aslr_forward_*.hip.
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -8,12 +9,11 @@
 using namespace aslr;
 
 namespace {
-thread_local char g_err_storage[kErrLen] = {0};
+thread_local char g_err[kErrLen] = {0};
 }
 namespace aslr {
-char *err_buf() { return g_err_storage; }
+char *err_buf() { return g_err; }
 } // namespace aslr
-#define g_err g_err_storage
 
 namespace {
 
@@ -160,10 +160,8 @@ struct aslr_problem {
   bool have_sub;
   unsigned sub_flags;
   // model-only chunks of the DERIV records (cost-weight diagonals): const_ok = the cost stacks allow skipping them,
-  // const_written = a sweep that evaluated every knot of every trajectory has put them in place
+  // const_written = a sweep that evaluated every knot of every trajectory has put them in place (diff_mode)
   bool const_ok, const_written;
-  bool const_pending_full; // aslr_iterate_n: the first sweep of this call is the one that puts them in place
-  int pool_maxiter;        // > 0 inside aslr_solve_pool: trajectories stop by themselves after this many iterations
 };
 
 namespace {
@@ -304,6 +302,11 @@ bool is_identity3(const double *R) {
   for (int i = 0; i < 9; ++i) if (R[i] != (i % 4 == 0 ? 1.0 : 0.0)) return false;
   return true;
 }
+bool is_diagonal(int n, const double *A) {
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) if (i != j && A[i * n + j] != 0.0) return false;
+  return true;
+}
 
 // Closed-form frame-placement residuals (ChainPlanar::reach_residual) need: a planar chain, every cost frame turned
 // about z on its joint, every reference rotation -- cost defaults and per-trajectory overrides -- exactly the identity.
@@ -369,13 +372,20 @@ const KernelSet *find_kernel_set(int nj, int dam, bool traj_params = false) {
   return nullptr;
 }
 
-// ---- launch helpers: the handle's state in front of the launchers of its size ----
-int launch_calc(aslr_problem *p, bool diff, int mode, double th_gaptol, hipStream_t st, bool all_computed = false) {
-  if (diff && p->const_ok && !(mode & kModeNoCompute)) {
-    if (p->const_written) mode |= kModeSkipConst;
-    else if (all_computed) p->const_written = true; // this launch writes them
-  }
-  return p->ks->calc(p->k, diff, mode, th_gaptol, st);
+// ---- launch helpers: the launchers of the handle's size, with the argument block k the caller launches with ----
+// The mode word of a calcDiff launch with block k.  A sweep may mark the model-only record chunks written only when it
+// evaluates every knot of every trajectory (`full`: the caller's fact), covers the shard up to B (of sub-shards: the last
+// one's) and the cost stacks allow the skip; once marked, calcDiff launches carry kModeSkipConst, until
+// aslr_set_trajectory_params resets the mark.
+int diff_mode(aslr_problem *p, const KArgs &k, int mode, bool full) {
+  if (!p->const_ok) return mode;
+  if (p->const_written) return mode | kModeSkipConst;
+  if (full && k.b1 == p->desc.B) p->const_written = true; // this launch writes them
+  return mode;
+}
+
+int launch_calc(const aslr_problem *p, const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st) {
+  return p->ks->calc(k, diff, mode, th_gaptol, st);
 }
 
 ModelLimits make_limits(const aslr_problem *p) {
@@ -400,17 +410,31 @@ int solver_unsupported(const aslr_problem *p, int solver) {
   return ASLR_OK;
 }
 
-int launch_backward(aslr_problem *p, const SolverDev &sd, hipStream_t st) {
+int launch_backward(const aslr_problem *p, const KArgs &k, const SolverDev &sd, hipStream_t st) {
   if (int rc = solver_unsupported(p, sd.solver)) return rc;
-  return p->ks->backward(p->k, p->bwd_hs, p->blk_mfma != 0, sd, make_limits(p), st);
+  return p->ks->backward(k, p->bwd_hs, p->blk_mfma != 0, sd, make_limits(p), st);
 }
 
-int launch_forward(aslr_problem *p, const SolverDev &sd, hipStream_t st) {
+int launch_forward(const aslr_problem *p, const KArgs &k, const SolverDev &sd, hipStream_t st) {
   if (int rc = solver_unsupported(p, sd.solver)) return rc;
-  return p->ks->forward(p->k, sd, make_limits(p), st);
+  return p->ks->forward(k, sd, make_limits(p), st);
 }
 
 double reg_start(const aslr_solver_params_t *sp) { return std::isnan(sp->reg_init) ? sp->reg_min : sp->reg_init; }
+
+// solver state of the trajectories [k.b0, k.b1) at solve() entry
+int launch_init_state(const KArgs &k, const aslr_solver_params_t *sp, hipStream_t st) {
+  hipLaunchKernelGGL(init_state_kernel, dim3((k.b1 - k.b0 + 255) / 256), dim3(256), 0, st, k, reg_start(sp), sp->is_feasible);
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
+
+// no accepted candidate left to commit (the handle's block: the whole shard)
+int launch_reset_accepted(const KArgs &k, hipStream_t st) {
+  hipLaunchKernelGGL(reset_accepted_kernel, dim3((k.B + 255) / 256), dim3(256), 0, st, k);
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
 
 } // namespace
 
@@ -481,13 +505,11 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { snprintf(g_err, sizeof g_err, "no HIP device"); return ASLR_E_NODEVICE; }
-  aslr_problem *p = new (std::nothrow) aslr_problem();
-  if (p) {
-    const char *eh = getenv("ASLR_BWD_HS"), *em = getenv("ASLR_BLK_MFMA");
-    p->bwd_hs = eh ? atoi(eh) : 0;
-    p->blk_mfma = em ? (atoi(em) != 0) : 1;
-  }
+  std::unique_ptr<aslr_problem> p(new (std::nothrow) aslr_problem()); // (owns nothing but memory until h_done below)
   if (!p) return ASLR_E_INVALID;
+  const char *eh = getenv("ASLR_BWD_HS"), *em = getenv("ASLR_BLK_MFMA");
+  p->bwd_hs = eh ? atoi(eh) : 0;
+  p->blk_mfma = em ? (atoi(em) != 0) : 1;
   p->desc = *desc;
   p->desc.node_model = nullptr; p->desc.x0 = nullptr; p->desc.frame_ref = nullptr;
   p->nj = nj; p->nx = nx; p->nu = nu; p->dam = dam; p->rec = rec_len_c(nx, nu);
@@ -501,7 +523,6 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   carve(desc, nx, nu, p->regions, &total);
   if (!workspace || workspace_bytes < total || (reinterpret_cast<uintptr_t>(workspace) & 255u)) {
     snprintf(g_err, sizeof g_err, "workspace needs %lld bytes, 256-B aligned (got %lld)", (long long)total, (long long)workspace_bytes);
-    delete p;
     return ASLR_E_WORKSPACE;
   }
   p->ws = static_cast<char *>(workspace);
@@ -509,23 +530,22 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   hipStream_t st = static_cast<hipStream_t>(stream);
   auto reg = [&](int id) { return p->ws + p->regions[id].offset; };
   // device description (with Binv)
-  DevDesc *hd = new DevDesc();
-  memset(hd, 0, sizeof *hd);
+  std::unique_ptr<DevDesc> hd(new DevDesc());
+  memset(hd.get(), 0, sizeof *hd);
   hd->chain = desc->chain;
   fill_planar(desc->chain, &hd->planar);
   const int planar_ok = hd->planar.ok;
-  fill_planar_reach(desc, hd);
+  fill_planar_reach(desc, hd.get());
   const int planar_reach = hd->planar.reach_ok;
   for (int i = 0; i < desc->nmodels; ++i) {
     hd->models[i].m = desc->models[i];
     if (!invert(nj, desc->models[i].B, hd->models[i].Binv)) {
       snprintf(g_err, sizeof g_err, "motor inertia B of model %d is singular", i);
-      delete hd; delete p;
       return ASLR_E_INVALID;
     }
   }
   hd->traj_params = reinterpret_cast<const double *>(reg(ASLR_R_TRAJ_PARAMS));
-  hipError_t e = hipMemcpyAsync(reg(ASLR_R_DESC), hd, sizeof(DevDesc), hipMemcpyHostToDevice, st);
+  hipError_t e = hipMemcpyAsync(reg(ASLR_R_DESC), hd.get(), sizeof(DevDesc), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(reg(ASLR_R_NODE_MODEL), desc->node_model, sizeof(int32_t) * (desc->T + 1), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(reg(ASLR_R_X0), desc->x0, sizeof(double) * desc->B * nx, hipMemcpyHostToDevice, st);
   if (e == hipSuccess && desc->frame_ref) e = hipMemcpyAsync(reg(ASLR_R_FRAME_REF), desc->frame_ref, sizeof(double) * desc->B * 12, hipMemcpyHostToDevice, st);
@@ -536,12 +556,10 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   if (e == hipSuccess) e = hipMemsetAsync(reg(ASLR_R_DERIV), 0, p->regions[ASLR_R_DERIV].bytes, st);
   if (e == hipSuccess) e = hipMemsetAsync(reg(ASLR_R_KFF), 0, p->regions[ASLR_R_KFF].bytes, st);
   if (e == hipSuccess) e = hipMemsetAsync(reg(ASLR_R_VXXF), 0, p->regions[ASLR_R_VXXF].bytes, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st); // the host staging buffers die below
-  delete hd;
+  if (e == hipSuccess) e = hipStreamSynchronize(st); // the host staging buffers die on return
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&p->h_done), sizeof(int32_t) * desc->B, 0);
   if (e != hipSuccess) {
     snprintf(g_err, sizeof g_err, "upload failed: %s", hipGetErrorString(e));
-    delete p;
     return ASLR_E_HIP;
   }
   KArgs &k = p->k;
@@ -559,14 +577,14 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   k.traj_f = (double *)reg(ASLR_R_TRAJ_F); k.traj_i = (int32_t *)reg(ASLR_R_TRAJ_I);
   k.B = desc->B; k.T = desc->T;
   k.b0 = 0; k.b1 = desc->B;
-  p->nsub = 1; p->have_sub = false; p->pool_maxiter = 0;
+  p->nsub = 1; p->have_sub = false;
   p->sub_b[0] = 0; p->sub_b[1] = desc->B;
   k.planar = planar_ok;
   k.planar_reach = planar_reach;
   k.iter_log = nullptr; k.log_cap = 0;
   k.seg_t0 = 0; k.seg_t1 = desc->T;
   k.pipeline = getenv("ASLR_PIPELINE") ? atoi(getenv("ASLR_PIPELINE")) : 1; // (read once, when the handle is created)
-  *out = p;
+  *out = p.release();
   return ASLR_OK;
 }
 
@@ -588,14 +606,6 @@ int aslr_problem_region(const aslr_problem_t *p, int32_t region_id, aslr_region_
   *out = p->regions[region_id];
   return ASLR_OK;
 }
-
-namespace {
-bool is_diagonal(int n, const double *A) {
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) if (i != j && A[i * n + j] != 0.0) return false;
-  return true;
-}
-} // namespace
 
 int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, void *stream) {
   if (!p) return ASLR_E_INVALID;
@@ -657,53 +667,72 @@ int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, 
 
 int aslr_calc(aslr_problem_t *p, void *stream) {
   if (!p) return ASLR_E_INVALID;
-  return launch_calc(p, false, 0, -1.0, static_cast<hipStream_t>(stream));
+  return launch_calc(p, p->k, false, 0, -1.0, static_cast<hipStream_t>(stream));
 }
 
 int aslr_calc_diff(aslr_problem_t *p, void *stream) {
   if (!p) return ASLR_E_INVALID;
-  return launch_calc(p, true, 0, -1.0, static_cast<hipStream_t>(stream), true);
+  return launch_calc(p, p->k, true, diff_mode(p, p->k, 0, true), -1.0, static_cast<hipStream_t>(stream));
 }
 
 int aslr_backward_pass(aslr_problem_t *p, const aslr_solver_params_t *sp, void *stream) {
   if (!p || !sp) return ASLR_E_INVALID;
-  return launch_backward(p, to_dev(sp, 1, 1), static_cast<hipStream_t>(stream));
+  return launch_backward(p, p->k, to_dev(sp, 1, 1), static_cast<hipStream_t>(stream));
 }
 
 int aslr_forward_pass(aslr_problem_t *p, const aslr_solver_params_t *sp, void *stream) {
   if (!p || !sp) return ASLR_E_INVALID;
-  return launch_forward(p, to_dev(sp, 1, 0), static_cast<hipStream_t>(stream));
+  return launch_forward(p, p->k, to_dev(sp, 1, 0), static_cast<hipStream_t>(stream));
 }
 
 namespace {
+// what one call of the iteration driver brings along; nothing of it outlives the call
+struct IterOpts {
+  KArgs k;          // the argument block: the handle's, or the pool's copy of it
+  int maxiter_traj; // SolverDev::maxiter_traj (pool solves)
+  bool full_first;  // the first sweep of this call evaluates every knot of every trajectory (diff_mode)
+  hipEvent_t *ev;   // four events around calcDiff / backward / forward of one whole-shard iteration, or nullptr
+};
+
+int record(hipEvent_t *ev, int i, hipStream_t st) {
+  if (ev) HIP_TRY(hipEventRecord(ev[i], st));
+  return ASLR_OK;
+}
+
 // one lock-step iteration of the trajectories [b0, b1) on stream st
-int iterate_range(aslr_problem *p, const aslr_solver_params_t *sp, int first, int b0, int b1, hipStream_t st) {
-  const KArgs full = p->k;
-  p->k.b0 = b0; p->k.b1 = b1; // (the launch helpers read p->k; restored below)
-  int rc = ASLR_OK;
-  if (first) {
-    hipLaunchKernelGGL(init_state_kernel, dim3((b1 - b0 + 255) / 256), dim3(256), 0, st, p->k, reg_start(sp), sp->is_feasible);
-    if (hipGetLastError() != hipSuccess) rc = ASLR_E_HIP;
-  }
+int iterate_range(aslr_problem *p, const aslr_solver_params_t *sp, bool first, bool full, const IterOpts &o, int b0, int b1, hipStream_t st) {
+  KArgs k = o.k;
+  k.b0 = b0; k.b1 = b1;
+  int rc = first ? launch_init_state(k, sp, st) : ASLR_OK;
   SolverDev sd = to_dev(sp, 0, 0);
-  sd.maxiter_traj = p->pool_maxiter;
-  // (the model-only record chunks are marked written by a sweep that covers the WHOLE shard: the last sub-shard's)
-  if (!rc) rc = launch_calc(p, true, kModeCommit | kModeSolver, sp->th_gaptol, st, (first != 0 || p->pool_maxiter > 0) && b1 == p->desc.B && p->const_pending_full);
-  if (!rc) rc = launch_backward(p, sd, st);
-  if (!rc) rc = launch_forward(p, sd, st);
-  p->k = full;
+  sd.maxiter_traj = o.maxiter_traj;
+  if (!rc) rc = record(o.ev, 0, st);
+  if (!rc) rc = launch_calc(p, k, true, diff_mode(p, k, kModeCommit | kModeSolver, full), sp->th_gaptol, st);
+  if (!rc) rc = record(o.ev, 1, st);
+  if (!rc) rc = launch_backward(p, k, sd, st);
+  if (!rc) rc = record(o.ev, 2, st);
+  if (!rc) rc = launch_forward(p, k, sd, st);
+  if (!rc) rc = record(o.ev, 3, st);
   return rc;
 }
 
-// fork: the sub-shard streams wait for what the caller's stream has enqueued so far
-int sub_fork(aslr_problem *p, hipStream_t st) {
-  HIP_TRY(hipEventRecord(p->sub_fork, st));
+// n lock-step iterations enqueued on st
+int iterate(aslr_problem *p, const aslr_solver_params_t *sp, bool first, int n, hipStream_t st, const IterOpts &o) {
+  if (p->nsub <= 1 || o.ev) { // (timed: the whole shard on the caller's stream, whatever aslr_set_subshards says)
+    for (int it = 0; it < n; ++it)
+      if (int rc = iterate_range(p, sp, first && it == 0, o.full_first && it == 0, o, 0, p->desc.B, st)) return rc;
+    return ASLR_OK;
+  }
+  // Each sub-shard runs its n iterations on its own stream with no synchronisation between sub-shards (trajectories
+  // are independent): their kernels interleave freely, the serial sweeps of one under the streaming kernels of the
+  // others.  The caller's stream is forked from before and joined after, so for the caller the call is still "n
+  // iterations enqueued on my stream".
+  HIP_TRY(hipEventRecord(p->sub_fork, st)); // fork: the sub-shard streams wait for what st holds so far
   for (int s = 1; s < p->nsub; ++s) HIP_TRY(hipStreamWaitEvent(p->sub_stream[s], p->sub_fork, 0));
-  return ASLR_OK;
-}
-// join: the caller's stream waits for every sub-shard stream
-int sub_join(aslr_problem *p, hipStream_t st) {
-  for (int s = 1; s < p->nsub; ++s) {
+  for (int it = 0; it < n; ++it)
+    for (int s = 0; s < p->nsub; ++s)
+      if (int rc = iterate_range(p, sp, first && it == 0, o.full_first && it == 0, o, p->sub_b[s], p->sub_b[s + 1], s == 0 ? st : p->sub_stream[s])) return rc;
+  for (int s = 1; s < p->nsub; ++s) { // join: st waits for every sub-shard stream
     HIP_TRY(hipEventRecord(p->sub_join[s], p->sub_stream[s]));
     HIP_TRY(hipStreamWaitEvent(st, p->sub_join[s], 0));
   }
@@ -742,23 +771,8 @@ int aslr_set_subshards(aslr_problem_t *p, int32_t n) {
 int aslr_iterate_n(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t first, int32_t n, void *stream) {
   if (!p || !sp || n < 0) return ASLR_E_INVALID;
   if (int rc = solver_unsupported(p, sp->solver)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int B = p->desc.B;
-  if (p->pool_maxiter == 0) p->const_pending_full = !p->const_written; // (aslr_solve_pool sets it itself)
-  if (p->nsub <= 1) {
-    for (int it = 0; it < n; ++it)
-      if (int rc = iterate_range(p, sp, first && it == 0, 0, B, st)) return rc;
-    return ASLR_OK;
-  }
-  // Each sub-shard runs its n iterations on its own stream with no synchronisation between sub-shards (trajectories
-  // are independent): their kernels interleave freely, the serial sweeps of one under the streaming kernels of the
-  // others.  The caller's stream is forked from before and joined after, so for the caller the call is still "n
-  // iterations enqueued on my stream".
-  if (int rc = sub_fork(p, st)) return rc;
-  for (int it = 0; it < n; ++it)
-    for (int s = 0; s < p->nsub; ++s)
-      if (int rc = iterate_range(p, sp, first && it == 0, p->sub_b[s], p->sub_b[s + 1], s == 0 ? st : p->sub_stream[s])) return rc;
-  return sub_join(p, st);
+  // (first: init_state_kernel sets RECALC everywhere, so the first sweep evaluates everything)
+  return iterate(p, sp, first != 0, n, static_cast<hipStream_t>(stream), IterOpts{p->k, 0, first != 0, nullptr});
 }
 
 int aslr_iterate(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t first, void *stream) {
@@ -773,21 +787,7 @@ int aslr_iterate_timed(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_
     for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreate(&p->ev[i]));
     p->have_ev = true;
   }
-  if (first) {
-    hipLaunchKernelGGL(init_state_kernel, dim3((p->desc.B + 255) / 256), dim3(256), 0, st, p->k, reg_start(sp), sp->is_feasible);
-    HIP_TRY(hipGetLastError());
-  }
-  const SolverDev sd = to_dev(sp, 0, 0); // (whole shard on the caller's stream, whatever aslr_set_subshards says)
-  HIP_TRY(hipEventRecord(p->ev[0], st));
-  int rc = launch_calc(p, true, kModeCommit | kModeSolver, sp->th_gaptol, st, first != 0); // the first sweep evaluates all
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(p->ev[1], st));
-  rc = launch_backward(p, sd, st);
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(p->ev[2], st));
-  rc = launch_forward(p, sd, st);
-  if (rc) return rc;
-  HIP_TRY(hipEventRecord(p->ev[3], st));
+  if (int rc = iterate(p, sp, first != 0, 1, st, IterOpts{p->k, 0, first != 0, p->ev})) return rc;
   HIP_TRY(hipEventSynchronize(p->ev[3]));
   for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms3[i], p->ev[i], p->ev[i + 1]));
   return ASLR_OK;
@@ -796,11 +796,8 @@ int aslr_iterate_timed(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_
 int aslr_finalize(aslr_problem_t *p, void *stream) {
   if (!p) return ASLR_E_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int rc = launch_calc(p, false, kModeCommit | kModeNoCompute, -1.0, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(reset_accepted_kernel, dim3((p->desc.B + 255) / 256), dim3(256), 0, st, p->k);
-  HIP_TRY(hipGetLastError());
-  return ASLR_OK;
+  if (int rc = launch_calc(p, p->k, false, kModeCommit | kModeNoCompute, -1.0, st)) return rc;
+  return launch_reset_accepted(p->k, st);
 }
 
 int aslr_count_active(aslr_problem_t *p, void *stream, int32_t *active) {
@@ -875,19 +872,18 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
   double *save = reinterpret_cast<double *>(p->ws + p->regions[ASLR_R_POOL_SAVE].offset);
   HIP_TRY(hipMemcpyAsync(save, p->k.x0, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st));
   if (p->k.frame_ref) HIP_TRY(hipMemcpyAsync(save + (size_t)B * p->nx, p->k.frame_ref, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st));
-  aslr_solver_params_t spi = *sp;
-  const KArgs saved = p->k;
-  p->k.iter_log = nullptr; p->k.log_cap = 0; // (a slot's iteration index restarts with every problem)
+  // the pool's argument block; trajectories stop by themselves after maxiter iterations; the first sweep covers every
+  // slot when the pool fills them all
+  IterOpts o{p->k, sp->maxiter, pool->P >= B, nullptr};
+  o.k.iter_log = nullptr; o.k.log_cap = 0; // (a slot's iteration index restarts with every problem)
   // the closed-form reach residual was validated for the references given at create time only (fill_planar_reach):
   // pool targets take the general log map
-  if (pool->frame_ref) p->k.planar_reach = 0;
-  p->pool_maxiter = sp->maxiter;
+  if (pool->frame_ref) o.k.planar_reach = 0;
   int it = 0, rc = ASLR_OK;
   // the slowest possible schedule: every problem takes maxiter iterations, one wave of B problems after the other
   const long long cap = ((long long)(pool->P + B - 1) / B + 1) * (long long)(sp->maxiter + refill_every);
-  bool first = true;
   auto refill = [&] { // flush the stopped slots and hand them their next problems
-    hipLaunchKernelGGL(pool_refill_kernel, dim3(B), dim3(64), 0, st, p->k, pl, reg0, sp->is_feasible);
+    hipLaunchKernelGGL(pool_refill_kernel, dim3(B), dim3(64), 0, st, o.k, pl, reg0, sp->is_feasible);
     return hipGetLastError() == hipSuccess;
   };
   auto flush_and_count = [&](int32_t *fin) { // ... and read how many problems have been written out so far
@@ -898,11 +894,9 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
   };
   while (it < cap) {
     if (!refill()) { rc = ASLR_E_HIP; break; }
-    // (the first sweep covers every slot when the pool fills them all: it puts the model-only record chunks in place)
-    p->const_pending_full = first && pool->P >= B && !p->const_written;
-    rc = aslr_iterate_n(p, &spi, 0, refill_every, stream);
+    rc = iterate(p, sp, false, refill_every, st, o);
     if (rc) break;
-    first = false;
+    o.full_first = false; // (later rounds evaluate the refilled slots only)
     it += refill_every;
     if (it % poll_every < refill_every) {
       int32_t fin = 0;
@@ -914,9 +908,7 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
   int32_t fin_total = -1;
   // one more flush, then every problem must have been written out
   if (!rc && !flush_and_count(&fin_total)) rc = ASLR_E_HIP;
-  p->pool_maxiter = 0;
-  p->k = saved;
-  {
+  { // (after an error in the loop this restore is enqueued without a synchronisation first: ADVICE.md proposes one)
     hipError_t e = hipMemcpyAsync(const_cast<double *>(p->k.x0), save, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && p->k.frame_ref) e = hipMemcpyAsync(const_cast<double *>(p->k.frame_ref), save + (size_t)B * p->nx, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st);
     if (e != hipSuccess && !rc) rc = ASLR_E_HIP;
@@ -927,9 +919,7 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
     snprintf(g_err, sizeof g_err, "aslr_solve_pool: %d of %d problems finished within the iteration bound", fin_total, pool->P);
     return ASLR_E_INVALID;
   }
-  hipLaunchKernelGGL(reset_accepted_kernel, dim3((B + 255) / 256), dim3(256), 0, st, p->k);
-  HIP_TRY(hipGetLastError());
-  return ASLR_OK;
+  return launch_reset_accepted(p->k, st);
 }
 
 int aslr_dam_eval(aslr_problem_t *p, int32_t model_index, int32_t n, const double *x, const double *u, double *xout,

@@ -741,3 +741,105 @@ def test_pool_smaller_than_the_slots_on_a_fresh_handle_and_a_regularisation_that
     torch.cuda.synchronize()
     st = e.traj_i(_abi.TI_STATUS).cpu().numpy()
     assert ((st & _abi.ST_REG_MAX) != 0).all() and int(e.traj_i(_abi.TI_ITER).max()) <= 5
+
+
+@pytest.mark.parametrize("name, solver, B, T", [("two_dof_vsa_boxddp", "SolverBoxDDP", 70, 8), ("talos_arm_sea", "SolverFDDP", 6, 5)])
+def test_iterate_timed_gives_the_bits_of_iterate_n(name, solver, B, T):
+    """aslr_iterate_timed (the per-phase figures of bench.py --full) is the iteration of aslr_iterate_n with events in
+    between: four timed calls, the first with first = True, leave the bits of iterate_n(sp, True, 4) -- also on a handle
+    that iterates sub-shards, which the timed call does not use."""
+    import torch
+    from aslr_to_amd.engine import Engine
+    sc = scenarios.SCENARIOS[name](B=B, T=T, seed=3)
+    low = scenarios.lower(sc)
+    sp = scenarios.solver_params(sc, solver=solver, fixed_iterations=1, maxiter=4)
+    regions = (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_I, _abi.R_DERIV, _abi.R_KGAIN, _abi.R_TRAJ_F)
+    res = []
+    for timed in (True, False):
+        e = Engine(low)
+        e.set_candidate(None, None)
+        if timed:
+            e.set_subshards(2)
+            for i in range(4):
+                ms = e.iterate_timed(sp, first=(i == 0))
+                assert len(ms) == 3 and all(m >= 0.0 for m in ms)
+        else:
+            e.iterate_n(sp, True, 4)
+        e.finalize()
+        torch.cuda.synchronize()
+        res.append([e.region(r).clone() for r in regions])
+    assert int(res[1][2][_abi.TI_ITER].min()) == 4
+    for r, a, b in zip(regions, res[0], res[1]):
+        if r == _abi.R_TRAJ_F:   # (NaN for failed line-search trials)
+            a, b = torch.nan_to_num(a), torch.nan_to_num(b)
+        assert torch.equal(a, b), r
+
+
+@pytest.mark.parametrize("name, B, T, nmax", [("two_dof_sea", 130, 6, 3), ("talos_arm_sea", 70, 5, 2)])
+def test_model_only_record_chunks_are_in_place_whatever_the_schedule(name, B, T, nmax):
+    """The DERIV chunks that depend on the model only are written by the first sweep that evaluates everything and skipped
+    afterwards.  Whatever the sub-shard schedule (1 sub-shard, or as many as there are 64-trajectory blocks), after
+    iterate_n(first) + iterate_n + finalize a calcDiff sweep leaves the records that a fresh handle -- which writes every
+    chunk -- computes at the same point, bit for bit (a chunk wrongly skipped would be zero, or stale); again after a
+    stiffness table is set, and after it is cleared: both reset the mark."""
+    import torch
+    from aslr_to_amd.engine import Engine
+    sc = scenarios.SCENARIOS[name](B=B, T=T, seed=5)
+    low = scenarios.lower(sc)
+    sp = scenarios.solver_params(sc, solver="SolverFDDP")
+    stiffness = scenarios.with_traj_params(sc, seed=6)["traj_params"]["stiffness"]
+    engines = {n: Engine(low) for n in (1, nmax)}
+    for n, e in engines.items():
+        e.set_subshards(n)
+    gap = lambda a, b: "max |difference| %.3e" % float((a - b).abs().max())
+    for tp in (None, dict(stiffness=stiffness), {}):   # as created; a stiffness table set; the table cleared
+        D = {}
+        for n, e in engines.items():
+            if tp is not None:
+                e.set_trajectory_params(**tp)
+            e.set_candidate(None, None)
+            e.iterate_n(sp, True, 2)
+            e.iterate_n(sp, False, 1)
+            e.finalize()
+            e.calc_diff()
+            torch.cuda.synchronize()
+            D[n] = e.region(_abi.R_DERIV).clone()
+        assert torch.equal(D[1], D[nmax]), gap(D[1], D[nmax])
+        fresh = Engine(low)
+        if tp:
+            fresh.set_trajectory_params(**tp)
+        fresh.region(_abi.R_XS).copy_(e.region(_abi.R_XS))
+        fresh.region(_abi.R_US).copy_(e.region(_abi.R_US))
+        fresh.calc_diff()
+        torch.cuda.synchronize()
+        full = fresh.region(_abi.R_DERIV)
+        assert float(full.abs().max()) > 0.0 and torch.equal(D[nmax], full), gap(D[nmax], full)
+
+
+def test_pool_solve_leaves_the_handle_and_its_iteration_log_as_they_were():
+    """aslr_solve_pool launches with its own copy of the handle's argument block (no iteration log: a slot's iteration
+    index restarts with every problem; the general log map for the pool's own references): on a small handle with a log
+    enabled, 20 problems through 8 slots leave the log untouched, and a solve of the handle's own problems afterwards
+    equals the same solve on a fresh engine, bit for bit, with the log filled for the iterations each trajectory ran."""
+    import torch
+    from aslr_to_amd.engine import Engine
+    slots, P, T, maxiter = 8, 20, 6, 15
+    sc = scenarios.two_dof_vsa_boxddp(B=P, T=T, seed=7)
+    sp = scenarios.solver_params(sc, maxiter=maxiter)
+    own = scenarios.lower(dict(sc, x0=sc["x0"][:slots], frame_refs=sc["frame_refs"][:slots]))
+    e = Engine(own)
+    log = e.enable_iteration_log(maxiter)
+    r = e.solve_pool(sc["x0"], sc["frame_refs"], sp)
+    assert int(r["iters"].min()) >= 1 and int(r["iters"].max()) <= maxiter
+    assert bool(torch.isnan(log).all())                   # the pool wrote nothing into the handle's log
+    fresh = Engine(own)
+    for g in (e, fresh):
+        g.set_candidate(None, None)
+        g.solve(sp, poll_every=4)
+    torch.cuda.synchronize()
+    for rid in (_abi.R_XS, _abi.R_US):
+        assert torch.equal(e.region(rid), fresh.region(rid)), rid
+    iters = e.traj_i(_abi.TI_ITER)
+    assert torch.equal(iters, fresh.traj_i(_abi.TI_ITER)) and torch.equal(e.traj_i(_abi.TI_STATUS), fresh.traj_i(_abi.TI_STATUS))
+    ran = torch.arange(maxiter, device=log.device)[:, None] < iters[None, :]    # [iteration, trajectory]
+    assert int(iters.min()) >= 1 and torch.equal(~torch.isnan(log[:, _abi.LOG_COST]), ran)
