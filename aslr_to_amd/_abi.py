@@ -13,7 +13,7 @@ MAX_NU = 14
 MAX_COSTS = 6
 MAX_MODELS = 4
 NALPHA = 10
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 OK, E_INVALID, E_HIP, E_NODEVICE, E_WORKSPACE = 0, -1, -2, -3, -4
 DAM_SEA, DAM_VSA = 0, 1
@@ -89,6 +89,13 @@ class TrajParams(C.Structure):
                 ("u_ub", C.POINTER(_d))]
 
 
+class Mpc(C.Structure):
+    """aslr_mpc_t: a receding-horizon run (aslr_mpc_run); device pointers, time-major arrays."""
+    _fields_ = [("n_steps", _i), ("first_maxiter", _i), ("iters_per_step", _i), ("_pad0", _i),
+                ("disturbance", C.c_void_p), ("x_closed", C.c_void_p), ("u_closed", C.c_void_p),
+                ("stat_f", C.c_void_p), ("stat_i", C.c_void_p)]
+
+
 class Region(C.Structure):
     _fields_ = [("offset", C.c_int64), ("bytes", C.c_int64)]
 
@@ -154,6 +161,7 @@ EXPORTED_SYMBOLS = [
     "aslr_iterate", "aslr_iterate_timed", "aslr_finalize", "aslr_count_active", "aslr_dam_eval", "aslr_quasi_static", "aslr_last_error",
     "aslr_dam_residuals", "aslr_residual_len", "aslr_frame_placement", "aslr_set_iteration_log",
     "aslr_iterate_n", "aslr_set_subshards", "aslr_solve_pool", "aslr_set_trajectory_params",
+    "aslr_mpc_run",
 ]
 
 
@@ -223,11 +231,13 @@ def load_library():
     lib.aslr_set_subshards.argtypes = [vp, i32]
     lib.aslr_set_trajectory_params.restype = C.c_int
     lib.aslr_set_trajectory_params.argtypes = [vp, C.POINTER(TrajParams), vp]
+    lib.aslr_mpc_run.restype = C.c_int
+    lib.aslr_mpc_run.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), vp]
     lib.aslr_set_iteration_log.restype = C.c_int
     lib.aslr_set_iteration_log.argtypes = [vp, vp, i32]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
-    for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams)):
+    for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):
         if lib.aslr_sizeof(which) != C.sizeof(st):
             raise ImportError("aslr_to_amd: struct %s size mismatch (C %d, Python %d)"
                               % (st.__name__, lib.aslr_sizeof(which), C.sizeof(st)))

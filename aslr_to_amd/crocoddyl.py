@@ -387,6 +387,23 @@ class SolverDDP(object):
             self._replay_callbacks()
         return bool(((st & _abi.ST_CONVERGED) != 0).all().item())
 
+    def solve_mpc(self, n_steps, iters_per_step, init_xs=None, init_us=None, maxiter=100, isFeasible=False,
+                  disturbance=None, regInit=None):
+        """A receding-horizon run of n_steps control steps on the device (aslr_mpc_run): `solve(init_xs, init_us,
+        maxiter, isFeasible)` first, then per step -- apply us[0] to the plant (the first running model), add
+        disturbance[:, s] ([B, n_steps, nx], optional) to its next state, shift the plan one knot,
+        `solve(xs, us, iters_per_step, isFeasible)` -- the loop a script writes around solver.solve, without a host
+        round trip per step.  Callbacks are not replayed (the per-iteration log would be overwritten every step).
+        -> engine.MpcResult; solver.xs / us are the last shifted plan."""
+        e = self.problem.engine
+        sp = self._sp
+        sp.maxiter = int(maxiter)
+        sp.is_feasible = 1 if isFeasible else 0
+        sp.reg_init = float("nan") if regInit is None else float(regInit)
+        e.set_candidate(init_xs, init_us)
+        e.enable_iteration_log(0)
+        return e.mpc_run(sp, n_steps, sp.maxiter, iters_per_step, disturbance)
+
     def solve_pool(self, x0s, frame_refs=None, maxiter=100, isFeasible=False, regInit=None, refill_every=4,
                    poll_every=16, init_xs=None, init_us=None):
         """Solve MANY problems of this solver's structure (per-problem x0 and, optionally, frame-placement targets as

@@ -126,6 +126,74 @@ __global__ void __launch_bounds__(64) pool_refill_kernel(KArgs a, PoolDev pl, do
   }
 }
 
+// aslr_mpc_run: what lies between two solves of a receding-horizon run, for one trajectory per 64-thread block -- record the
+// step, take the plant's next state (XNEXT[0], evaluated by a one-knot calc launch just before) plus the disturbance, move
+// the plan one knot down, zero the gaps and gains as the refill above does for a fresh problem.
+struct MpcDev {
+  int32_t nx, nu;
+  const double *dist;           // [B][nx] of this step, or nullptr
+  double *x_rec, *u_rec;        // x_closed[s], u_closed[s]
+  double *x_last;               // x_closed[n_steps] in the last step, nullptr before
+  double *stat_f;               // [4][B] of this step
+  int32_t *stat_i;              // [2][B]
+};
+// rows [0, n) of trajectory b's column of a [rows][B][w] array take the row above them.  A lane owns entry e = t w + i of
+// the column (a wave reads 64 / w whole rows, each w consecutive doubles); kStage chunks of 64 entries are loaded before any
+// of them is stored, with a barrier in between: a store of this round overwrites only rows this round or an earlier one has
+// read (this round reads entries below e0 + 64 kStage + w, the next one reads from e0 + 64 kStage + w on)
+constexpr int kStage = 4;
+__device__ void shift_column(double *base, int n, int B, int b, int w, int tid) {
+  const int ne = n * w;
+  for (int e0 = 0; e0 < ne; e0 += 64 * kStage) { // (block-uniform trip count)
+    double v[kStage] = {};
+    ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
+      const int e = e0 + 64 * k + tid, t = e / w, i = e - t * w;
+      if (e < ne) v[k] = base[((size_t)(t + 1) * B + b) * w + i];
+    }
+    __syncthreads();
+    ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
+      const int e = e0 + 64 * k + tid, t = e / w, i = e - t * w;
+      if (e < ne) base[((size_t)t * B + b) * w + i] = v[k];
+    }
+  }
+}
+__device__ void zero_column(double *base, int n, int B, int b, int w, int tid) {
+  for (int e = tid; e < n * w; e += 64) {
+    const int t = e / w, i = e - t * w;
+    base[((size_t)t * B + b) * w + i] = 0.0;
+  }
+}
+__global__ void __launch_bounds__(64) mpc_advance_kernel(KArgs a, MpcDev m) {
+  const int b = blockIdx.x, tid = threadIdx.x, B = a.B, T = a.T, nx = m.nx, nu = m.nu;
+  const size_t bx = (size_t)b * nx, bu = (size_t)b * nu; // knot 0 of trajectory b
+  // ---- record; the plant's next state (no addition without a disturbance: x + 0 is not x for x = -0) ----
+  double xp = 0.0;
+  if (tid < nx) {
+    m.x_rec[bx + tid] = a.xs[bx + tid];
+    xp = a.xnext[bx + tid];
+    if (m.dist) xp += m.dist[bx + tid];
+  }
+  if (tid < nu) m.u_rec[bu + tid] = a.us[bu + tid];
+  if (tid < 4) {
+    const int row = tid == 0 ? ASLR_TF_COST : tid == 1 ? ASLR_TF_STOP : tid == 2 ? ASLR_TF_XREG : ASLR_TF_STEP;
+    m.stat_f[(size_t)tid * B + b] = a.traj_f[(size_t)row * B + b];
+  }
+  if (tid < 2) m.stat_i[(size_t)tid * B + b] = a.traj_i[(size_t)(tid == 0 ? ASLR_TI_ITER : ASLR_TI_STATUS) * B + b];
+  // ---- shift: xs[t] <- xs[t + 1] (t < T), us[t] <- us[t + 1] (t < T - 1); the last rows stay; then xs[0] <- x+ ----
+  shift_column(a.xs, T, B, b, nx, tid);
+  shift_column(a.us, T - 1, B, b, nu, tid);
+  __syncthreads(); // (knot 0 was written by the shift, possibly by other lanes)
+  if (tid < nx) {
+    a.xs[bx + tid] = xp;
+    const_cast<double *>(a.x0)[bx + tid] = xp;
+    if (m.x_last) m.x_last[bx + tid] = xp;
+  }
+  // ---- reset: the next solve starts from zeroed gaps and gains ----
+  zero_column(a.gaps, T + 1, B, b, nx, tid);
+  zero_column(a.vxxf, T + 1, B, b, nx, tid);
+  zero_column(a.kff, T, B, b, nu, tid);
+}
+
 } // namespace
 
 // =================================================================================================
@@ -162,6 +230,7 @@ struct aslr_problem {
   // model-only chunks of the DERIV records (cost-weight diagonals): const_ok = the cost stacks allow skipping them,
   // const_written = a sweep that evaluated every knot of every trajectory has put them in place (diff_mode)
   bool const_ok, const_written;
+  bool uniform_running; // every running knot uses one action model (aslr_mpc_run shifts the plan along the horizon)
 };
 
 namespace {
@@ -452,6 +521,7 @@ int64_t aslr_sizeof(int which) {
   case 5: return sizeof(aslr_region_t);
   case 6: return sizeof(aslr_pool_t);
   case 7: return sizeof(aslr_traj_params_t);
+  case 8: return sizeof(aslr_mpc_t);
   default: return -1;
   }
 }
@@ -514,6 +584,9 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   p->desc.node_model = nullptr; p->desc.x0 = nullptr; p->desc.frame_ref = nullptr;
   p->nj = nj; p->nx = nx; p->nu = nu; p->dam = dam; p->rec = rec_len_c(nx, nu);
   p->ks = ks;
+  p->uniform_running = true;
+  for (int t = 1; t < desc->T; ++t)
+    if (desc->node_model[t] != desc->node_model[0]) p->uniform_running = false;
   p->const_written = false;
   p->const_ok = true; // every cost type but the pendulum cost has a knot-independent diagonal Hessian outside Lqq
   for (int i = 0; i < desc->nmodels; ++i)
@@ -836,6 +909,37 @@ int aslr_solve(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t poll_e
   }
   if (iters_done) *iters_done = it;
   return aslr_finalize(p, stream);
+}
+
+int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, void *stream) {
+  auto fail = [&](const char *msg) { snprintf(g_err, sizeof g_err, "aslr_mpc_run: %s", msg); return ASLR_E_INVALID; };
+  if (!p || !sp || !mpc) return fail("NULL argument");
+  if (mpc->n_steps < 1 || mpc->first_maxiter < 1 || mpc->iters_per_step < 1) return fail("n_steps, first_maxiter and iters_per_step must be >= 1");
+  if (!mpc->x_closed || !mpc->u_closed || !mpc->stat_f || !mpc->stat_i) return fail("x_closed, u_closed, stat_f and stat_i must be given");
+  if (!p->uniform_running) return fail("the running knots use more than one action model: shifting the plan needs one (per-knot references are not supported)");
+  if (p->k.iter_log) return fail("an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)");
+  if (int rc = solver_unsupported(p, sp->solver)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t B = p->desc.B, nx = p->nx, nu = p->nu;
+  KArgs plant = p->k; // the plant: node 0's action model on knot 0 of every trajectory, through the handle's calc launcher
+  plant.seg_t1 = 0;
+  for (int s = 0; s < mpc->n_steps; ++s) {
+    // a solve as aslr_solve enqueues it when the host never polls
+    if (int rc = iterate(p, sp, true, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, st, IterOpts{p->k, 0, true, nullptr})) return rc;
+    if (int rc = aslr_finalize(p, stream)) return rc;
+    if (int rc = launch_calc(p, plant, false, 0, -1.0, st)) return rc;
+    MpcDev m;
+    m.nx = p->nx; m.nu = p->nu;
+    m.dist = mpc->disturbance ? mpc->disturbance + s * B * nx : nullptr;
+    m.x_rec = mpc->x_closed + s * B * nx;
+    m.u_rec = mpc->u_closed + s * B * nu;
+    m.x_last = s == mpc->n_steps - 1 ? mpc->x_closed + (s + 1) * B * nx : nullptr;
+    m.stat_f = mpc->stat_f + s * 4 * B;
+    m.stat_i = mpc->stat_i + s * 2 * B;
+    hipLaunchKernelGGL(mpc_advance_kernel, dim3(p->desc.B), dim3(64), 0, st, p->k, m);
+    HIP_TRY(hipGetLastError());
+  }
+  return ASLR_OK;
 }
 
 int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool, int32_t refill_every,

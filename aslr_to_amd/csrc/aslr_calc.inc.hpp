@@ -383,7 +383,8 @@ template <int NJ, int PHASE, bool TP> __global__ void dyn_team_kernel(KArgs a, i
 template <int NJ, int DAM, bool TP>
 int launch_calc(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream_t st) {
   using S = SizeTraits<NJ, DAM>;
-  const dim3 grid((k.b1 - k.b0 + 63) / 64, k.T + 1), block(64);
+  // knots [0, seg_t1]: the whole horizon unless the caller's block says otherwise (aslr_mpc_run evaluates knot 0 alone)
+  const dim3 grid((k.b1 - k.b0 + 63) / 64, k.seg_t1 + 1), block(64);
   with_planar<NJ>(k, [&](auto P) {
     constexpr bool PLANAR = decltype(P)::value, PRE = S::team_dyn;
     if (!diff) {
@@ -391,7 +392,7 @@ int launch_calc(const KArgs &k, bool diff, int mode, double th_gaptol, hipStream
       return;
     }
     if constexpr (PRE) { // rigid-body part by 8-lane teams (aslr_calc_team.inc.hpp), then products + costs + record per lane
-      const dim3 tgrid((k.b1 - k.b0 + 7) / 8, k.T + 1);
+      const dim3 tgrid((k.b1 - k.b0 + 7) / 8, k.seg_t1 + 1);
       hipLaunchKernelGGL((dyn_team_kernel<NJ, 0, TP>), tgrid, block, 0, st, k, mode);
       hipLaunchKernelGGL((dyn_team_kernel<NJ, 1, TP>), tgrid, block, 0, st, k, mode);
     }

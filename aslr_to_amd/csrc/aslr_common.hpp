@@ -45,7 +45,8 @@ struct KArgs {
   double *iter_log;  // per-iteration log [log_cap][ASLR_LOG_COUNT][B] (aslr_set_iteration_log), or nullptr
   int32_t log_cap;
   // knots [seg_t0, seg_t1] of the horizon this launch covers (kernels that can work on a part of it: the rollout carries
-  // its state over through the candidate it has stored; the trial costs are per knot): the whole horizon = [0, T]
+  // its state over through the candidate it has stored; the trial costs are per knot; the calc / calcDiff sweeps take
+  // knots [0, seg_t1], seg_t0 is not theirs): the whole horizon = [0, T]
   int32_t seg_t0, seg_t1;
   int32_t pipeline; // forward pass in two launches: the trial costs of the first half of the horizon run in the launch that rolls
                     // out the second half (rollout_and_cost_kernel; planar 2-joint chains).  0: off, 1 or 2: two segments (default), 3, 4: more (measured: no better)

@@ -18,6 +18,15 @@ def _torch():
     return torch
 
 
+class MpcResult(object):
+    """What Engine.mpc_run returns: batch-major device tensors, views of the time-major arrays the kernels wrote --
+    xs_closed [B, n+1, nx], us_closed [B, n, nu_user], and per step's solve iters, status (int32), cost, stop, x_reg,
+    step [B, n]."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class Engine(object):
     """ShootingProblem shard resident in HBM.  Region layouts: include/aslr_to_amd.h."""
 
@@ -335,6 +344,35 @@ class Engine(object):
         torch.cuda.synchronize(self.device)
         return dict(xs=xs, us=self.cut_u(us), cost=sf[:, 0], stop=sf[:, 1], x_reg=sf[:, 2], step=sf[:, 3], iters=si[:, 0],
                     status=si[:, 1], batch_iters=it.value)
+
+    def mpc_run(self, sp, n_steps, first_maxiter, iters_per_step, disturbance=None):
+        """A receding-horizon run on the device (aslr_mpc_run): step 0 solves first_maxiter iterations from the candidate
+        as it was set, every later step iters_per_step from the shifted plan; between two solves the first control is
+        applied to the plant (node 0's model, the trajectory's parameters), `disturbance` [B, n_steps, nx] (host or
+        device, optional) is added to its next state and the plan moves one knot down.  One ABI call, no host round
+        trip per step.  -> MpcResult; XS / US are left with the last shifted plan, X0 with the last plant state."""
+        torch = _torch()
+        n = int(n_steps)
+        with torch.cuda.device(self.device):
+            dist = None
+            if disturbance is not None:
+                d = torch.as_tensor(disturbance, dtype=torch.float64, device=self.device)
+                if tuple(d.shape) != (self.B, n, self.nx):
+                    raise ValueError("disturbance must have shape [B=%d, n_steps=%d, nx=%d]" % (self.B, n, self.nx))
+                dist = d.permute(1, 0, 2).contiguous()
+            m = max(n, 0)
+            xc = torch.zeros((m + 1, self.B, self.nx), dtype=torch.float64, device=self.device)
+            uc = torch.zeros((m, self.B, self.nu), dtype=torch.float64, device=self.device)
+            sf = torch.zeros((m, 4, self.B), dtype=torch.float64, device=self.device)
+            si = torch.zeros((m, 2, self.B), dtype=torch.int32, device=self.device)
+        mpc = _abi.Mpc()
+        mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, int(first_maxiter), int(iters_per_step)
+        mpc.disturbance = dist.data_ptr() if dist is not None else None
+        mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = xc.data_ptr(), uc.data_ptr(), sf.data_ptr(), si.data_ptr()
+        self._call("aslr_mpc_run", C.byref(sp), C.byref(mpc), self._stream())
+        torch.cuda.synchronize(self.device)  # (the time-major disturbance copy dies on return)
+        return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
+                         status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t())
 
     def traj_f(self, row):
         return self.region(_abi.R_TRAJ_F)[row]

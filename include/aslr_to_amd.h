@@ -34,12 +34,12 @@
 extern "C" {
 #endif
 
-#define ASLR_ABI_VERSION 3
+#define ASLR_ABI_VERSION 4
 
 #define ASLR_MAX_NJ     7   /* link-side DoF (2-DoF arm, 7-DoF arm)          */
 #define ASLR_MAX_NX     28  /* 4 * ASLR_MAX_NJ                                */
 #define ASLR_MAX_NU     14  /* 2 * ASLR_MAX_NJ (VSA)                          */
-/* Sizes the solver entry points (aslr_backward_pass, aslr_forward_pass, aslr_iterate*, aslr_solve, aslr_solve_pool)
+/* Sizes the solver entry points (aslr_backward_pass, aslr_forward_pass, aslr_iterate*, aslr_solve, aslr_solve_pool, aslr_mpc_run)
  * accept: nj = 2 (SEA / VSA / pendulum actuation) and nj = 7 with SEA, every solver; nj = 7 with VSA (nu = 14) with
  * ASLR_SOLVER_BOXDDP only -- the other solvers return ASLR_E_INVALID for it (model-level entry points and
  * aslr_quasi_static work for every combination). */
@@ -261,7 +261,7 @@ typedef struct aslr_problem aslr_problem_t; /* opaque */
 /* ---- ABI self-description (callable without a GPU) ------------------------------------ */
 int aslr_abi_version(void);
 /* sizeof() of the POD structs above as compiled, so a binding can check its mirror:
- * which = 0 chain, 1 cost, 2 model, 3 problem_desc, 4 solver_params, 5 region, 6 pool, 7 traj_params */
+ * which = 0 chain, 1 cost, 2 model, 3 problem_desc, 4 solver_params, 5 region, 6 pool, 7 traj_params, 8 mpc */
 int64_t aslr_sizeof(int which);
 /* record length in doubles (padded) for given nx, nu */
 int32_t aslr_record_len(int32_t nx, int32_t nu);
@@ -366,6 +366,37 @@ typedef struct aslr_pool {
  * counter every `poll_every` iterations (one 4-byte D2H). */
 int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool, int32_t refill_every,
                     int32_t poll_every, void *stream, int32_t *iters_done);
+
+/* A receding-horizon (MPC) run that stays on the device: solve a few iterations, apply the first control, let the plant
+ * move, shift the plan by one knot, solve again -- the closed loop a script writes around `solver.solve(xs, us, n)`
+ * (examples/two_dof_vsa_boxddp.py:81) -- n_steps times without a host round trip.  Step s:
+ *   1. the iterations aslr_solve enqueues when the host never polls (first_maxiter of them at s = 0, from the candidate
+ *      XS / US hold on entry; iters_per_step later), then aslr_finalize.  Every step starts like a solve: regularisation
+ *      at sp->reg_init, feasibility sp->is_feasible; trajectories that stop early idle.  sp->maxiter is not read.
+ *   2. record: x_closed[s] = xs[0], u_closed[s] = us[0], the solve's statistics;
+ *      plant:  x+ = xnext(xs[0], us[0]) + disturbance[s] with node 0's action model and the trajectory's parameters
+ *              (aslr_set_trajectory_params): bit for bit XNEXT[0] of an aslr_calc on the finalized trajectory;
+ *      shift:  xs[t] <- xs[t+1] (t < T; xs[T] stays), us[t] <- us[t+1] (t < T-1; us[T-1] stays), xs[0] <- x+, X0 <- x+;
+ *      reset:  GAPS, VXXF, KFF of the trajectory to zero (as a fresh problem has them).
+ * After the last step x_closed[n_steps] = x+; XS / US hold the shifted plan and X0 the last plant state (the handle's
+ * x0 is NOT restored: the loop has moved it).  XNEXT[0] / COST[0] hold the last plant evaluation.
+ * DEVICE pointers owned by the caller, time-major like the workspace.  Everything is enqueued on `stream`; the host
+ * never waits inside the call.  Sub-shards (aslr_set_subshards) apply to the iterations of a step.
+ * ASLR_E_INVALID (aslr_last_error): NULL or non-positive arguments; running knots that do not all use one action model
+ * (the terminal model may differ: a receding horizon over a time-varying stack needs per-knot references); an iteration
+ * log that is set (every step would overwrite it); the solver / size combinations the solver entry points decline. */
+typedef struct aslr_mpc {
+  int32_t n_steps;            /* control steps, >= 1                                                            */
+  int32_t first_maxiter;      /* iterations of step 0, >= 1                                                     */
+  int32_t iters_per_step;     /* iterations of steps 1 and later, >= 1                                          */
+  int32_t _pad0;
+  const double *disturbance;  /* [n_steps][B][nx] added to the plant's next state, or NULL                      */
+  double *x_closed;           /* [n_steps+1][B][nx] closed-loop states                                          */
+  double *u_closed;           /* [n_steps][B][nu] applied controls                                              */
+  double *stat_f;             /* [n_steps][4][B]: cost, stop, x_reg, last step length of each step's solve      */
+  int32_t *stat_i;            /* [n_steps][2][B]: iterations, ASLR_ST_* status word                             */
+} aslr_mpc_t;
+int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, void *stream);
 
 /* one lock-step DDP iteration (calcDiff sweep + backward pass + line search), the unit the
  * benchmark's "step" times.  `first` != 0 re-initialises the per-trajectory solver state. */
