@@ -8,86 +8,26 @@ import pytest
 
 from aslr_to_amd import _abi, scenarios
 
-import _geometry_chains as gc
+import _geometry_chains as chains
+import _gpu_case as gc
 import _parity
-from _forward_case import (forward_inputs as _forward_inputs, random_candidate as _random_candidate,
-                           run_forward as _run_forward)
 
 pytestmark = pytest.mark.gpu
 
 TAYLOR = 2.0 ** -13
 
 
-def _engine(low):
-    from aslr_to_amd.engine import Engine
-    return Engine(low)
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _relerr(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return np.max(np.abs(a - b) / (1.0 + np.abs(b))) if a.size else 0.0
-
-
-def _bits(t):
-    import torch
-    return t.view(torch.int64) if t.dtype == torch.float64 else t
-
-
-def _check_calc_and_calc_diff(oracle, low, seed=1):
-    """Both sweeps of test_gpu_parity.test_calc_and_calcdiff_match_oracle: calcDiff, calc alone, and calcDiff at a second
-    point (the variant that skips the record chunks the first sweep already holds)."""
-    import torch
-    e = _engine(low)
-    for k, s in enumerate((seed, seed + 4)):
-        xs, us = _random_candidate(low, s)
-        e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-        e.region(_abi.R_US).copy_(torch.as_tensor(us))
-        e.calc_diff()
-        _sync()
-        xnext, cost, deriv = oracle.calc_diff(low, xs, us)
-        assert _relerr(_np(e.region(_abi.R_XNEXT)), xnext) < 1e-11
-        assert _relerr(_np(e.region(_abi.R_COST)), cost) < 1e-11
-        err = _relerr(_np(e.region(_abi.R_DERIV)), deriv)
-        assert err < 1e-9, "DERIV record mismatch %g (sweep %d)" % (err, k)
-        if k == 0:
-            e.region(_abi.R_XNEXT).zero_()
-            e.region(_abi.R_COST).zero_()
-            e.calc()
-            _sync()
-            assert _relerr(_np(e.region(_abi.R_XNEXT)), xnext) < 1e-11
-            assert _relerr(_np(e.region(_abi.R_COST)), cost) < 1e-11
-    return e
-
-
 def _check_forward(oracle, low, solver, seed=5):
     """Rollout + trial costs of every step length against the oracle (FDDP: infeasible start, the gaps are closed by
     the rollout)."""
-    sp = _abi.default_solver_params({"SolverDDP": _abi.SOLVER_DDP, "SolverFDDP": _abi.SOLVER_FDDP,
-                                     "SolverBoxDDP": _abi.SOLVER_BOXDDP}[solver])
+    sp = _abi.default_solver_params(gc.SOLVERS[solver])
     fddp = solver == "SolverFDDP"
-    xs, us, K, k, gaps = _forward_inputs(oracle, low, sp, seed, fddp)
+    xs, us, K, k, gaps = gc.forward_inputs(oracle, low, sp, seed, fddp)
     feasible = 0 if fddp else 1
-    e = _run_forward(low, sp, xs, us, K, k, gaps, feasible)
-    XT, UT = _np(e.region(_abi.R_XS_TRY)), _np(e.region(_abi.R_US_TRY))
-    for a in range(_abi.NALPHA):
-        xs_try, us_try, cost_try, fail = oracle.forward_pass(low, sp, 0.5 ** a, xs, us, K, k,
-                                                             gaps if fddp else None, feasible if fddp else None)
-        ok = fail == 0
-        assert ok.mean() > 0.5
-        assert _relerr(XT[a][:, ok], xs_try[:, ok]) < 1e-9
-        assert _relerr(UT[a][:, ok], us_try[:, ok]) < 1e-9
-        got = _np(e.traj_f(_abi.TF_COST_TRY0 + a))
-        assert _relerr(got[ok], cost_try[ok]) < 1e-9
-        assert np.isnan(got[~ok]).all()
+    e = gc.run_forward(low, sp, xs, us, K, k, gaps, feasible)
+    oks, _ = gc.assert_forward_matches(*gc.forward_outputs(e), lambda alpha: oracle.forward_pass(
+        low, sp, alpha, xs, us, K, k, gaps if fddp else None, feasible if fddp else None))
+    assert all(ok.mean() > 0.5 for ok in oks)
     return e
 
 
@@ -96,12 +36,12 @@ def _check_forward(oracle, low, solver, seed=5):
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B", [70, 130])
 @pytest.mark.parametrize("actuator", ["sea", "vsa"])
-@pytest.mark.parametrize("chain", gc.CHAINS)
+@pytest.mark.parametrize("chain", chains.CHAINS)
 def test_calc_and_calcdiff_on_non_planar_two_joint_chains(oracle, chain, actuator, B):
     """calc_kernel<2, SEA / VSA, *, false, ...> (the planar detector declines all three chains) at batches that leave a
     partial wave, T = 5, both sweeps."""
-    low = scenarios.lower(gc.problem(chain, actuator, B=B, T=5, seed=B))
-    _check_calc_and_calc_diff(oracle, low)
+    low = scenarios.lower(chains.problem(chain, actuator, B=B, T=5, seed=B))
+    gc.check_calc_and_calc_diff(oracle, low)
 
 
 @pytest.mark.parametrize("actuator", ["sea", "vsa"])
@@ -109,13 +49,13 @@ def test_model_level_entry_points_on_the_general_chain(oracle, actuator):
     """dam_eval, dam_residuals, frame_placement (every frame, the welded end effector with its rotated origin included)
     and quasi_static through the general path, running and terminal models, against the oracle point by point."""
     import torch
-    sc = gc.problem("general", actuator, B=70, T=3, seed=2)
-    sc["frame_refs"][0, :9] = gc.random_rotation(np.random.default_rng(3)).reshape(9)
+    sc = chains.problem("general", actuator, B=70, T=3, seed=2)
+    sc["frame_refs"][0, :9] = chains.random_rotation(np.random.default_rng(3)).reshape(9)
     low = scenarios.lower(sc)
     fref = low.frame_ref[0]       # (the point evaluators take trajectory 0's reference for every point)
-    e = _engine(low)
+    e = gc.engine(low)
     n = 70
-    xs, us = _random_candidate(low, 9)
+    xs, us = gc.random_candidate(low, 9)
     x, u = xs[0], us[0]
     for mi in range(low.desc.nmodels):
         got = e.dam_eval(mi, x, u)
@@ -123,15 +63,15 @@ def test_model_level_entry_points_on_the_general_chain(oracle, actuator):
         for b in range(n):
             ref = oracle.dam(low, mi, x[b], u[b], frame_ref=fref)
             for key in ("xout", "cost"):
-                assert _relerr(got[key][b], ref[key]) < 1e-11, (mi, b, key)
+                assert gc.relerr(got[key][b], ref[key]) < 1e-11, (mi, b, key)
             for key in ("Fx", "Fu", "Lx", "Lu", "Lxx", "Lxu", "Luu"):
-                assert _relerr(got[key][b], ref[key]) < 1e-9, (mi, b, key)
-            assert _relerr(res[b], oracle.dam_residuals(low, mi, x[b], u[b], frame_ref=fref)) < 1e-11, (mi, b)
+                assert gc.relerr(got[key][b], ref[key]) < 1e-9, (mi, b, key)
+            assert gc.relerr(res[b], oracle.dam_residuals(low, mi, x[b], u[b], frame_ref=fref)) < 1e-11, (mi, b)
     model = sc["terminal"].state.pinocchio
     xd = torch.as_tensor(x, device=e.device)
     for fr in model.frames[1:]:
         R, p = e.frame_placement(fr.parent, fr.placement.rotation, fr.placement.translation, xd)
-        R, p = _np(R), _np(p)
+        R, p = gc.to_np(R), gc.to_np(p)
         for b in range(n):
             Rr, pr = oracle.frame_placement(low.desc.chain, x[b, :2], fr.parent, fr.placement.rotation,
                                             fr.placement.translation)
@@ -140,9 +80,9 @@ def test_model_level_entry_points_on_the_general_chain(oracle, actuator):
     # quasi-static controls of the states in XS (Gauss-Newton on the Euler step), knot by knot
     xs[..., 4:] *= 0.25
     e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-    iters = _np(e.quasi_static())
-    _sync()
-    U = _np(e.region(_abi.R_US))
+    iters = gc.to_np(e.quasi_static())
+    gc.sync()
+    U = gc.to_np(e.region(_abi.R_US))
     assert (iters >= 0).all()
     for t in range(low.T):
         for b in range(0, n, 7):
@@ -155,7 +95,7 @@ def test_model_level_entry_points_on_the_general_chain(oracle, actuator):
 @pytest.mark.parametrize("actuator", ["sea", "vsa"])
 def test_forward_pass_on_the_general_chain_for_every_alpha(oracle, actuator, solver):
     """rollout_kernel<2, *, false, *> and trial_cost_kernel<2, *, false, false>: the non-planar forward pass."""
-    low = scenarios.lower(gc.problem("general", actuator, B=70, T=20, seed=4))
+    low = scenarios.lower(chains.problem("general", actuator, B=70, T=20, seed=4))
     _check_forward(oracle, low, solver)
 
 
@@ -163,22 +103,19 @@ def test_forward_pass_on_the_general_chain_for_every_alpha(oracle, actuator, sol
 def test_short_solves_on_the_general_chain(oracle, actuator, solver):
     """Full solves, B = 16, T = 40, through every kernel of the general path: the oracle's iteration counts exactly,
     decision bits of the status words exactly, xs / us within 1e-6 of the size of the iterates."""
-    sc = gc.problem("general", actuator, B=16, T=40, seed=3)
+    sc = chains.problem("general", actuator, B=16, T=40, seed=3)
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc, solver=solver)
     ref = oracle.solve(low, sp, nthreads=8)
-    e = _engine(low)
-    e.set_candidate(None, None)
-    e.solve(sp, poll_every=4)
-    _sync()
+    _, g = gc.solve_gpu(low, sp, poll_every=4)
     st_r = ref["traj_i"][_abi.TI_STATUS]
     assert ((st_r & _abi.ST_CONVERGED) != 0).all()
-    np.testing.assert_array_equal(_np(e.traj_i(_abi.TI_ITER)), ref["traj_i"][_abi.TI_ITER])
-    _parity.assert_status_words_match(_np(e.traj_i(_abi.TI_STATUS)), st_r)
+    np.testing.assert_array_equal(g["traj_i"][_abi.TI_ITER], ref["traj_i"][_abi.TI_ITER])
+    _parity.assert_status_words_match(g["traj_i"][_abi.TI_STATUS], st_r)
     scale = np.maximum(1.0, np.maximum(np.abs(ref["xs"]).max(axis=(0, 2)), np.abs(ref["us"]).max(axis=(0, 2))))
-    dx = np.abs(_np(e.region(_abi.R_XS)) - ref["xs"]).max(axis=(0, 2)) / scale
-    du = np.abs(_np(e.region(_abi.R_US)) - ref["us"]).max(axis=(0, 2)) / scale
-    dc = np.abs(_np(e.traj_f(_abi.TF_COST)) - ref["traj_f"][_abi.TF_COST])
+    dx = np.abs(g["xs"] - ref["xs"]).max(axis=(0, 2)) / scale
+    du = np.abs(g["us"] - ref["us"]).max(axis=(0, 2)) / scale
+    dc = np.abs(g["traj_f"][_abi.TF_COST] - ref["traj_f"][_abi.TF_COST])
     print("general %s %s: iterations %s, max rel |dx| %.2e |du| %.2e, |dcost| %.2e"
           % (actuator, solver, ref["traj_i"][_abi.TI_ITER], dx.max(), du.max(), dc.max()))
     assert dx.max() < 1e-6 and du.max() < 1e-6
@@ -202,13 +139,13 @@ def _rotated_refs(oracle, low, sc, xs, seed):
     B, T = low.B, low.T
     refs = np.zeros((B, 12))
     for b in range(B):
-        refs[b, :9] = gc.random_rotation(rng).reshape(9)
+        refs[b, :9] = chains.random_rotation(rng).reshape(9)
         refs[b, 9:] = sc["frame_refs"][b, 9:] + rng.uniform(-0.05, 0.05, 3)
     model = sc["terminal"].state.pinocchio
     fr = model.frames[model.getFrameId("EE")]
     for b, angle in enumerate(BAND_ANGLES):
         R, p = oracle.frame_placement(low.desc.chain, xs[T, b, :2], fr.parent, fr.placement.rotation, fr.placement.translation)
-        dR, dp = gc.random_rotation(rng, angle), rng.uniform(-0.05, 0.05, 3)
+        dR, dp = chains.random_rotation(rng, angle), rng.uniform(-0.05, 0.05, 3)
         # Mref = oMf * (dR, dp)^-1  =>  rMf = (dR, dp)
         refs[b, :9] = R.dot(dR.T).reshape(9)
         refs[b, 9:] = p - R.dot(dR.T).dot(dp)
@@ -226,13 +163,12 @@ def test_calc_and_calcdiff_with_rotated_references_in_every_log_band(oracle, cha
     """frame_refs with random rotations, and references that put the terminal residual's rotation in each band of the
     log (checked on the oracle's log6 of rMf); on the planar arm of C2 / C3 and on the general chain, whose cost frame is
     itself rotated on its joint.  Both sweeps against the oracle."""
-    import torch
     if chain == "planar":
         sc = scenarios.SCENARIOS["two_dof_sea" if actuator == "sea" else "two_dof_vsa_boxddp"](B=70, T=5, seed=3)
     else:
-        sc = gc.problem(chain, actuator, B=70, T=5, seed=3)
+        sc = chains.problem(chain, actuator, B=70, T=5, seed=3)
     low0 = scenarios.lower(sc)
-    xs, us = _random_candidate(low0, 1)
+    xs, us = gc.random_candidate(low0, 1)
     refs = _rotated_refs(oracle, low0, sc, xs, seed=6)
     low = scenarios.lower(_with_refs(sc, refs))
     # the residual rotation of knot T really lies in each band
@@ -244,23 +180,10 @@ def test_calc_and_calcdiff_with_rotated_references_in_every_log_band(oracle, cha
         Rr = refs[b, :9].reshape(3, 3)
         th = np.linalg.norm(oracle.log6(Rr.T.dot(R), Rr.T.dot(p - refs[b, 9:]))[3:])
         assert abs(th - angle) < 1e-6 * max(angle, 1e-3), (b, th, angle)
-    e = _engine(low)
-    e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-    e.region(_abi.R_US).copy_(torch.as_tensor(us))
-    e.calc_diff()
-    _sync()
-    xnext, cost, deriv = oracle.calc_diff(low, xs, us)
-    assert _relerr(_np(e.region(_abi.R_XNEXT)), xnext) < 1e-11
-    got = _np(e.region(_abi.R_COST))
-    err = np.abs(got - cost) / (1.0 + np.abs(cost))
-    assert err.max() < 1e-11, "cost mismatch %g at (t, b) %s" % (err.max(), np.unravel_index(err.argmax(), err.shape))
-    gd = _np(e.region(_abi.R_DERIV))
-    err = (np.abs(gd - deriv) / (1.0 + np.abs(deriv))).max(axis=2)
-    assert err.max() < 1e-9, "DERIV mismatch %g at (t, b) %s" % (err.max(), np.unravel_index(err.argmax(), err.shape))
-    e.region(_abi.R_COST).zero_()
-    e.calc()
-    _sync()
-    assert _relerr(_np(e.region(_abi.R_COST)), cost) < 1e-11
+    e = gc.engine(low)
+    ref = oracle.calc_diff(low, xs, us)
+    gc.assert_records_match(*gc.run_calc_diff(e, xs, us), ref=ref)   # (a mismatch is reported with its (t, b))
+    gc.assert_records_match(None, gc.run_calc(e)[1], None, ref=ref)
 
 
 def test_residual_rotation_of_exactly_pi_gives_the_oracles_cost(oracle):
@@ -272,9 +195,9 @@ def test_residual_rotation_of_exactly_pi_gives_the_oracles_cost(oracle):
     not logs of R -- tests/test_oracle_geometry.py shows the tie.)  Compared to 1e-7 relative: theta = acos((tr - 1) / 2)
     at a trace within a few eps of -1 is pi to ~sqrt(eps), and so are the square roots of the near-zero diagonal terms."""
     import torch
-    sc = gc.problem("general", "sea", B=70, T=2, seed=8)
+    sc = chains.problem("general", "sea", B=70, T=2, seed=8)
     low0 = scenarios.lower(sc)
-    xs, us = _random_candidate(low0, 2)
+    xs, us = gc.random_candidate(low0, 2)
     rng = np.random.default_rng(12)
     model = sc["terminal"].state.pinocchio
     fr = model.frames[model.getFrameId("EE")]
@@ -287,13 +210,13 @@ def test_residual_rotation_of_exactly_pi_gives_the_oracles_cost(oracle):
         refs[b, :9] = R.dot(dR).reshape(9)
         refs[b, 9:] = p + rng.uniform(-0.05, 0.05, 3)
     low = scenarios.lower(_with_refs(sc, refs))
-    e = _engine(low)
+    e = gc.engine(low)
     e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
     e.region(_abi.R_US).copy_(torch.as_tensor(us))
     e.calc()
-    _sync()
+    gc.sync()
     _, cost, _ = oracle.calc_diff(low, xs, us, diff=False)
-    got = _np(e.region(_abi.R_COST))[low.T]
+    got = gc.to_np(e.region(_abi.R_COST))[low.T]
     err = np.abs(got - cost[low.T]) / np.abs(cost[low.T])
     assert err.max() < 1e-7, "cost at a half turn: %.3e relative (trajectory %d)" % (err.max(), err.argmax())
 
@@ -303,33 +226,29 @@ def test_closed_form_reach_switch_falls_back_with_rotated_references(oracle, mon
     """ASLR_PLANAR_REACH=1 asks for the closed-form planar reach residual, which needs identity reference rotations:
     with rotated frame_refs fill_planar_reach declines, so calc / calcDiff and the forward pass give the same bits as
     with the switch off (and match the oracle)."""
-    import torch
     sc = scenarios.SCENARIOS["two_dof_sea" if actuator == "sea" else "two_dof_vsa_boxddp"](B=70, T=20, seed=5)
     low0 = scenarios.lower(sc)
-    xs, _ = _random_candidate(low0, 5)      # the candidate _forward_inputs draws below
+    xs, _ = gc.random_candidate(low0, 5)      # the candidate gc.forward_inputs draws below
     low = scenarios.lower(_with_refs(sc, _rotated_refs(oracle, low0, sc, xs, seed=9)))
     sp = scenarios.solver_params(sc)
-    xs, us, K, k, gaps = _forward_inputs(oracle, low, sp, 5, False)
+    xs, us, K, k, gaps = gc.forward_inputs(oracle, low, sp, 5, False)
     out = {}
     for flag in ("0", "1"):
         monkeypatch.setenv("ASLR_PLANAR_REACH", flag)   # (read when the handle is created)
-        e = _run_forward(low, sp, xs, us, K, k, gaps, 1)
+        e = gc.run_forward(low, sp, xs, us, K, k, gaps, 1)
         fwd = [e.region(r).clone() for r in (_abi.R_XS_TRY, _abi.R_US_TRY, _abi.R_TRAJ_F)]
-        e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-        e.region(_abi.R_US).copy_(torch.as_tensor(us))
-        e.calc_diff()
-        _sync()
+        gc.run_calc_diff(e, xs, us)
         out[flag] = fwd + [e.region(r).clone() for r in (_abi.R_XNEXT, _abi.R_COST, _abi.R_DERIV)]
     for a, b in zip(out["0"], out["1"]):
-        assert torch.equal(_bits(a), _bits(b))
+        gc.same_bits(a, b, "ASLR_PLANAR_REACH / ASLR_NO_PLANAR = 0 and = 1")
     _, cost, deriv = oracle.calc_diff(low, xs, us)
-    assert _relerr(_np(out["1"][4]), cost) < 1e-11
-    assert _relerr(_np(out["1"][5]), deriv) < 1e-9
+    assert gc.relerr(gc.to_np(out["1"][4]), cost) < 1e-11
+    assert gc.relerr(gc.to_np(out["1"][5]), deriv) < 1e-9
     for a in range(_abi.NALPHA):
         _, _, cost_try, fail = oracle.forward_pass(low, sp, 0.5 ** a, xs, us, K, k)
-        got = _np(out["1"][2][_abi.TF_COST_TRY0 + a])
+        got = gc.to_np(out["1"][2][_abi.TF_COST_TRY0 + a])
         ok = fail == 0
-        assert ok.mean() > 0.5 and _relerr(got[ok], cost_try[ok]) < 1e-9
+        assert ok.mean() > 0.5 and gc.relerr(got[ok], cost_try[ok]) < 1e-9
 
 
 # ---------------------------------------------------------------------------------------------
@@ -342,7 +261,7 @@ def test_general_path_on_the_planar_scenarios_matches_oracle(oracle, monkeypatch
     monkeypatch.setenv("ASLR_NO_PLANAR", "1")
     sc = scenarios.SCENARIOS[name](B=70, T=20, seed=1)
     low = scenarios.lower(sc)
-    _check_calc_and_calc_diff(oracle, low)
+    gc.check_calc_and_calc_diff(oracle, low)
     _check_forward(oracle, low, "SolverDDP")
 
 
@@ -352,10 +271,10 @@ def test_planar_switch_changes_nothing_where_the_detector_declines(monkeypatch, 
     """On the flipped (axes -z) and tilted (1e-3 rad) arms the planar detector declines, so ASLR_NO_PLANAR=0 and =1 run
     the same kernels: calc / calcDiff and forward-pass outputs must be the same bits."""
     import torch
-    sc = gc.problem(chain, actuator, B=70, T=20, seed=7)
+    sc = chains.problem(chain, actuator, B=70, T=20, seed=7)
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc, solver="SolverFDDP")
-    xs, us = _random_candidate(low, 4)
+    xs, us = gc.random_candidate(low, 4)
     rng = np.random.default_rng(4)
     K = rng.uniform(-0.05, 0.05, (low.T, low.B, low.nu, low.nx))
     k = rng.uniform(-0.05, 0.05, (low.T, low.B, low.nu))
@@ -363,13 +282,10 @@ def test_planar_switch_changes_nothing_where_the_detector_declines(monkeypatch, 
     out = {}
     for flag in ("0", "1"):
         monkeypatch.setenv("ASLR_NO_PLANAR", flag)
-        e = _run_forward(low, sp, xs, us, K, k, gaps, 0)
+        e = gc.run_forward(low, sp, xs, us, K, k, gaps, 0)
         res = [e.region(r).clone() for r in (_abi.R_XS_TRY, _abi.R_US_TRY, _abi.R_TRAJ_F)]
-        e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-        e.region(_abi.R_US).copy_(torch.as_tensor(us))
-        e.calc_diff()
-        _sync()
+        gc.run_calc_diff(e, xs, us)
         out[flag] = res + [e.region(r).clone() for r in (_abi.R_XNEXT, _abi.R_COST, _abi.R_DERIV)]
     assert torch.isfinite(out["0"][4]).all()
     for a, b in zip(out["0"], out["1"]):
-        assert torch.equal(_bits(a), _bits(b))
+        gc.same_bits(a, b, "ASLR_PLANAR_REACH / ASLR_NO_PLANAR = 0 and = 1")

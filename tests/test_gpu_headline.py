@@ -20,6 +20,7 @@ import pytest
 
 from aslr_to_amd import _abi, scenarios
 
+import _gpu_case as gc
 import _parity
 
 pytestmark = pytest.mark.gpu
@@ -60,22 +61,13 @@ def classify(row, sp):
 
 
 def test_headline_batch_full_solves_match_the_oracle_trajectory_by_trajectory(oracle):
-    import torch
-    from aslr_to_amd.engine import Engine
     B = 4096
     sc = scenarios.two_dof_vsa_boxddp(B=B, T=100, seed=0)
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc)
     nth = min(16, len(os.sched_getaffinity(0)))
     ref = oracle.solve(low, sp, nthreads=nth, log_cap=sp.maxiter)
-    e = Engine(low)
-    e.set_candidate(None, None)
-    e.enable_iteration_log(sp.maxiter)
-    e.solve(sp, poll_every=4)
-    torch.cuda.synchronize()
-    gpu = dict(xs=e.region(_abi.R_XS).cpu().numpy(), us=e.region(_abi.R_US).cpu().numpy(),
-               traj_f=e.region(_abi.R_TRAJ_F).cpu().numpy(), traj_i=e.region(_abi.R_TRAJ_I).cpu().numpy(),
-               log=e.iteration_log().cpu().numpy())
+    _, gpu = gc.solve_gpu(low, sp, log_cap=sp.maxiter)
     r = _parity.compare(gpu, ref, sp)
     kinds = [classify(row, sp) for row in r["exceptions"]]
     text = "\n".join("[%s] %s" % (k, _parity.describe(row, sp)) for k, row in zip(kinds, r["exceptions"]))

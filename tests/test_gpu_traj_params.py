@@ -10,6 +10,7 @@ the scenario's constants, log-uniform per trajectory and joint; VSA stiffness fl
 import numpy as np
 import pytest
 
+import _gpu_case as gc
 import _parity
 import _traj_oracle
 from aslr_to_amd import _abi, crocoddyl, scenarios
@@ -18,25 +19,6 @@ pytestmark = pytest.mark.gpu
 
 # trajectories allowed to part from the oracle in iteration count, by test batch, with the cause (cap: one per 64)
 TIE_FLIPS = {"two_dof_sea": {}, "two_dof_vsa_boxddp": {}, "talos_arm_sea": {}}
-
-
-def _engine(low):
-    from aslr_to_amd.engine import Engine
-    return Engine(low)
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _np(t):
-    return t.detach().cpu().numpy().copy()
-
-
-def _relerr(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return np.max(np.abs(a - b) / (1.0 + np.abs(b))) if a.size else 0.0
 
 
 def _scenario(name, B, T, seed=4, floors=None):
@@ -48,11 +30,7 @@ def _scenario(name, B, T, seed=4, floors=None):
 
 
 def _inputs(low, seed):
-    rng = np.random.default_rng(seed)
-    xs = rng.uniform(-0.8, 0.8, (low.T + 1, low.B, low.nx))
-    us = rng.uniform(-1.0, 1.0, (low.T, low.B, low.nu))
-    if low.dam == _abi.DAM_VSA:
-        us[..., low.nj:] = rng.uniform(0.1, 5.0, (low.T, low.B, low.nj))
+    xs, us = gc.random_candidate(low, seed)
     tp = low.traj_params
     if "u_lb" in tp:
         us = np.clip(us, tp["u_lb"][None], tp["u_ub"][None])
@@ -64,49 +42,17 @@ SIZES = ["sea2", "vsa2", "sea7", "vsa7"]
 
 @pytest.mark.parametrize("name", SIZES)
 def test_calc_diff_records_match_the_per_trajectory_oracle(oracle, name):
-    import torch
     low = scenarios.lower(_scenario(name, B=5, T=6))
     xs, us = _inputs(low, 3)
-    xn_r, c_r, d_r = _traj_oracle.calc_diff(oracle, low, xs, us)
-    e = _engine(low)
-    e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-    e.region(_abi.R_US).copy_(torch.as_tensor(us))
+    ref = _traj_oracle.calc_diff(oracle, low, xs, us)
+    e = gc.engine(low)
     for sweep in range(2):  # (the second sweep skips the model-only chunks where the size has that variant)
-        e.calc_diff()
-        _sync()
-        for what, got, ref in (("xnext", e.region(_abi.R_XNEXT), xn_r), ("cost", e.region(_abi.R_COST), c_r),
-                               ("deriv", e.region(_abi.R_DERIV), d_r)):
-            err = _relerr(_np(got), ref)
-            print("%s sweep %d %s relerr %.2e" % (name, sweep, what, err))
-            assert err < 1e-9, (what, err)
+        gc.assert_records_match(*gc.run_calc_diff(e, xs, us), ref=ref, tol_state=1e-9)
     # ... and the table is what made the difference: the plain handle's records are elsewhere
     plain = dict(_scenario(name, B=5, T=6))
     plain["traj_params"] = None
-    e0 = _engine(scenarios.lower(plain))
-    e0.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-    e0.region(_abi.R_US).copy_(torch.as_tensor(us))
-    e0.calc_diff()
-    _sync()
-    assert _relerr(_np(e0.region(_abi.R_XNEXT)), xn_r) > 1e-6
-
-
-def _backward(e, sp, us, deriv, gaps, k0, xreg, feasible):
-    import torch
-    e.region(_abi.R_US).copy_(torch.as_tensor(us))
-    e.region(_abi.R_DERIV).copy_(torch.as_tensor(deriv))
-    e.region(_abi.R_GAPS).copy_(torch.as_tensor(gaps))
-    e.region(_abi.R_KFF).copy_(torch.as_tensor(k0))
-    e.region(_abi.R_TRAJ_F)[_abi.TF_XREG].fill_(xreg)
-    e.region(_abi.R_TRAJ_I)[_abi.TI_FEASIBLE].fill_(feasible)
-    e.region(_abi.R_TRAJ_I)[_abi.TI_STATUS].fill_(0)
-    e.backward_pass(sp)
-    _sync()
-    out = dict(K=_np(e.region(_abi.R_KGAIN)), k=_np(e.region(_abi.R_KFF)), Qu=_np(e.region(_abi.R_QU)),
-               Vx=_np(e.region(_abi.R_VX)), Vxx=_np(e.region(_abi.R_VXX)))
-    for fld, nm in ((_abi.TF_D1, "d1"), (_abi.TF_D2, "d2"), (_abi.TF_STOP, "stop")):
-        out[nm] = _np(e.traj_f(fld))
-    out["status"] = _np(e.traj_i(_abi.TI_STATUS))
-    return out
+    xnext0 = gc.run_calc_diff(gc.engine(scenarios.lower(plain)), xs, us)[0]
+    assert gc.relerr(xnext0, ref[0]) > 1e-6
 
 
 def _tight_box(sc, B, nu, seed):
@@ -150,22 +96,16 @@ def test_backward_pass_reads_the_per_trajectory_box(oracle, monkeypatch, name, e
     gaps = np.zeros((T + 1, B, low.nx))
     k0 = np.random.default_rng(6).uniform(-0.5, 0.5, us.shape)
     ref = _traj_oracle.backward_pass(oracle, low, sp, deriv, gaps, us, 1e-3, 1, k0)
-    assert not ref["fail"].any()
     clamped = (ref["Qu"] == 0.0).mean()
     print("clamped share of Qu: %.3f" % clamped)
     assert 0.02 < clamped < 0.98, clamped
-    out = _backward(_engine(low), sp, us, deriv, gaps, k0, 1e-3, 1)
-    assert (out["status"] & _abi.ST_BACKWARD_ERR == 0).all()
-    for nm in ("K", "k", "Qu", "Vx", "Vxx", "d1", "d2", "stop"):
-        err = _relerr(out[nm], ref[nm])
-        print("%s %s=%s %s relerr %.2e" % (name, env[0], env[1], nm, err))
-        assert err < tol, (nm, err)
+    out = gc.run_backward(gc.engine(low), sp, us, deriv, gaps, 1e-3, 1, k0=k0)
+    gc.assert_backward_matches(out, ref, tol)
     np.testing.assert_array_equal(out["Qu"] == 0.0, ref["Qu"] == 0.0)
 
 
 @pytest.mark.parametrize("name", SIZES)
 def test_forward_pass_candidates_match_the_per_trajectory_oracle(oracle, name):
-    import torch
     B, T = 5, 6
     sc = _scenario(name, B=B, T=T)
     sc = _tight_box(sc, B, scenarios.lower(sc).nu, 9)  # (SEA included: boxed models, a per-trajectory box, BoxDDP)
@@ -176,35 +116,9 @@ def test_forward_pass_candidates_match_the_per_trajectory_oracle(oracle, name):
     rng = np.random.default_rng(8)
     K = rng.uniform(-0.3, 0.3, (T, B, low.nu, low.nx))
     k = rng.uniform(-0.3, 0.3, (T, B, low.nu))
-    e = _engine(low)
-    for rid, v in ((_abi.R_XS, xs), (_abi.R_US, us), (_abi.R_KGAIN, K), (_abi.R_KFF, k)):
-        e.region(rid).copy_(torch.as_tensor(v))
-    e.region(_abi.R_TRAJ_I)[_abi.TI_FEASIBLE].fill_(1)
-    e.forward_pass(sp)
-    _sync()
-    X, U, Cs = _np(e.region(_abi.R_XS_TRY)), _np(e.region(_abi.R_US_TRY)), _np(e.region(_abi.R_TRAJ_F))
-    for ai in range(_abi.NALPHA):
-        xr, ur, cr, fail = _traj_oracle.forward_pass(oracle, low, sp, 0.5 ** ai, xs, us, K, k)
-        assert not fail.any()
-        for what, got, ref in (("xs", X[ai], xr), ("us", U[ai], ur), ("cost", Cs[_abi.TF_COST_TRY0 + ai], cr)):
-            err = _relerr(got, ref)
-            assert err < 1e-9, (name, ai, what, err)
-
-
-def _gpu_solve(low, sp, subshards=1, log_cap=0):
-    e = _engine(low)
-    if subshards > 1:
-        e.set_subshards(subshards)
-    if log_cap:
-        e.enable_iteration_log(log_cap)
-    e.set_candidate(None, None)
-    e.solve(sp)
-    _sync()
-    out = dict(xs=_np(e.region(_abi.R_XS)), us=_np(e.region(_abi.R_US)), traj_f=_np(e.region(_abi.R_TRAJ_F)),
-               traj_i=_np(e.region(_abi.R_TRAJ_I)))
-    if log_cap:
-        out["log"] = _np(e.iteration_log())
-    return out, e
+    e = gc.run_forward(low, sp, xs, us, K, k, None, 1)
+    oks, _ = gc.assert_forward_matches(*gc.forward_outputs(e), lambda alpha: _traj_oracle.forward_pass(oracle, low, sp, alpha, xs, us, K, k))
+    assert all(ok.all() for ok in oks)
 
 
 def _assert_solve_parity(gpu, ref, sp, allowed):
@@ -263,7 +177,7 @@ def test_full_solve_matches_the_per_trajectory_oracle(oracle, scen):
     conv = int(((ref["traj_i"][_abi.TI_STATUS] & _abi.ST_CONVERGED) != 0).sum())
     print("oracle converged on %d of %d" % (conv, low.B))
     assert conv >= 0.9 * low.B
-    gpu, _ = _gpu_solve(low, sp, log_cap=sp.maxiter)
+    _, gpu = gc.solve_gpu(low, sp, log_cap=sp.maxiter)
     _assert_solve_parity(gpu, ref, sp, TIE_FLIPS[scen])
 
 
@@ -277,7 +191,7 @@ def test_the_stiffness_floor_matters(oracle):
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc)
     ref = _traj_oracle.solve(oracle, low, sp, log_cap=sp.maxiter)
-    gpu, _ = _gpu_solve(low, sp, log_cap=sp.maxiter)
+    _, gpu = gc.solve_gpu(low, sp, log_cap=sp.maxiter)
     _assert_solve_parity(gpu, ref, sp, {})
     lb = low.traj_params["u_lb"][:, 2:]
     on_floor = (gpu["us"][:, :, 2:] == lb[None]).any(axis=(0, 2))
@@ -290,9 +204,9 @@ def test_a_table_equal_to_the_constants_changes_nothing(name):
     sc = _scenario(name, B=16, T=30)
     sc["traj_params"] = None
     sp = scenarios.solver_params(sc, maxiter=25)
-    plain, _ = _gpu_solve(scenarios.lower(sc), sp)
+    _, plain = gc.solve_gpu(scenarios.lower(sc), sp)
     sc["traj_params"] = scenarios.constant_traj_params(sc)
-    tab, e = _gpu_solve(scenarios.lower(sc), sp)
+    e, tab = gc.solve_gpu(scenarios.lower(sc), sp)
     np.testing.assert_array_equal(tab["traj_i"][_abi.TI_ITER], plain["traj_i"][_abi.TI_ITER])
     np.testing.assert_array_equal(tab["traj_i"][_abi.TI_STATUS], plain["traj_i"][_abi.TI_STATUS])
     dx, du = np.abs(tab["xs"] - plain["xs"]).max(), np.abs(tab["us"] - plain["us"]).max()
@@ -310,8 +224,8 @@ def test_scheduling_does_not_change_the_results():
     sc = _scenario("vsa2", B=256, T=30)
     sp = scenarios.solver_params(sc, maxiter=12)
     low = scenarios.lower(sc)
-    one, _ = _gpu_solve(low, sp)
-    four, _ = _gpu_solve(low, sp, subshards=4)
+    _, one = gc.solve_gpu(low, sp)
+    _, four = gc.solve_gpu(low, sp, subshards=4)
     for k in ("xs", "us", "traj_f", "traj_i"):
         np.testing.assert_array_equal(one[k], four[k], err_msg=k)
     big = dict(sc)
@@ -319,7 +233,7 @@ def test_scheduling_does_not_change_the_results():
     big["x0"] = np.tile(sc["x0"], (rep, 1))
     big["frame_refs"] = np.tile(sc["frame_refs"], (rep, 1))
     big["traj_params"] = {k: (None if v is None else np.tile(v, (rep, 1))) for k, v in sc["traj_params"].items()}
-    wide, _ = _gpu_solve(scenarios.lower(big), sp)
+    _, wide = gc.solve_gpu(scenarios.lower(big), sp)
     np.testing.assert_array_equal(wide["xs"][:, :256], one["xs"])
     np.testing.assert_array_equal(wide["us"][:, -256:], one["us"])
     np.testing.assert_array_equal(wide["traj_i"][_abi.TI_ITER][:256], one["traj_i"][_abi.TI_ITER])
@@ -332,9 +246,9 @@ def test_table_lifecycle(oracle):
     sp = scenarios.solver_params(sc, maxiter=20)
     plain = dict(sc)
     plain["traj_params"] = None
-    fresh, _ = _gpu_solve(scenarios.lower(plain), sp)
+    _, fresh = gc.solve_gpu(scenarios.lower(plain), sp)
     low = scenarios.lower(sc)
-    first, e = _gpu_solve(low, sp)
+    e, first = gc.solve_gpu(low, sp)
     assert np.abs(first["xs"] - fresh["xs"]).max() > 1e-6
     with pytest.raises(_abi.AslrError, match="parameter table"):
         e.solve_pool(low.x0, low.frame_ref, sp)
@@ -353,18 +267,18 @@ def test_table_lifecycle(oracle):
     e.set_trajectory_params(**low2.traj_params)
     e.set_candidate(None, None)
     e.solve(sp)
-    _sync()
+    gc.sync()
     ref2 = _traj_oracle.solve(oracle, low2, sp)
-    np.testing.assert_array_equal(_np(e.traj_i(_abi.TI_ITER)), ref2["traj_i"][_abi.TI_ITER])
-    assert np.abs(_np(e.region(_abi.R_XS)) - ref2["xs"]).max() < 1e-6
+    np.testing.assert_array_equal(gc.to_np(e.traj_i(_abi.TI_ITER)), ref2["traj_i"][_abi.TI_ITER])
+    assert np.abs(gc.to_np(e.region(_abi.R_XS)) - ref2["xs"]).max() < 1e-6
     # cleared: the bits of a handle that never had one
     e.set_trajectory_params()
     e.set_candidate(None, None)
     e.solve(sp)
-    _sync()
-    np.testing.assert_array_equal(_np(e.region(_abi.R_XS)), fresh["xs"])
-    np.testing.assert_array_equal(_np(e.region(_abi.R_US)), fresh["us"])
-    np.testing.assert_array_equal(_np(e.region(_abi.R_TRAJ_I)), fresh["traj_i"])
+    gc.sync()
+    np.testing.assert_array_equal(gc.to_np(e.region(_abi.R_XS)), fresh["xs"])
+    np.testing.assert_array_equal(gc.to_np(e.region(_abi.R_US)), fresh["us"])
+    np.testing.assert_array_equal(gc.to_np(e.region(_abi.R_TRAJ_I)), fresh["traj_i"])
 
 
 def _c_table(**fields):
@@ -388,20 +302,20 @@ def test_bad_tables_are_refused_by_the_library():
     """the checks of aslr_set_trajectory_params itself, past the Python pre-checks (a C caller has only these)"""
     B = 4
     sc = _scenario("vsa2", B=B, T=5)
-    e = _engine(scenarios.lower(dict(sc, traj_params=None)))
+    e = gc.engine(scenarios.lower(dict(sc, traj_params=None)))
     _refused(e, "VSA", stiffness=np.ones((B, 2)))
     _refused(e, "u_lb <= u_ub", u_lb=np.full((B, 4), 200.0))
     _refused(e, "u_lb <= u_ub", u_lb=np.zeros((B, 4)), u_ub=np.full((B, 4), np.nan))
     _refused(e, "motor_inertia", motor_inertia=np.zeros((B, 2)))
     _refused(e, "motor_inertia", motor_inertia=np.full((B, 2), np.inf))
     s2 = _scenario("sea2", B=B, T=5)
-    e2 = _engine(scenarios.lower(dict(s2, traj_params=None)))
+    e2 = gc.engine(scenarios.lower(dict(s2, traj_params=None)))
     _refused(e2, "no model of the problem has control limits", u_lb=np.zeros((B, 2)), u_ub=np.ones((B, 2)))
     _refused(e2, "stiffness", stiffness=np.full((B, 2), np.nan))
     # models that differ in a field the table leaves out
     s3 = _scenario("sea2", B=B, T=5)
     s3["terminal"].differential.B = 2.0 * np.asarray(s3["terminal"].differential.B)
-    e3 = _engine(scenarios.lower(dict(s3, traj_params=None)))
+    e3 = gc.engine(scenarios.lower(dict(s3, traj_params=None)))
     _refused(e3, "differ in B", stiffness=np.ones((B, 2)))
     st, keep = _c_table(stiffness=np.ones((B, 2)), motor_inertia=np.ones((B, 2)))  # ... given: accepted
     import ctypes as C
@@ -411,7 +325,7 @@ def test_bad_tables_are_refused_by_the_library():
     K = np.array(s4["running"][0].differential.K, dtype=float)
     K[0, 1] = K[1, 0] = 1e-3
     s4["running"][0].differential.K = K
-    e4 = _engine(scenarios.lower(dict(s4, traj_params=None)))
+    e4 = gc.engine(scenarios.lower(dict(s4, traj_params=None)))
     _refused(e4, "diagonal", motor_inertia=np.ones((B, 2)))
     # a refused table leaves the handle as it was: still the plain kernels, so a pool solve is not declined
     sp = scenarios.solver_params(sc, maxiter=3)
@@ -423,7 +337,7 @@ def test_the_table_region_lies_inside_the_workspace():
     import ctypes as C
     for name, rows in (("sea2", 8), ("vsa2", 12), ("sea7", 28), ("vsa7", 42)):
         low = scenarios.lower(_scenario(name, B=70, T=4))
-        e = _engine(low)
+        e = gc.engine(low)
         total = e.lib.aslr_workspace_bytes(C.byref(low.desc))
         r, prev = _abi.Region(), _abi.Region()
         _abi.check(e.lib.aslr_problem_region(e.handle, _abi.R_TRAJ_PARAMS, C.byref(r)), "region")
@@ -446,8 +360,8 @@ def test_python_facade_with_one_command_padding(oracle):
     sp = scenarios.solver_params(sc, solver="SolverFDDP", maxiter=30)
     ref = _traj_oracle.solve(oracle, scenarios.lower(sc), sp)
     e = problem.engine
-    np.testing.assert_array_equal(_np(e.traj_i(_abi.TI_ITER)), ref["traj_i"][_abi.TI_ITER])
-    assert np.abs(_np(e.region(_abi.R_XS)) - ref["xs"]).max() < 1e-6
+    np.testing.assert_array_equal(gc.to_np(e.traj_i(_abi.TI_ITER)), ref["traj_i"][_abi.TI_ITER])
+    assert np.abs(gc.to_np(e.region(_abi.R_XS)) - ref["xs"]).max() < 1e-6
     # nu = 1
     pc = scenarios.double_pendulum_nu1(T=30)  # (its models are built by this call: the box set here stays with them)
     pc["running"][0].u_lb, pc["running"][0].u_ub = np.array([-5.0]), np.array([5.0])
@@ -456,6 +370,6 @@ def test_python_facade_with_one_command_padding(oracle):
     s1.solve([], [], 10)
     low1 = p1.lowered
     ref1 = _traj_oracle.solve(oracle, low1, scenarios.solver_params(pc, solver="SolverBoxDDP", maxiter=10))
-    us = _np(p1.engine.region(_abi.R_US))
+    us = gc.to_np(p1.engine.region(_abi.R_US))
     assert us[..., 0].min() >= -0.7 and us[..., 0].max() <= 0.4 and (us[..., 1] == 0.0).all()
     assert np.abs(us - ref1["us"]).max() < 1e-6

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import _gpu_case as gc
 import _parity
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
@@ -20,53 +21,9 @@ pytestmark = pytest.mark.gpu
 TIE_FLIPS = {False: {}, True: {}}
 
 
-def _engine(low):
-    from aslr_to_amd.engine import Engine
-    return Engine(low)
-
-
-def _sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _relerr(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return np.max(np.abs(a - b) / (1.0 + np.abs(b))) if a.size else 0.0
-
-
-def _inputs(oracle, low, seed, lb, ub):
-    rng = np.random.default_rng(seed)
-    xs = rng.uniform(-0.8, 0.8, (low.T + 1, low.B, low.nx))
-    us = rng.uniform(-1.0, 1.0, (low.T, low.B, low.nu))
-    us[..., 7:] = rng.uniform(0.1, 5.0, (low.T, low.B, 7))
-    us = np.clip(us, lb, ub)
-    _, _, deriv = oracle.calc_diff(low, xs, us)
-    gaps = np.random.default_rng(seed + 7).uniform(-0.05, 0.05, (low.T + 1, low.B, low.nx))
-    return xs, us, deriv, gaps
-
-
-def _backward(e, sp, us, deriv, gaps, k0, xreg, feasible):
-    import torch
-    e.region(_abi.R_US).copy_(torch.as_tensor(us))
-    e.region(_abi.R_DERIV).copy_(torch.as_tensor(deriv))
-    e.region(_abi.R_GAPS).copy_(torch.as_tensor(gaps))
-    e.region(_abi.R_KFF).copy_(torch.as_tensor(k0))
-    e.region(_abi.R_TRAJ_F)[_abi.TF_XREG].fill_(xreg)
-    e.region(_abi.R_TRAJ_I)[_abi.TI_FEASIBLE].fill_(feasible)
-    e.region(_abi.R_TRAJ_I)[_abi.TI_STATUS].fill_(0)
-    e.backward_pass(sp)
-    _sync()
-    out = dict(K=_np(e.region(_abi.R_KGAIN)).copy(), k=_np(e.region(_abi.R_KFF)).copy(), Qu=_np(e.region(_abi.R_QU)).copy(),
-               Vx=_np(e.region(_abi.R_VX)).copy(), Vxx=_np(e.region(_abi.R_VXX)).copy())
-    for fld, name in ((_abi.TF_D1, "d1"), (_abi.TF_D2, "d2"), (_abi.TF_STOP, "stop")):
-        out[name] = _np(e.traj_f(fld)).copy()
-    out["status"] = _np(e.traj_i(_abi.TI_STATUS)).copy()
-    return out
+def _box(low):
+    m = low.desc.models[0]
+    return np.array(m.u_lb[:14]), np.array(m.u_ub[:14])
 
 
 @pytest.mark.parametrize("feasible", [1, 0])
@@ -78,15 +35,12 @@ def test_backward_pass_with_the_wave_box_qp_matches_oracle(oracle, monkeypatch, 
     sc = scenarios.talos_arm_vsa(B=5, T=12, seed=2, tight=True)
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc)
-    m = low.desc.models[0]
-    lb, ub = np.array(m.u_lb[:14]), np.array(m.u_ub[:14])
-    xs, us, deriv, gaps = _inputs(oracle, low, 3, lb, ub)
+    xs, us, deriv, gaps = gc.backward_inputs(oracle, low, 3, clip=_box(low))
     if feasible:
         gaps = np.zeros_like(gaps)
     k0 = np.random.default_rng(5).uniform(-0.5, 0.5, us.shape)
     xreg = 1e-3
     ref = oracle.backward_pass(low, sp, deriv, gaps, us, xreg, feasible, kff0=k0)
-    assert not ref["fail"].any()
     if feasible:
         clamped = (ref["Qu"] == 0.0).mean()
         print("clamped share of Qu: %.3f" % clamped)
@@ -94,77 +48,40 @@ def test_backward_pass_with_the_wave_box_qp_matches_oracle(oracle, monkeypatch, 
     outs = []
     for mfma in ("1", "0"):
         monkeypatch.setenv("ASLR_BLK_MFMA", mfma)
-        out = _backward(_engine(low), sp, us, deriv, gaps, k0, xreg, feasible)
-        assert (out["status"] & _abi.ST_BACKWARD_ERR == 0).all()
-        for name in ("K", "k", "Qu", "Vx", "Vxx", "d1", "d2", "stop"):
-            err = _relerr(out[name], ref[name])
-            print("mfma=%s feasible=%d %s relerr %.2e" % (mfma, feasible, name, err))
-            assert err < 1e-8, (name, err)
+        out = gc.run_backward(gc.engine(low), sp, us, deriv, gaps, xreg, feasible, k0=k0)
+        gc.assert_backward_matches(out, ref, 1e-8)
         if feasible:
             np.testing.assert_array_equal(out["Qu"] == 0.0, ref["Qu"] == 0.0)
         outs.append(out)
-    for name in ("K", "k", "Qu", "Vx", "Vxx", "d1", "d2", "stop"):
+    for name in gc.BACKWARD_FIELDS:
         np.testing.assert_array_equal(outs[0][name], outs[1][name], err_msg=name)
 
 
 def test_register_column_kernel_declines_nu_14(monkeypatch):
     monkeypatch.setenv("ASLR_BWD_HS", "2")
     sc = scenarios.talos_arm_vsa(B=2, T=3)
-    e = _engine(scenarios.lower(sc))
+    e = gc.engine(scenarios.lower(sc))
     with pytest.raises(_abi.AslrError, match="nu=14"):
         e.backward_pass(scenarios.solver_params(sc))
 
 
 def test_forward_pass_matches_oracle_for_every_alpha(oracle):
-    import torch
     sc = scenarios.talos_arm_vsa(B=5, T=6, seed=1, tight=True)
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc)
-    m = low.desc.models[0]
-    lb, ub = np.array(m.u_lb[:14]), np.array(m.u_ub[:14])
-    xs, us, deriv, gaps = _inputs(oracle, low, 5, lb, ub)
+    lb, ub = _box(low)
+    xs, us, deriv, gaps = gc.backward_inputs(oracle, low, 5, clip=(lb, ub))
     ref_b = oracle.backward_pass(low, sp, deriv, np.zeros_like(gaps), us, 1e-3, 0)
     K, k = 0.05 * ref_b["K"], 0.05 * ref_b["k"]  # mild gains keep every alpha's rollout finite
-    e = _engine(low)
-    e.region(_abi.R_XS).copy_(torch.as_tensor(xs))
-    e.region(_abi.R_US).copy_(torch.as_tensor(us))
-    e.region(_abi.R_KGAIN).copy_(torch.as_tensor(K))
-    e.region(_abi.R_KFF).copy_(torch.as_tensor(k))
-    e.region(_abi.R_TRAJ_I)[_abi.TI_FEASIBLE].fill_(1)
-    e.forward_pass(sp)
-    _sync()
-    XT, UT = _np(e.region(_abi.R_XS_TRY)), _np(e.region(_abi.R_US_TRY))
+    XT, UT, costs = gc.forward_outputs(gc.run_forward(low, sp, xs, us, K, k, None, 1))
+    oks, refs = gc.assert_forward_matches(XT, UT, costs, lambda alpha: oracle.forward_pass(low, sp, alpha, xs, us, K, k))
     on_bound = 0
-    for a in range(_abi.NALPHA):
-        xs_try, us_try, cost_try, fail = oracle.forward_pass(low, sp, 0.5 ** a, xs, us, K, k)
-        ok = fail == 0
-        assert ok.any()
-        assert _relerr(XT[a][:, ok], xs_try[:, ok]) < 1e-9
-        assert _relerr(UT[a][:, ok], us_try[:, ok]) < 1e-9
-        got = _np(e.traj_f(_abi.TF_COST_TRY0 + a))
-        assert _relerr(got[ok], cost_try[ok]) < 1e-9
-        assert np.isnan(got[~ok]).all()
-        ut = us_try[:, ok]
+    for a, ok in enumerate(oks):
+        ut = refs[a][1][:, ok]
         assert (ut >= lb).all() and (ut <= ub).all()
         on_bound += int(((ut == lb) | (ut == ub)).sum())
         np.testing.assert_array_equal((UT[a][:, ok] == lb) | (UT[a][:, ok] == ub), (ut == lb) | (ut == ub))
     assert on_bound > 0   # the clamp of us_try is exercised (both halves of u are boxed)
-
-
-def _solve_both(oracle, tight, B=64, T=50, seed=3):
-    sc = scenarios.talos_arm_vsa(B=B, T=T, seed=seed, tight=tight)
-    low = scenarios.lower(sc)
-    sp = scenarios.solver_params(sc)
-    nth = min(16, len(os.sched_getaffinity(0)))
-    ref = oracle.solve(low, sp, nthreads=nth, log_cap=sp.maxiter)
-    e = _engine(low)
-    e.set_candidate(None, None)
-    e.enable_iteration_log(sp.maxiter)
-    e.solve(sp, poll_every=4)
-    _sync()
-    gpu = dict(xs=_np(e.region(_abi.R_XS)), us=_np(e.region(_abi.R_US)), traj_f=_np(e.region(_abi.R_TRAJ_F)),
-               traj_i=_np(e.region(_abi.R_TRAJ_I)), log=_np(e.iteration_log()))
-    return sc, low, sp, e, gpu, ref
 
 
 @pytest.mark.parametrize("tight", [False, True])
@@ -172,7 +89,11 @@ def test_full_solves_match_oracle_trajectory_by_trajectory(oracle, tight):
     """(B = 64, T = 50, seed = 3) of the scenario and of its test variant with active torque bounds: iteration counts and
     status words equal on every trajectory (but those named in TIE_FLIPS: at most one), xs / us within 1e-6 and the cost
     within 1e-4 relative on those."""
-    sc, low, sp, e, gpu, ref = _solve_both(oracle, tight)
+    sc = scenarios.talos_arm_vsa(B=64, T=50, seed=3, tight=tight)
+    low = scenarios.lower(sc)
+    sp = scenarios.solver_params(sc)
+    ref = oracle.solve(low, sp, nthreads=min(16, len(os.sched_getaffinity(0))), log_cap=sp.maxiter)
+    _, gpu = gc.solve_gpu(low, sp, log_cap=sp.maxiter)
     r = _parity.compare(gpu, ref, sp)
     text = "\n".join(_parity.describe(row, sp) for row in r["exceptions"])
     it_g, it_r = gpu["traj_i"][_abi.TI_ITER], ref["traj_i"][_abi.TI_ITER]
@@ -193,9 +114,9 @@ def test_full_solves_match_oracle_trajectory_by_trajectory(oracle, tight):
     cost_r = ref["traj_f"][_abi.TF_COST]
     assert r["dx"][same].max() < 1e-6 and r["du"][same].max() < 1e-6
     assert (r["dc"][same] / np.maximum(1.0, np.abs(cost_r[same]))).max() < 1e-4
-    m = low.desc.models[0]
     U = gpu["us"]
-    assert (U >= np.array(m.u_lb[:14])).all() and (U <= np.array(m.u_ub[:14])).all()
+    lb, ub = _box(low)
+    assert (U >= lb).all() and (U <= ub).all()
     assert (U[..., 7:] == 1.0).mean() > 0.3
     if tight:
         assert (np.abs(U[..., :7]) == 1.0).any()
@@ -206,10 +127,10 @@ def test_pool_and_subshards_give_the_bits_of_the_batch_solve():
     P, slots_n, T = 40, 16, 20
     sc = scenarios.talos_arm_vsa(B=P, T=T, seed=6, tight=True)
     sp = scenarios.solver_params(sc, maxiter=60)
-    full = _engine(scenarios.lower(sc))
+    full = gc.engine(scenarios.lower(sc))
     full.set_candidate(None, None)
     full.solve(sp, poll_every=8)
-    _sync()
+    gc.sync()
     X = full.region(_abi.R_XS).permute(1, 0, 2).contiguous()
     U = full.region(_abi.R_US).permute(1, 0, 2).contiguous()
     iters, status = full.traj_i(_abi.TI_ITER).clone(), full.traj_i(_abi.TI_STATUS).clone()
@@ -217,7 +138,7 @@ def test_pool_and_subshards_give_the_bits_of_the_batch_solve():
     assert int(iters.min()) < int(iters.max())
     slots = dict(sc)
     slots["x0"], slots["frame_refs"] = sc["x0"][:slots_n], sc["frame_refs"][:slots_n]
-    e = _engine(scenarios.lower(slots))
+    e = gc.engine(scenarios.lower(slots))
     r = e.solve_pool(sc["x0"], sc["frame_refs"], sp, refill_every=3, poll_every=9)
     assert torch.equal(r["iters"], iters) and torch.equal(r["status"], status)
     assert torch.equal(r["xs"], X) and torch.equal(r["us"], U) and torch.equal(r["cost"], cost)
@@ -226,11 +147,11 @@ def test_pool_and_subshards_give_the_bits_of_the_batch_solve():
     sp2 = scenarios.solver_params(sc2, maxiter=12)
     outs = []
     for nsub in (1, 2):
-        e2 = _engine(scenarios.lower(sc2))
+        e2 = gc.engine(scenarios.lower(sc2))
         e2.set_subshards(nsub)
         e2.set_candidate(None, None)
         e2.solve(sp2, poll_every=4)
-        _sync()
+        gc.sync()
         outs.append((e2.region(_abi.R_XS).clone(), e2.region(_abi.R_US).clone(), e2.traj_i(_abi.TI_ITER).clone(),
                      e2.region(_abi.R_KGAIN).clone()))
     for a, b in zip(*outs):

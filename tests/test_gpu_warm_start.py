@@ -13,18 +13,10 @@ import pytest
 
 from aslr_to_amd import _abi, scenarios
 
+import _gpu_case as gc
 import _parity
 
 pytestmark = pytest.mark.gpu
-
-
-def _engine(low):
-    from aslr_to_amd.engine import Engine
-    return Engine(low)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 def _guess(sc, low, seed=3):
@@ -37,33 +29,28 @@ def _guess(sc, low, seed=3):
     return xs, us
 
 
-def _solve_both(oracle, low, sp, xs, us, nthreads=8):
-    """The oracle and the GPU from the same candidate (None: the empty one), both with their iteration logs."""
-    import torch
+def _solve(oracle, low, sp, xs, us, nthreads=8):
+    """The oracle and the GPU from the same candidate (None: the empty one), both with their iteration logs
+    -> the engine, gc.solution of it, the oracle's result"""
     ref = oracle.solve(low, sp, xs=xs, us=us, nthreads=nthreads, log_cap=sp.maxiter)
-    e = _engine(low)
-    e.set_candidate(None if xs is None else xs.transpose(1, 0, 2), None if us is None else us.transpose(1, 0, 2))
-    e.enable_iteration_log(sp.maxiter)
-    e.solve(sp, poll_every=4)
-    torch.cuda.synchronize()
-    return e, ref
+    return gc.solve_gpu(low, sp, xs, us, log_cap=sp.maxiter) + (ref,)
 
 
-def _compare(e, ref, label, sel=None):
+def _compare(gpu, ref, label, sel=None):
     """Iteration counts, status words and the logged decisions exactly; iterates and costs within north_star's
     tolerances -- on the trajectories in `sel` (a mask; default: all of them)."""
     it_r, st_r = ref["traj_i"][_abi.TI_ITER], ref["traj_i"][_abi.TI_STATUS]
     sel = np.ones(it_r.shape, dtype=bool) if sel is None else sel
-    np.testing.assert_array_equal(_np(e.traj_i(_abi.TI_ITER))[sel], it_r[sel])
-    _parity.assert_status_words_match(_np(e.traj_i(_abi.TI_STATUS))[sel], st_r[sel])
-    lg, lr = _np(e.iteration_log()), ref["log"]
+    np.testing.assert_array_equal(gpu["traj_i"][_abi.TI_ITER][sel], it_r[sel])
+    _parity.assert_status_words_match(gpu["traj_i"][_abi.TI_STATUS][sel], st_r[sel])
+    lg, lr = gpu["log"], ref["log"]
     for row, what in ((_abi.LOG_ACCEPTED, "accepted step index"), (_abi.LOG_FEASIBLE, "feasibility"), (_abi.LOG_XREG, "x_reg")):
         np.testing.assert_array_equal(lg[:, row][:, sel], lr[:, row][:, sel], err_msg="per-iteration %s (rows: iterations)" % what)
     scale = np.maximum(1.0, np.maximum(np.abs(ref["xs"]).max(axis=(0, 2)), np.abs(ref["us"]).max(axis=(0, 2))))
-    dx = (np.abs(_np(e.region(_abi.R_XS)) - ref["xs"]).max(axis=(0, 2)) / scale)[sel].max()
-    du = (np.abs(_np(e.region(_abi.R_US)) - ref["us"]).max(axis=(0, 2)) / scale)[sel].max()
+    dx = (np.abs(gpu["xs"] - ref["xs"]).max(axis=(0, 2)) / scale)[sel].max()
+    du = (np.abs(gpu["us"] - ref["us"]).max(axis=(0, 2)) / scale)[sel].max()
     cost = ref["traj_f"][_abi.TF_COST]
-    dc = (np.abs(_np(e.traj_f(_abi.TF_COST)) - cost) / np.maximum(1.0, np.abs(cost)))[sel].max()
+    dc = (np.abs(gpu["traj_f"][_abi.TF_COST] - cost) / np.maximum(1.0, np.abs(cost)))[sel].max()
     print("%s: iterations %d..%d, max rel |dx| %.2e |du| %.2e |dcost| %.2e"
           % (label, it_r[sel].min(), it_r[sel].max(), dx, du, dc))
     assert dx < 1e-6 and du < 1e-6, (dx, du)
@@ -96,13 +83,13 @@ def test_warm_started_solve_matches_oracle(oracle, name, solver, B, T, seed, per
     sp = scenarios.solver_params(sc, solver=solver, maxiter=100)
     assert sp.is_feasible == 0
     xs, us = _guess(sc, low, seed)
-    e, ref = _solve_both(oracle, low, sp, xs, us)
+    _, gpu, ref = _solve(oracle, low, sp, xs, us)
     assert ((ref["traj_i"][_abi.TI_STATUS] & _abi.ST_CONVERGED) != 0).all()
     if persistent:   # (a condition on the guess: change the seed, not this line)
         n = _persistent_gap_iterations(ref["log"])
         print("iterations that keep their gaps, per trajectory: %s" % n)
         assert n.max() >= 1
-    _compare(e, ref, "%s %s B=%d T=%d from a guess" % (name, solver, B, T))
+    _compare(gpu, ref, "%s %s B=%d T=%d from a guess" % (name, solver, B, T))
 
 
 def test_boxddp_first_iterations_from_a_guess_take_the_oracles_decisions(oracle):
@@ -115,10 +102,10 @@ def test_boxddp_first_iterations_from_a_guess_take_the_oracles_decisions(oracle)
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc, solver="SolverBoxDDP", maxiter=6)
     xs, us = _guess(sc, low)
-    e, ref = _solve_both(oracle, low, sp, xs, us)
-    np.testing.assert_array_equal(_np(e.traj_i(_abi.TI_ITER)), ref["traj_i"][_abi.TI_ITER])
-    _parity.assert_status_words_match(_np(e.traj_i(_abi.TI_STATUS)), ref["traj_i"][_abi.TI_STATUS])
-    np.testing.assert_array_equal(_np(e.traj_f(_abi.TF_XREG)), ref["traj_f"][_abi.TF_XREG])
+    _, gpu, ref = _solve(oracle, low, sp, xs, us)
+    np.testing.assert_array_equal(gpu["traj_i"][_abi.TI_ITER], ref["traj_i"][_abi.TI_ITER])
+    _parity.assert_status_words_match(gpu["traj_i"][_abi.TI_STATUS], ref["traj_i"][_abi.TI_STATUS])
+    np.testing.assert_array_equal(gpu["traj_f"][_abi.TF_XREG], ref["traj_f"][_abi.TF_XREG])
     print("2-DoF VSA BoxDDP, 6 iterations from a guess: status %s, x_reg %s"
           % (sorted(set(ref["traj_i"][_abi.TI_STATUS].tolist())), sorted(set(ref["traj_f"][_abi.TF_XREG].tolist()))))
 
@@ -141,7 +128,7 @@ def test_boxddp_from_a_perturbed_iterate_switches_to_the_qp_like_the_oracle(orac
     cold = oracle.solve(low, scenarios.solver_params(sc, solver="SolverBoxDDP", maxiter=5))
     xs = cold["xs"] + np.random.default_rng(1).uniform(-1e-3, 1e-3, cold["xs"].shape)
     sp = scenarios.solver_params(sc, solver="SolverBoxDDP")
-    e, ref = _solve_both(oracle, low, sp, xs, cold["us"])
+    _, gpu, ref = _solve(oracle, low, sp, xs, cold["us"])
     st, it = ref["traj_i"][_abi.TI_STATUS], ref["traj_i"][_abi.TI_ITER]
     conv = (st & _abi.ST_CONVERGED) != 0
     assert conv.sum() >= 12 and (st & _abi.ST_BACKWARD_ERR == 0).all()
@@ -158,8 +145,8 @@ def test_boxddp_from_a_perturbed_iterate_switches_to_the_qp_like_the_oracle(orac
     # rounding under the three perturbations above); the GPU code has no part in it.  If this line fails after the oracle
     # was built with another compiler or OpenMP runtime, derive the set again on the oracle; it is no kernel defect.
     assert list(np.nonzero(~stable)[0]) == [7]
-    _compare(e, ref, "2-DoF VSA BoxDDP from a perturbed iterate", sel=stable & conv)
-    lg = _np(e.iteration_log())
+    _compare(gpu, ref, "2-DoF VSA BoxDDP from a perturbed iterate", sel=stable & conv)
+    lg = gpu["log"]
     for row in (_abi.LOG_ACCEPTED, _abi.LOG_FEASIBLE, _abi.LOG_XREG):
         np.testing.assert_array_equal(lg[:12, row][:, ~stable], ref["log"][:12, row][:, ~stable])
 
@@ -168,20 +155,16 @@ def test_boxddp_from_a_perturbed_iterate_switches_to_the_qp_like_the_oracle(orac
 def test_feasible_warm_start_matches_oracle(oracle, solver):
     """The GPU's own iterate after three cold iterations, declared feasible (is_feasible = 1: no gap terms anywhere),
     solved again on the GPU and by the oracle from the same arrays."""
-    import torch
     sc = scenarios.two_dof_sea(B=16, T=40)
     low = scenarios.lower(sc)
-    e0 = _engine(low)
-    e0.set_candidate(None, None)
-    e0.solve(scenarios.solver_params(sc, solver="SolverDDP", maxiter=3), poll_every=0)
-    torch.cuda.synchronize()
-    xs, us = _np(e0.region(_abi.R_XS)).copy(), _np(e0.region(_abi.R_US)).copy()
+    _, third = gc.solve_gpu(low, scenarios.solver_params(sc, solver="SolverDDP", maxiter=3), poll_every=0)
+    xs, us = third["xs"], third["us"]
     sp = scenarios.solver_params(sc, solver=solver, is_feasible=1)
-    e, ref = _solve_both(oracle, low, sp, xs, us)
+    _, gpu, ref = _solve(oracle, low, sp, xs, us)
     assert ((ref["traj_i"][_abi.TI_STATUS] & _abi.ST_CONVERGED) != 0).all()
     assert (ref["log"][0, _abi.LOG_FEASIBLE] == 1).all()
-    np.testing.assert_array_equal(_np(e.traj_i(_abi.TI_STATUS)), ref["traj_i"][_abi.TI_STATUS])
-    _compare(e, ref, "2-DoF SEA %s from the GPU's third iterate, feasible" % solver)
+    np.testing.assert_array_equal(gpu["traj_i"][_abi.TI_STATUS], ref["traj_i"][_abi.TI_STATUS])
+    _compare(gpu, ref, "2-DoF SEA %s from the GPU's third iterate, feasible" % solver)
 
 
 def test_cold_and_warm_trajectories_in_one_batch(oracle):
@@ -195,18 +178,12 @@ def test_cold_and_warm_trajectories_in_one_batch(oracle):
     xs, us = _guess(sc, low)
     odd = np.arange(low.B) % 2 == 1
     xs_mix, us_mix = np.where(odd[None, :, None], xs, 0.0), np.where(odd[None, :, None], us, 0.0)
-    e, ref = _solve_both(oracle, low, sp, xs_mix, us_mix)
-    _compare(e, ref, "2-DoF SEA FDDP, cold and warm trajectories mixed")
+    e, gpu, ref = _solve(oracle, low, sp, xs_mix, us_mix)
+    _compare(gpu, ref, "2-DoF SEA FDDP, cold and warm trajectories mixed")
     regions = (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_F, _abi.R_TRAJ_I)
     mixed = [e.region(r).clone() for r in regions]
-    for which, cand in ((~odd, (None, None)), (odd, (xs.transpose(1, 0, 2), us.transpose(1, 0, 2)))):
-        h = _engine(low)
-        h.set_candidate(*cand)
-        h.solve(sp, poll_every=4)
-        torch.cuda.synchronize()
+    for which, cand in ((~odd, (None, None)), (odd, (xs, us))):
+        h, _ = gc.solve_gpu(low, sp, *cand)
         sel = torch.as_tensor(which, device=h.device)
         for r, m in zip(regions, mixed):
-            a, b = h.region(r)[:, sel], m[:, sel]
-            if a.dtype == torch.float64:
-                a, b = a.view(torch.int64), b.view(torch.int64)
-            assert torch.equal(a, b), "region %d of the %s trajectories" % (r, "warm" if which is odd else "cold")
+            gc.same_bits(h.region(r)[:, sel], m[:, sel], "region %d of the %s trajectories" % (r, "warm" if which is odd else "cold"))
