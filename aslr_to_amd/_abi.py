@@ -13,7 +13,7 @@ MAX_NU = 14
 MAX_COSTS = 6
 MAX_MODELS = 4
 NALPHA = 10
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 OK, E_INVALID, E_HIP, E_NODEVICE, E_WORKSPACE = 0, -1, -2, -3, -4
 DAM_SEA, DAM_VSA = 0, 1
@@ -161,7 +161,7 @@ EXPORTED_SYMBOLS = [
     "aslr_iterate", "aslr_iterate_timed", "aslr_finalize", "aslr_count_active", "aslr_dam_eval", "aslr_quasi_static", "aslr_last_error",
     "aslr_dam_residuals", "aslr_residual_len", "aslr_frame_placement", "aslr_set_iteration_log",
     "aslr_iterate_n", "aslr_set_subshards", "aslr_solve_pool", "aslr_set_trajectory_params",
-    "aslr_mpc_run",
+    "aslr_mpc_run", "aslr_set_reference_path", "aslr_reference_row",
 ]
 
 
@@ -233,6 +233,10 @@ def load_library():
     lib.aslr_set_trajectory_params.argtypes = [vp, C.POINTER(TrajParams), vp]
     lib.aslr_mpc_run.restype = C.c_int
     lib.aslr_mpc_run.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), vp]
+    lib.aslr_set_reference_path.restype = C.c_int
+    lib.aslr_set_reference_path.argtypes = [vp, vp, i32, i32, vp]
+    lib.aslr_reference_row.restype = C.c_int
+    lib.aslr_reference_row.argtypes = [vp, C.POINTER(i32)]
     lib.aslr_set_iteration_log.restype = C.c_int
     lib.aslr_set_iteration_log.argtypes = [vp, vp, i32]
     if lib.aslr_abi_version() != ABI_VERSION:

@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 from . import _abi
-from .lowering import lower_problem, lower_traj_params, shard_rows
+from .lowering import lower_problem, lower_reference_path, lower_traj_params, shard_rows
 from .models import (ActivationModelQuad, ActivationModelWeightedQuad, CostModelResidual,  # noqa: F401
                      CostModelSum, Jcomponent, ResidualModelControl, ResidualModelState)
 
@@ -115,10 +115,12 @@ class ShootingProblem(object):
     (SURVEY.md 8(e)); every trajectory is solved independently, so results do not depend on the
     sharding.  `stiffness` / `motor_inertia` ([B, nj]) and `u_lb` / `u_ub` ([B, nu]) give every trajectory its own
     diagonal K and B and its own control box (a design sweep in one batch); sharded like x0s and frame_refs.
+    `frame_ref_path` ([B, N, 12] or B lists of N SE3) gives every trajectory a reference placement per knot: knot t tracks
+    row min(reference_row + t, N - 1) with every frame-placement cost (set_reference_path; solve_mpc slides along it).
     """
 
     def __init__(self, x0, runningModels, terminalModel, frame_refs=None, rank=0, world_size=1, device=None,
-                 stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
+                 stiffness=None, motor_inertia=None, u_lb=None, u_ub=None, frame_ref_path=None):
         x0 = np.atleast_2d(np.asarray(x0, dtype=np.float64))
         self._x0_all = x0
         self.batch_total = x0.shape[0]
@@ -136,6 +138,29 @@ class ShootingProblem(object):
         self.nx, self.nu = self._lowered.nx, self._lowered.nu_user
         self._device = device
         self._engine = None
+        if frame_ref_path is not None:
+            self.set_reference_path(frame_ref_path)
+
+    def set_reference_path(self, path=None, row0=0):
+        """Set (whole-batch [B, N, 12] array or B lists of N SE3), reposition or clear (None) the time-varying reference
+        placements between solves; knot t then tracks row min(row0 + t, N - 1)."""
+        low = self._lowered
+        if path is None:
+            low.ref_path = None
+        else:
+            if len(path) != self.batch_total:
+                raise ValueError("frame_ref_path must have shape [B=%d, n_rows, 12], got %d paths" % (self.batch_total, len(path)))
+            lo, hi = self.rows
+            low.ref_path = (lower_reference_path(low.desc, path[lo:hi], row0), int(row0))
+        if self._engine is not None:
+            self._engine.upload_reference_path(*(low.ref_path or (None, 0)))
+
+    @property
+    def reference_row(self):
+        """the path row knot 0 tracks: row0 of set_reference_path plus the control steps of every solve_mpc since"""
+        if self._engine is not None:
+            return self._engine.reference_row
+        return 0 if self._lowered.ref_path is None else self._lowered.ref_path[1]
 
     def _shard_params(self, stiffness, motor_inertia, u_lb, u_ub):
         """rows of this rank out of whole-batch parameter arrays"""
@@ -394,6 +419,8 @@ class SolverDDP(object):
         disturbance[:, s] ([B, n_steps, nx], optional) to its next state, shift the plan one knot,
         `solve(xs, us, iters_per_step, isFeasible)` -- the loop a script writes around solver.solve, without a host
         round trip per step.  Callbacks are not replayed (the per-iteration log would be overwritten every step).
+        With a reference path (ShootingProblem(frame_ref_path=) / set_reference_path) step s plans against the rows
+        reference_row + s + t; afterwards problem.reference_row has grown by n_steps (MpcResult.reference_row).
         -> engine.MpcResult; solver.xs / us are the last shifted plan."""
         e = self.problem.engine
         sp = self._sp

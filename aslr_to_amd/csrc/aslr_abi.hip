@@ -231,6 +231,13 @@ struct aslr_problem {
   // const_written = a sweep that evaluated every knot of every trajectory has put them in place (diff_mode)
   bool const_ok, const_written;
   bool uniform_running; // every running knot uses one action model (aslr_mpc_run shifts the plan along the horizon)
+  // aslr_set_reference_path: while a path is set, k.frame_ref / k.ref_row0 / k.ref_last describe the caller's buffer and
+  // k.planar_reach is off; these are what the handle was created with, put back when the path is cleared (and what
+  // aslr_dam_eval / aslr_dam_residuals keep reading)
+  bool ref_path_set;
+  const double *own_frame_ref;
+  int32_t own_planar_reach;
+  bool has_placement; // some model of the problem has a frame-placement cost
 };
 
 namespace {
@@ -592,6 +599,10 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   for (int i = 0; i < desc->nmodels; ++i)
     for (int c = 0; c < desc->models[i].ncosts; ++c)
       if (desc->models[i].costs[c].type == ASLR_COST_PENDULUM) p->const_ok = false;
+  p->has_placement = false;
+  for (int i = 0; i < desc->nmodels; ++i)
+    for (int c = 0; c < desc->models[i].ncosts; ++c)
+      if (desc->models[i].costs[c].type == ASLR_COST_FRAME_PLACEMENT) p->has_placement = true;
   int64_t total;
   carve(desc, nx, nu, p->regions, &total);
   if (!workspace || workspace_bytes < total || (reinterpret_cast<uintptr_t>(workspace) & 255u)) {
@@ -657,6 +668,10 @@ int aslr_problem_create(const aslr_problem_desc_t *desc, void *workspace, int64_
   k.iter_log = nullptr; k.log_cap = 0;
   k.seg_t0 = 0; k.seg_t1 = desc->T;
   k.pipeline = getenv("ASLR_PIPELINE") ? atoi(getenv("ASLR_PIPELINE")) : 1; // (read once, when the handle is created)
+  k.ref_row0 = 0; k.ref_last = 0; // the create-time table: a path of one row
+  p->ref_path_set = false;
+  p->own_frame_ref = k.frame_ref;
+  p->own_planar_reach = planar_reach;
   *out = p.release();
   return ASLR_OK;
 }
@@ -735,6 +750,36 @@ int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, 
   HIP_TRY(hipMemcpyAsync(p->ws + p->regions[ASLR_R_TRAJ_PARAMS].offset, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st)); // (the staging buffer dies here)
   switch_to(true);
+  return ASLR_OK;
+}
+
+int aslr_set_reference_path(aslr_problem_t *p, const double *path, int32_t n_rows, int32_t row0, void *stream) {
+  (void)stream; // nothing is uploaded or copied: the kernels read the caller's buffer where it lies
+  if (!p) return ASLR_E_INVALID;
+  KArgs &k = p->k;
+  if (!path) { // back to the references the handle was created with
+    k.frame_ref = p->own_frame_ref;
+    k.ref_row0 = 0; k.ref_last = 0;
+    k.planar_reach = p->own_planar_reach;
+    p->ref_path_set = false;
+    return ASLR_OK;
+  }
+  auto fail = [&](const char *msg) { snprintf(g_err, sizeof g_err, "aslr_set_reference_path: %s", msg); return ASLR_E_INVALID; };
+  if (n_rows < 1) return fail("n_rows must be >= 1");
+  if (row0 < 0 || row0 >= n_rows) return fail("row0 must lie in [0, n_rows)");
+  if (!p->has_placement) return fail("no model of the problem has a frame-placement cost");
+  k.frame_ref = path;
+  k.ref_row0 = row0; k.ref_last = n_rows - 1;
+  // the closed-form reach residual was validated for the create-time references only (fill_planar_reach): path rows take
+  // the general log map, as pool targets do
+  k.planar_reach = 0;
+  p->ref_path_set = true;
+  return ASLR_OK;
+}
+
+int aslr_reference_row(const aslr_problem_t *p, int32_t *row0) {
+  if (!p || !row0) return ASLR_E_INVALID;
+  *row0 = p->k.ref_row0;
   return ASLR_OK;
 }
 
@@ -916,16 +961,22 @@ int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_m
   if (!p || !sp || !mpc) return fail("NULL argument");
   if (mpc->n_steps < 1 || mpc->first_maxiter < 1 || mpc->iters_per_step < 1) return fail("n_steps, first_maxiter and iters_per_step must be >= 1");
   if (!mpc->x_closed || !mpc->u_closed || !mpc->stat_f || !mpc->stat_i) return fail("x_closed, u_closed, stat_f and stat_i must be given");
-  if (!p->uniform_running) return fail("the running knots use more than one action model: shifting the plan needs one (per-knot references are not supported)");
+  if (!p->uniform_running) return fail("the running knots use more than one action model: shifting the plan needs one (references that vary along the horizon: aslr_set_reference_path)");
   if (p->k.iter_log) return fail("an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)");
   if (int rc = solver_unsupported(p, sp->solver)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t B = p->desc.B, nx = p->nx, nu = p->nu;
-  KArgs plant = p->k; // the plant: node 0's action model on knot 0 of every trajectory, through the handle's calc launcher
-  plant.seg_t1 = 0;
+  const int32_t row0 = p->k.ref_row0;
+  if (p->ref_path_set && row0 > INT32_MAX - mpc->n_steps - p->desc.T) return fail("the reference row would overflow: reposition it with aslr_set_reference_path");
   for (int s = 0; s < mpc->n_steps; ++s) {
+    // with a reference path the window slides one row per control step: step s plans against rows row0 + s + t.  The
+    // offset travels by value in the argument block; nothing moves on the device
+    KArgs ks = p->k;
+    if (p->ref_path_set) ks.ref_row0 = row0 + s;
+    KArgs plant = ks; // the plant: node 0's action model on knot 0 of every trajectory, through the handle's calc launcher
+    plant.seg_t1 = 0;
     // a solve as aslr_solve enqueues it when the host never polls
-    if (int rc = iterate(p, sp, true, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, st, IterOpts{p->k, 0, true, nullptr})) return rc;
+    if (int rc = iterate(p, sp, true, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, st, IterOpts{ks, 0, true, nullptr})) return rc;
     if (int rc = aslr_finalize(p, stream)) return rc;
     if (int rc = launch_calc(p, plant, false, 0, -1.0, st)) return rc;
     MpcDev m;
@@ -939,6 +990,7 @@ int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_m
     hipLaunchKernelGGL(mpc_advance_kernel, dim3(p->desc.B), dim3(64), 0, st, p->k, m);
     HIP_TRY(hipGetLastError());
   }
+  if (p->ref_path_set) p->k.ref_row0 = row0 + mpc->n_steps; // (the next run, or a solve, carries on where this one ended)
   return ASLR_OK;
 }
 
@@ -953,6 +1005,10 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
   }
   if (p->ks->traj_params) {
     snprintf(g_err, sizeof g_err, "aslr_solve_pool: the handle has a per-trajectory parameter table set (a pool problem would inherit its slot's parameters); clear it with aslr_set_trajectory_params(p, NULL, stream)");
+    return ASLR_E_INVALID;
+  }
+  if (p->ref_path_set) {
+    snprintf(g_err, sizeof g_err, "aslr_solve_pool: the handle has a reference path set (a pool problem would inherit its slot's path); clear it with aslr_set_reference_path(p, NULL, 0, 0, stream)");
     return ASLR_E_INVALID;
   }
   if (int rc = solver_unsupported(p, sp->solver)) return rc;
@@ -1031,7 +1087,9 @@ int aslr_dam_eval(aslr_problem_t *p, int32_t model_index, int32_t n, const doubl
                   void *stream) {
   if (!p || n <= 0 || model_index < 0 || model_index >= p->desc.nmodels || !x || !u) return ASLR_E_INVALID;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  return p->ks->dam_eval(p->k, model_index, n, x, u, xout, cost, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu, st);
+  KArgs k = p->k;
+  k.frame_ref = p->own_frame_ref; // (trajectory 0's create-time reference, whatever path is set)
+  return p->ks->dam_eval(k, model_index, n, x, u, xout, cost, Fx, Fu, Lx, Lu, Lxx, Lxu, Luu, st);
 }
 
 int32_t aslr_residual_len(const aslr_model_t *m, int32_t nj) {
@@ -1056,7 +1114,9 @@ int aslr_dam_residuals(aslr_problem_t *p, int32_t model_index, int32_t n, const 
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nr = aslr_residual_len(&p->desc.models[model_index], p->nj);
   if (nr <= 0) return nr < 0 ? nr : ASLR_OK;
-  return p->ks->dam_residuals(p->k, model_index, n, x, u, r, nr, st);
+  KArgs k = p->k;
+  k.frame_ref = p->own_frame_ref;
+  return p->ks->dam_residuals(k, model_index, n, x, u, r, nr, st);
 }
 
 int aslr_frame_placement(aslr_problem_t *p, int32_t frame_joint, const double *frame_R, const double *frame_p, int32_t n,

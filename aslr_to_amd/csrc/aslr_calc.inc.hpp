@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(64, ASLR_CALC_WAVES) calc_kernel(KArgs a, int 
 
   const DevDesc &D = *a.desc;
   const DevModel &dm = D.models[node_model_at(a, t)];
-  const double *fref = a.frame_ref ? a.frame_ref + 12 * (size_t)b : nullptr;
+  const double *fref = a.frame_ref ? a.frame_ref + 12 * ((size_t)min(a.ref_row0 + t, a.ref_last) * B + b) : nullptr; // (the knot's row of the reference path)
 
   double xnext[NX], cost = 0.0;
   KnotDiff<NJ, NU> kd;
@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(64) quasi_static_kernel(KArgs a, int maxiter, 
   const size_t tb = (size_t)t * B + b;
   const DevDesc &D = *a.desc;
   const DevModel &dm = D.models[node_model_at(a, t)];
-  const double *fref = a.frame_ref ? a.frame_ref + 12 * (size_t)b : nullptr;
+  const double *fref = a.frame_ref ? a.frame_ref + 12 * ((size_t)min(a.ref_row0 + t, a.ref_last) * B + b) : nullptr; // (the knot's row of the reference path)
   const typename CH::Consts cc(D);
   ModelRegs<NJ, NU> mr;
   mr.template load_for<TP>(dm, D, b, B);

@@ -50,6 +50,14 @@ struct KArgs {
   int32_t seg_t0, seg_t1;
   int32_t pipeline; // forward pass in two launches: the trial costs of the first half of the horizon run in the launch that rolls
                     // out the second half (rollout_and_cost_kernel; planar 2-joint chains).  0: off, 1 or 2: two segments (default), 3, 4: more (measured: no better)
+  // frame_ref is a path [ref_last + 1][B][12]: knot t of trajectory b reads row min(ref_row0 + t, ref_last), at
+  // frame_ref + 12 ((size_t)row B + b).  The create-time table is a path of one row (0, 0); aslr_set_reference_path puts the
+  // caller's buffer here and aslr_mpc_run advances ref_row0 by one per control step, on the host.  The knot is block-uniform
+  // wherever the address is formed (it comes from blockIdx), so the row offset is scalar arithmetic on kernel arguments, and
+  // a wave's 64 trajectories read one contiguous stretch of the row.  The expression is written out at its three sites
+  // (calc_kernel, quasi_static_kernel, trial_cost_body): behind a helper that takes the argument block by reference the
+  // trial-cost kernels kept their control vector in scratch memory (32 - 128 bytes per lane where there was none)
+  int32_t ref_row0, ref_last;
 };
 
 // -DASLR_EXP_STAMP (tools/stamp_gaps.py): every kernel of an iteration records when its first wave started and its last one

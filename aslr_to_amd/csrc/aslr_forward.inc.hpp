@@ -211,7 +211,7 @@ ASLR_DEV void trial_cost_body(const KArgs &a, const SolverDev &sp, int vbx, int 
   }
   const DevDesc &D = *a.desc;
   const DevModel &dm = D.models[node_model_at(a, t)];
-  const double *fref = a.frame_ref ? a.frame_ref + 12 * (size_t)b : nullptr;
+  const double *fref = a.frame_ref ? a.frame_ref + 12 * ((size_t)min(a.ref_row0 + t, a.ref_last) * B + b) : nullptr; // (the knot's row of the reference path)
   const typename CH::Consts cc(D);
   ModelRegs<NJ, NU> mr;
   mr.load(dm);

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .lowering import lower_problem, lower_traj_params
+from .lowering import lower_problem, lower_reference_path, lower_traj_params
 
 
 def _torch():
@@ -21,7 +21,7 @@ def _torch():
 class MpcResult(object):
     """What Engine.mpc_run returns: batch-major device tensors, views of the time-major arrays the kernels wrote --
     xs_closed [B, n+1, nx], us_closed [B, n, nu_user], and per step's solve iters, status (int32), cost, stop, x_reg,
-    step [B, n]."""
+    step [B, n]; reference_row (int): the row of the reference path knot 0 reads after the run (0 without a path)."""
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
@@ -52,8 +52,37 @@ class Engine(object):
                                                     nbytes, self._stream(), C.byref(self.handle)),
                        "aslr_problem_create")
         self._views = {}
+        self._ref_path = None
         if getattr(lowered, "traj_params", None):
             self.upload_traj_params(lowered.traj_params)
+        if getattr(lowered, "ref_path", None) is not None:
+            self.upload_reference_path(*lowered.ref_path)
+
+    def set_reference_path(self, path, row0=0):
+        """Time-varying reference placements of this shard (aslr_set_reference_path): path [B, N, 12] (row-major R, p; host
+        or lists of SE3) or None = back to the create-time references; knot t reads row min(row0 + t, N - 1)."""
+        self.upload_reference_path(None if path is None else lower_reference_path(self.low.desc, path, row0), row0)
+
+    def upload_reference_path(self, path_tm, row0=0):
+        """path_tm: what lower_reference_path returned ([N, B, 12], time-major, validated) or a device tensor of that
+        shape, or None.  The engine keeps the tensor alive while it is set (the library reads it where it lies)."""
+        torch = _torch()
+        if path_tm is None:
+            self._call("aslr_set_reference_path", None, 0, 0, self._stream())
+            self._ref_path = None
+            return
+        with torch.cuda.device(self.device):
+            t = torch.as_tensor(path_tm, dtype=torch.float64, device=self.device).contiguous()
+        if t.dim() != 3 or t.shape[1] != self.B or t.shape[2] != 12:
+            raise ValueError("the time-major reference path must have shape [n_rows, B=%d, 12]" % self.B)
+        self._call("aslr_set_reference_path", C.c_void_p(t.data_ptr()), int(t.shape[0]), int(row0), self._stream())
+        self._ref_path = t  # (only once the library took it: a declined path leaves the earlier one set and alive)
+
+    @property
+    def reference_row(self):
+        n = C.c_int32(0)
+        self._call("aslr_reference_row", C.byref(n))
+        return n.value
 
     def set_trajectory_params(self, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
         """Per-trajectory diagonals of K and B ([B, nj]) and control boxes ([B, nu], or the models' own narrower nu:
@@ -350,7 +379,9 @@ class Engine(object):
         as it was set, every later step iters_per_step from the shifted plan; between two solves the first control is
         applied to the plant (node 0's model, the trajectory's parameters), `disturbance` [B, n_steps, nx] (host or
         device, optional) is added to its next state and the plan moves one knot down.  One ABI call, no host round
-        trip per step.  -> MpcResult; XS / US are left with the last shifted plan, X0 with the last plant state."""
+        trip per step.  With a reference path set the window slides along it, one row per step, and the handle's
+        reference_row has grown by n_steps afterwards.  -> MpcResult; XS / US are left with the last shifted plan, X0 with
+        the last plant state."""
         torch = _torch()
         n = int(n_steps)
         with torch.cuda.device(self.device):
@@ -372,7 +403,8 @@ class Engine(object):
         self._call("aslr_mpc_run", C.byref(sp), C.byref(mpc), self._stream())
         torch.cuda.synchronize(self.device)  # (the time-major disturbance copy dies on return)
         return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
-                         status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t())
+                         status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t(),
+                         reference_row=self.reference_row)
 
     def traj_f(self, row):
         return self.region(_abi.R_TRAJ_F)[row]

@@ -17,12 +17,37 @@ class LoweredProblem(object):
         self.desc, self.node_model, self.x0, self.frame_ref = desc, node_model, x0, frame_ref
         # per-trajectory parameter table: dict of the given fields (device-sized, see lower_traj_params), or None
         self.traj_params = traj_params
+        # time-varying reference placements: (path [N, B, 12] time-major, row0) as lower_reference_path made it, or None
+        self.ref_path = None
         self.nj, self.nx, self.nu, self.dam = nj, nx, nu, dam
         # nu: control size on the device; nu_user: the models' own nu (smaller for a pendulum actuation with one motor
         # command: the lowered controls are padded, models._DifferentialBase.lower)
         self.nu_user = nu if nu_user is None else nu_user
         self.B, self.T = desc.B, desc.T
         self.rec = _abi.record_len(nx, nu)
+
+
+def lower_reference_path(desc, path, row0=0):
+    """Validate a time-varying reference path against a lowered description (the checks aslr_set_reference_path repeats
+    on its side, with its messages) and bring it to the device's layout: path [B, N, 12] (row-major R, p) or B lists of N
+    SE3 -> C-contiguous float64 [N, B, 12], time-major."""
+    B = desc.B
+    if len(path) and hasattr(path[0], "__len__") and len(path[0]) and hasattr(path[0][0], "as12"):
+        path = [[f.as12() for f in row] for row in path]
+    a = np.array(path, dtype=np.float64)
+    if a.ndim != 3 or a.shape[0] != B or a.shape[2] != 12:
+        raise ValueError("frame_ref_path must have shape [B=%d, n_rows, 12], got %r" % (B, a.shape))
+    n_rows = a.shape[1]
+    if n_rows < 1:
+        raise ValueError("n_rows must be >= 1")
+    if not np.all(np.isfinite(a)):
+        raise ValueError("frame_ref_path entries must be finite")
+    if not 0 <= int(row0) < n_rows:
+        raise ValueError("row0 must lie in [0, n_rows)")
+    if not any(desc.models[i].costs[c].type == _abi.COST_FRAME_PLACEMENT
+               for i in range(desc.nmodels) for c in range(desc.models[i].ncosts)):
+        raise ValueError("no model of the problem has a frame-placement cost")
+    return np.ascontiguousarray(a.transpose(1, 0, 2))
 
 
 TRAJ_PARAM_FIELDS = ("stiffness", "motor_inertia", "u_lb", "u_ub")

@@ -261,9 +261,37 @@ def constant_traj_params(sc):
     return tp
 
 
+# Seeded reference paths (aslr_set_reference_path): via-points that approach the scenario's own target.
+def reference_via_points(sc, seed=11, rows=4, step=(0.01, -0.008, 0.0), jitter=0.004):
+    """-> [B, rows, 12]: row i of trajectory b is the scenario's own frame_refs[b] with its translation moved by
+    (i - (rows - 1)) * step + U(-jitter, jitter) * (1, 1, 0); the draws come from default_rng(seed), trajectory by
+    trajectory, row by row, x then y.  The last row is the scenario's target up to the jitter."""
+    refs = np.asarray(sc["frame_refs"], dtype=np.float64).reshape(-1, 12)
+    B = refs.shape[0]
+    noise = np.random.default_rng(seed).uniform(-jitter, jitter, (B, rows, 2))
+    via = np.repeat(refs[:, None, :], rows, axis=1)
+    for i in range(rows):
+        via[:, i, 9:] += (i - (rows - 1)) * np.asarray(step, dtype=np.float64)
+        via[:, i, 9:11] += noise[:, i]
+    return via
+
+
+def hold_via_points(via, T):
+    """[B, 4, 12] via-points -> the path [B, T + 1, 12] that holds row 0 on the knots [0, T/3), row 1 on [T/3, 2T/3), row 2 on
+    [2T/3, T) and row 3 on the terminal node: piecewise constant, so the same problem can be written with four action
+    models."""
+    via = np.asarray(via, dtype=np.float64)
+    seg = np.searchsorted([T // 3, 2 * T // 3, T], np.arange(T + 1), side="right")
+    return np.ascontiguousarray(via[:, seg])
+
+
 def lower(sc):
-    from .lowering import lower_problem
-    return lower_problem(sc["x0"], sc["running"], sc["terminal"], sc["frame_refs"], **(sc.get("traj_params") or {}))
+    from .lowering import lower_problem, lower_reference_path
+    low = lower_problem(sc["x0"], sc["running"], sc["terminal"], sc["frame_refs"], **(sc.get("traj_params") or {}))
+    if sc.get("ref_path") is not None:
+        row0 = int(sc.get("ref_row0", 0))
+        low.ref_path = (lower_reference_path(low.desc, sc["ref_path"], row0), row0)
+    return low
 
 
 def solver_params(sc, **overrides):

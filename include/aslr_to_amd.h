@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define ASLR_ABI_VERSION 4
+#define ASLR_ABI_VERSION 5
 
 #define ASLR_MAX_NJ     7   /* link-side DoF (2-DoF arm, 7-DoF arm)          */
 #define ASLR_MAX_NX     28  /* 4 * ASLR_MAX_NJ                                */
@@ -306,6 +306,26 @@ typedef struct aslr_traj_params {
  * the handle is then left as it was. */
 int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, void *stream);
 
+/* Time-varying reference placements: a reaching motion through via-points, an end-effector path
+ * (ResidualModelFramePlacementASR takes ONE placement, python/aslr_to/residual_frame_placement.py:7-10; a script that tracks
+ * a path builds one action model per knot -- here at most ASLR_MAX_MODELS models exist, and the path is how references vary).
+ * `path` is a DEVICE buffer [n_rows][B][12], time-major like the workspace, each entry R row-major then p as aslr_cost_t.ref.
+ * The caller owns it and keeps it alive while it is set (the rule of aslr_set_iteration_log); nothing is copied, the workspace
+ * is not re-carved.  NULL clears it: back to the references the handle was created with.
+ * While a path is set, knot t of trajectory b (t = 0 .. T, the terminal node included) takes row min(row0 + t, n_rows - 1) as
+ * the reference of EVERY ASLR_COST_FRAME_PLACEMENT term of that node's model, overriding both the models' own `ref` and the
+ * create-time frame_ref table.  Rows past the end hold the last row: a path may be shorter than the horizon, and an MPC run
+ * may go past its end.  Honoured by aslr_calc, aslr_calc_diff, aslr_forward_pass, aslr_iterate*, aslr_solve and aslr_mpc_run
+ * (which advances row0, see there), sub-shards and the per-trajectory parameter table included.  aslr_dam_eval /
+ * aslr_dam_residuals keep trajectory 0's create-time reference (arbitrary points, not knots); aslr_quasi_static reads no cost;
+ * aslr_solve_pool declines a handle with a path set (ASLR_E_INVALID).  The opt-in closed-form planar reach residual
+ * (ASLR_PLANAR_REACH) is off while a path is set: it is validated for the create-time references only.
+ * ASLR_E_INVALID with a message (aslr_last_error), the handle left as it was: n_rows < 1; row0 < 0 or row0 >= n_rows; no model
+ * of the problem has a frame-placement cost.  `stream` is not used today (no upload); pass the stream the solves run on. */
+int aslr_set_reference_path(aslr_problem_t *p, const double *path, int32_t n_rows, int32_t row0, void *stream);
+/* the row knot 0 reads (0 without a path): what aslr_set_reference_path set, plus the control steps of every aslr_mpc_run since */
+int aslr_reference_row(const aslr_problem_t *p, int32_t *row0);
+
 /* ---- the hot path ---------------------------------------------------------------------- */
 /* ShootingProblem.calc(xs, us): IntegratedActionModelEulerASR.calc on every node
  * (python/aslr_to/integrated_action.py:13-26 -> free_fwddyn_asr.py:20-56 / free_fwddyn_vsa.py:20-57).
@@ -344,7 +364,8 @@ int aslr_solve(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t poll_e
  * Side effects on the handle: while the pool runs, the slots' X0 / FRAME_REF columns hold the pool's problems; the
  * handle's own are kept in POOL_SAVE and put back before the call returns, so a later aslr_solve / rollout sees the
  * problems the handle was created with.  XS / US / the per-trajectory state are left with the last slot contents
- * (every solver entry point re-initialises them from its own arguments).  Pool targets always take the general SE(3)
+ * (every solver entry point re-initialises them from its own arguments).  A handle with a reference path set
+ * (aslr_set_reference_path) is declined, like one with a parameter table.  Pool targets always take the general SE(3)
  * log map (the opt-in closed-form reach residual is validated for the create-time references only).  The call fails
  * (ASLR_E_INVALID, aslr_last_error) if fewer than P problems were flushed within its iteration bound. */
 typedef struct aslr_pool {
@@ -382,9 +403,14 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
  * x0 is NOT restored: the loop has moved it).  XNEXT[0] / COST[0] hold the last plant evaluation.
  * DEVICE pointers owned by the caller, time-major like the workspace.  Everything is enqueued on `stream`; the host
  * never waits inside the call.  Sub-shards (aslr_set_subshards) apply to the iterations of a step.
+ * With a reference path (aslr_set_reference_path) the window slides along it: control step s plans against rows
+ * row0 + s + t (clamped to the last row), and its plant step evaluates knot 0 against row row0 + s.  The offset is a host
+ * integer carried by value in the kernel arguments and advanced once per step: nothing is shifted or copied on the device.
+ * After the run the handle's row0 has grown by n_steps (like X0, it is NOT restored: the loop has moved it);
+ * aslr_reference_row reads it, aslr_set_reference_path repositions it.
  * ASLR_E_INVALID (aslr_last_error): NULL or non-positive arguments; running knots that do not all use one action model
- * (the terminal model may differ: a receding horizon over a time-varying stack needs per-knot references); an iteration
- * log that is set (every step would overwrite it); the solver / size combinations the solver entry points decline. */
+ * (the terminal model may differ; references that vary along the horizon are given as a path, not as a stack of models); an
+ * iteration log that is set (every step would overwrite it); the solver / size combinations the solver entry points decline. */
 typedef struct aslr_mpc {
   int32_t n_steps;            /* control steps, >= 1                                                            */
   int32_t first_maxiter;      /* iterations of step 0, >= 1                                                     */
