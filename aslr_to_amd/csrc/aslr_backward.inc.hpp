@@ -893,8 +893,7 @@ int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, cons
     if constexpr (SizeTraits<NJ, DAM>::reg_column) {
       return hs == 2 ? launch_backward_t<NX, NU, 2, TP>(k, sd, lim, st) : launch_backward_t<NX, NU, 1, TP>(k, sd, lim, st);
     } else { // VSA: the block kernel only (wave-cooperative gains / box QP, aslr_wave_gains.hpp)
-      snprintf(err_buf(), kErrLen, "backward: the register-column kernel (ASLR_BWD_HS=%d) is not built for (nx=%d, nu=%d)", hs, NX, NU);
-      return ASLR_E_INVALID;
+      return fail(ASLR_E_INVALID, "launch_backward: the register-column kernel (ASLR_BWD_HS=%d) is not built for (nx=%d, nu=%d)", hs, NX, NU);
     }
   }
 }

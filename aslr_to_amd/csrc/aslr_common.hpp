@@ -12,17 +12,18 @@
 
 namespace aslr {
 
-char *err_buf();            // thread-local error string (aslr_last_error)
+// The one way a call fails: writes the thread's error string (aslr_last_error; printf-style) and returns `code`.  Every
+// non-OK return of the C ABI comes from here.  A refused argument or condition is reported under the name of the entry
+// point that was called; a failed HIP call (HIP_TRY) under the name of the function it sits in, which may be an internal
+// launcher, with the call, HIP's error string, file and line.
+int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 constexpr int kErrLen = 512;
 
-#define HIP_TRY(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t e_ = (expr);                                                                         \
-    if (e_ != hipSuccess) {                                                                         \
-      snprintf(aslr::err_buf(), aslr::kErrLen, "%s -> %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-               __LINE__);                                                                           \
-      return ASLR_E_HIP;                                                                            \
-    }                                                                                               \
+#define HIP_TRY(expr)                                                                                                  \
+  do {                                                                                                                 \
+    hipError_t e_ = (expr);                                                                                            \
+    if (e_ != hipSuccess)                                                                                              \
+      return aslr::fail(ASLR_E_HIP, "%s: %s -> %s (%s:%d)", __func__, #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
 constexpr int rec_len_c(int nx, int nu) { return (2 * nx * nx + 2 * nx * nu + nu * nu + nx + nu + 15) / 16 * 16; }

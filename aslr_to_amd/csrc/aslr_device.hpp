@@ -280,162 +280,16 @@ ASLR_DEV SV inertia_mul(double mass, V3 c, const M3 &I, SV m) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// SE(3) log map and its Jacobian (Pinocchio 2.6 explog: acos on the trace, branch near pi)
+// constants of the SE(3) log map and its Jacobian (log6_shared / jlog6_shared below)
 // ---------------------------------------------------------------------------------------------
 constexpr double kTaylorPrec = 1.220703125e-04; // eps^(1/4)
 constexpr double kPi = 3.14159265358979323846;
 
-ASLR_DEV double log3(const M3 &R, V3 &w) {
-  double tr = R.a[0] + R.a[4] + R.a[8], theta;
-  if (tr >= 3.0) { tr = 3.0; theta = 0.0; }
-  else if (tr <= -1.0) { tr = -1.0; theta = kPi; }
-  else theta = acos((tr - 1.0) / 2.0);
-  if (theta >= kPi - 1e-2) {
-    const double cphi = -(tr - 1.0) / 2.0;
-    const double beta = theta * theta / (1.0 + cphi);
-    const double t0 = (R.a[0] + cphi) * beta, t1 = (R.a[4] + cphi) * beta, t2 = (R.a[8] + cphi) * beta;
-    w.x = (R.a[7] > R.a[5] ? 1.0 : -1.0) * (t0 > 0.0 ? sqrt(t0) : 0.0);
-    w.y = (R.a[2] > R.a[6] ? 1.0 : -1.0) * (t1 > 0.0 ? sqrt(t1) : 0.0);
-    w.z = (R.a[3] > R.a[1] ? 1.0 : -1.0) * (t2 > 0.0 ? sqrt(t2) : 0.0);
-  } else {
-    const double t = ((theta > kTaylorPrec) ? theta / sin(theta) : 1.0) / 2.0;
-    w.x = t * (R.a[7] - R.a[5]);
-    w.y = t * (R.a[2] - R.a[6]);
-    w.z = t * (R.a[3] - R.a[1]);
-  }
-  return theta;
-}
-
-// r = log6(M).vector = [v; w] (residual_frame_placement.py:14-15); also returns theta and w.
-ASLR_DEV void log6(const SE3d &M, double *r, double &t, V3 &w) {
-  t = log3(M.R, w);
-  const double t2 = t * t;
-  double alpha, beta;
-  if (t < kTaylorPrec) {
-    alpha = 1.0 - t2 / 12.0 - t2 * t2 / 720.0;
-    beta = 1.0 / 12.0 + t2 / 720.0;
-  } else {
-    double st, ct;
-    sincos(t, &st, &ct);
-    alpha = t * st / (2.0 * (1.0 - ct));
-    beta = 1.0 / t2 - st / (2.0 * t * (1.0 - ct));
-  }
-  const V3 wxp = cross(w, M.p);
-  const double wp = dot(w, M.p);
-  r[0] = alpha * M.p.x - 0.5 * wxp.x + beta * wp * w.x;
-  r[1] = alpha * M.p.y - 0.5 * wxp.y + beta * wp * w.y;
-  r[2] = alpha * M.p.z - 0.5 * wxp.z + beta * wp * w.z;
-  r[3] = w.x; r[4] = w.y; r[5] = w.z;
-}
-
-ASLR_DEV M3 jlog3(double theta, V3 w) {
-  const double t2 = theta * theta;
-  double alpha, diag;
-  if (theta < kTaylorPrec) {
-    alpha = 1.0 / 12.0 + t2 / 720.0;
-    diag = 0.5 * (2.0 - t2 / 6.0);
-  } else {
-    double st, ct;
-    sincos(theta, &st, &ct);
-    const double st_1mct = st / (1.0 - ct);
-    alpha = 1.0 / t2 - st_1mct / (2.0 * theta);
-    diag = 0.5 * (theta * st_1mct);
-  }
-  const double wv[3] = {w.x, w.y, w.z};
-  M3 J;
-  ASLR_UNROLL for (int i = 0; i < 3; ++i)
-    ASLR_UNROLL for (int j = 0; j < 3; ++j) J.a[3 * i + j] = alpha * wv[i] * wv[j];
-  J.a[0] += diag; J.a[4] += diag; J.a[8] += diag;
-  J.a[1] -= 0.5 * w.z; J.a[2] += 0.5 * w.y;
-  J.a[3] += 0.5 * w.z; J.a[5] -= 0.5 * w.x;
-  J.a[6] -= 0.5 * w.y; J.a[7] += 0.5 * w.x;
-  return J;
-}
-
-// Jlog6(M) = [[A, B], [0, A]] (residual_frame_placement.py:19); theta, w from log6
-ASLR_DEV void jlog6(const SE3d &M, double t, V3 w, M3 &A, M3 &Bm) {
-  const double t2 = t * t;
-  double beta, bdot;
-  if (t < kTaylorPrec) {
-    beta = 1.0 / 12.0 + t2 / 720.0;
-    bdot = 1.0 / 360.0;
-  } else {
-    const double tinv = 1.0 / t, t2inv = tinv * tinv;
-    double st, ct;
-    sincos(t, &st, &ct);
-    const double inv_2_2ct = 1.0 / (2.0 * (1.0 - ct));
-    beta = t2inv - st * tinv * inv_2_2ct;
-    bdot = -2.0 * t2inv * t2inv + (1.0 + st * tinv) * t2inv * inv_2_2ct;
-  }
-  A = jlog3(t, w);
-  const V3 p = M.p;
-  const double wTp = dot(w, p);
-  const V3 v3t = (bdot * wTp) * w - (t2 * bdot + 2.0 * beta) * p;
-  const double vv[3] = {v3t.x, v3t.y, v3t.z}, wv[3] = {w.x, w.y, w.z}, pv[3] = {p.x, p.y, p.z};
-  M3 Cm;
-  ASLR_UNROLL for (int i = 0; i < 3; ++i)
-    ASLR_UNROLL for (int j = 0; j < 3; ++j) Cm.a[3 * i + j] = vv[i] * wv[j] + beta * wv[i] * pv[j];
-  Cm.a[0] += wTp * beta; Cm.a[4] += wTp * beta; Cm.a[8] += wTp * beta;
-  Cm.a[1] -= 0.5 * p.z; Cm.a[2] += 0.5 * p.y;
-  Cm.a[3] += 0.5 * p.z; Cm.a[5] -= 0.5 * p.x;
-  Cm.a[6] -= 0.5 * p.y; Cm.a[7] += 0.5 * p.x;
-  Bm = mul(Cm, A);
-}
-
 // ---------------------------------------------------------------------------------------------
 // small dense helpers on register arrays
 // ---------------------------------------------------------------------------------------------
-// Cholesky LL^T in place (lower); returns true on a non-positive pivot
-template <int N>
-ASLR_DEV bool chol(double (&A)[N][N]) {
-  bool bad = false;
-  ASLR_UNROLL for (int j = 0; j < N; ++j) {
-    double d = A[j][j];
-    ASLR_UNROLL for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
-    if (!(d > 0.0)) bad = true;
-    d = sqrt(d);
-    A[j][j] = d;
-    ASLR_UNROLL for (int i = j + 1; i < N; ++i) {
-      double s = A[i][j];
-      ASLR_UNROLL for (int k = 0; k < j; ++k) s -= A[i][k] * A[j][k];
-      A[i][j] = s / d;
-    }
-  }
-  return bad;
-}
-template <int N>
-ASLR_DEV void chol_solve(const double (&L)[N][N], double (&b)[N]) {
-  ASLR_UNROLL for (int i = 0; i < N; ++i) {
-    double s = b[i];
-    ASLR_UNROLL for (int k = 0; k < i; ++k) s -= L[i][k] * b[k];
-    b[i] = s / L[i][i];
-  }
-  ASLR_UNROLL for (int i = N - 1; i >= 0; --i) {
-    double s = b[i];
-    ASLR_UNROLL for (int k = i + 1; k < N; ++k) s -= L[k][i] * b[k];
-    b[i] = s / L[i][i];
-  }
-}
-// Cholesky with reciprocal pivots: L (lower, in place) and rinv[i] = 1 / L[i][i]; true on a
-// non-positive pivot.  The triangular solves below multiply by rinv instead of dividing.
-template <int N>
-ASLR_DEV bool chol_r(double (&A)[N][N], double (&rinv)[N]) {
-  bool bad = false;
-  ASLR_UNROLL for (int j = 0; j < N; ++j) {
-    double d = A[j][j];
-    ASLR_UNROLL for (int k = 0; k < j; ++k) d -= A[j][k] * A[j][k];
-    if (!(d > 0.0)) bad = true;
-    d = sqrt(d);
-    A[j][j] = d;
-    rinv[j] = 1.0 / d;
-    ASLR_UNROLL for (int i = j + 1; i < N; ++i) {
-      double s = A[i][j];
-      ASLR_UNROLL for (int k = 0; k < j; ++k) s -= A[i][k] * A[j][k];
-      A[i][j] = s * rinv[j];
-    }
-  }
-  return bad;
-}
+// L L^T z = b in place, with the reciprocal pivots rinv[i] = 1 / L[i][i] of the factorisation (chol_rs,
+// aslr_backward.inc.hpp): the triangular solves multiply by rinv instead of dividing
 template <int N>
 ASLR_DEV void chol_solve_r(const double (&L)[N][N], const double (&rinv)[N], double (&b)[N]) {
   ASLR_UNROLL for (int i = 0; i < N; ++i) {
@@ -447,20 +301,6 @@ ASLR_DEV void chol_solve_r(const double (&L)[N][N], const double (&rinv)[N], dou
     double s = b[i];
     ASLR_UNROLL for (int k = i + 1; k < N; ++k) s -= L[k][i] * b[k];
     b[i] = s * rinv[i];
-  }
-}
-
-template <int N>
-ASLR_DEV void spd_inverse(const double (&A)[N][N], double (&Ainv)[N][N]) {
-  double L[N][N];
-  ASLR_UNROLL for (int i = 0; i < N; ++i)
-    ASLR_UNROLL for (int j = 0; j < N; ++j) L[i][j] = A[i][j];
-  chol<N>(L);
-  ASLR_UNROLL for (int j = 0; j < N; ++j) {
-    double e[N];
-    ASLR_UNROLL for (int i = 0; i < N; ++i) e[i] = (i == j) ? 1.0 : 0.0;
-    chol_solve<N>(L, e);
-    ASLR_UNROLL for (int i = 0; i < N; ++i) Ainv[i][j] = e[i];
   }
 }
 
@@ -859,7 +699,7 @@ struct ChainPlanar {
   // identity rotation at pref: the relative rotation is Rz(psi) with psi = sum_{i <= fj} (phi_i + q_i) + phiF wrapped
   // to (-pi, pi], so the angular part is w = (0, 0, psi) and, with p = oMf.p - pref and t = |psi|,
   //   r = [alpha p_x + psi p_y / 2, alpha p_y - psi p_x / 2, p_z, 0, 0, psi],   alpha = t sin t / (2 (1 - cos t)):
-  // log6()'s formulas with w x p = psi (-p_y, p_x, 0); on the z component alpha + beta t^2 = 1.  No acos, no 3-D
+  // log6_shared()'s formulas with w x p = psi (-p_y, p_x, 0); on the z component alpha + beta t^2 = 1.  No acos, no 3-D
   // products, one division -- a cost-only evaluation is otherwise dominated by the general SE(3) log.
   ASLR_DEV static void reach_residual(const Consts &cc, const double *q, int fj, const double *Fp, double cF, double sF,
                                       double phiF, const double *pref, double (&r)[6]) {
@@ -926,14 +766,17 @@ template <int NJ, int DAM> struct ModelDims {
   static constexpr int nu = DAM == ASLR_DAM_VSA ? 2 * NJ : NJ;
 };
 
-// SE(3) log of the frame-placement residual with the sin/cos of its angle shared between
-// log6, Jlog3 and Jlog6 (same formulas as log6()/jlog6() above).
+// SE(3) log of the frame-placement residual and its Jacobian, as Pinocchio 2.6 explog computes them (acos on the trace,
+// a branch of its own near pi, Taylor series below kTaylorPrec), with the sin / cos of the angle shared between log6,
+// Jlog3 and Jlog6.  log6_shared: r = log6(M).vector = [v; w] (residual_frame_placement.py:14-15), with theta and w kept
+// for the Jacobian; jlog6_shared: Jlog6(M) = [[A, B], [0, A]] (residual_frame_placement.py:19), A = Jlog3.
 struct Log6 {
   double r[6], t, st, ct;
   V3 w;
 };
 ASLR_DEV void log6_shared(const SE3d &M, Log6 &o) {
-  // log3 (same branches as log3() above) with sin(theta), cos(theta) taken from the trace:
+  // log3 (theta = 0 at tr >= 3, pi at tr <= -1; near pi the axis from the diagonal, signs from the off-diagonal
+  // differences; else theta / (2 sin theta) times those differences) with sin(theta), cos(theta) taken from the trace:
   // cos(theta) = (tr - 1) / 2 and sin(theta) = sqrt((1 - c)(1 + c)) for theta = acos(c) in [0, pi]
   const M3 &R = M.R;
   double tr = R.a[0] + R.a[4] + R.a[8], theta;

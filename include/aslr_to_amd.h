@@ -13,7 +13,15 @@
  *   - plain C types only: int32_t, double, raw pointers; no torch / C++ types;
  *   - all arithmetic is IEEE float64 (dtype "f64");
  *   - every function returns int: 0 = ok, <0 = error (see ASLR_E_*); no exceptions cross
- *     the ABI.  Numerical events (Cholesky failure, NaN, reg at max, not converged) are
+ *     the ABI.  After a non-OK return -- the negative returns of aslr_workspace_bytes and
+ *     aslr_residual_len included -- aslr_last_error() describes THAT call on this thread.  A
+ *     refusal (ASLR_E_INVALID, ASLR_E_NODEVICE, ASLR_E_WORKSPACE) starts with the name of the
+ *     entry point that was called and says which argument or condition it refused.  A failed
+ *     HIP runtime call (ASLR_E_HIP) starts with the name of the library function in which it
+ *     failed -- the entry point or an internal launcher -- followed by the HIP call, HIP's
+ *     error string and the source line.  After ASLR_OK the contents are unspecified (the
+ *     string is not cleared).
+ *     Numerical events (Cholesky failure, NaN, reg at max, not converged) are
  *     NOT errors: they are per-trajectory status bits (ASLR_ST_*), mirroring Crocoddyl's
  *     catch-and-regularise behaviour and its `solve -> bool`;
  *   - the caller owns every buffer.  The library owns only the opaque handle; the device
@@ -491,7 +499,8 @@ int aslr_set_iteration_log(aslr_problem_t *p, double *log, int32_t capacity);
  * iterations used. */
 int aslr_quasi_static(aslr_problem_t *p, int32_t maxiter, double tol, int32_t *iters_dev, void *stream);
 
-/* last HIP error string of this thread (static storage) */
+/* what the last failing call of this thread reported (thread-local static storage; the contract is under
+ * "Conventions" at the top: defined after a non-OK return, unspecified after ASLR_OK) */
 const char *aslr_last_error(void);
 
 #ifdef __cplusplus

@@ -840,3 +840,38 @@ def test_pool_solve_leaves_the_handle_and_its_iteration_log_as_they_were():
     assert torch.equal(iters, fresh.traj_i(_abi.TI_ITER)) and torch.equal(e.traj_i(_abi.TI_STATUS), fresh.traj_i(_abi.TI_STATUS))
     ran = torch.arange(maxiter, device=log.device)[:, None] < iters[None, :]    # [iteration, trajectory]
     assert int(iters.min()) >= 1 and torch.equal(~torch.isnan(log[:, _abi.LOG_COST]), ran)
+
+
+def test_refusals_name_their_own_function_and_leave_no_state_behind():
+    """After a non-OK return aslr_last_error() describes that call: four refusals in a row on one handle, each reported
+    under its own function's name and without the text of the one before.  None of them leaves anything on the handle:
+    a solve on it afterwards equals the same solve on a fresh handle, bit for bit."""
+    import ctypes as C
+    import torch
+    sc = scenarios.two_dof_vsa_boxddp(B=2, T=3)
+    low, sp = scenarios.lower(sc), scenarios.solver_params(sc, maxiter=20)
+    e = gc.engine(low)
+    path = torch.zeros((1, 2, 12), dtype=torch.float64, device=e.device)
+    x = torch.zeros((1, low.nx), dtype=torch.float64, device=e.device)
+    oMf = torch.empty((1, 12), dtype=torch.float64, device=e.device)
+    eye, zero3 = (C.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1), (C.c_double * 3)()
+    pool, iters = _abi.Pool(P=0), C.c_int32()
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    previous = None
+    for name, args in (("aslr_set_subshards", (0,)),
+                       ("aslr_set_reference_path", (ptr(path), 0, 0, e._stream())),
+                       ("aslr_frame_placement", (low.nj, eye, zero3, 1, ptr(x), low.nx, ptr(oMf), e._stream())),
+                       ("aslr_solve_pool", (C.byref(sp), C.byref(pool), 4, 16, e._stream(), C.byref(iters)))):
+        assert getattr(e.lib, name)(e.handle, *args) == _abi.E_INVALID, name
+        msg = e.lib.aslr_last_error().decode()
+        assert msg.startswith(name + ":"), msg
+        assert previous is None or previous not in msg, msg
+        previous = msg
+    assert e.reference_row == 0
+    fresh = gc.engine(low)
+    for h in (e, fresh):
+        h.set_candidate(None, None)
+        h.solve(sp, poll_every=4)
+    gc.sync()
+    for rid in (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_F, _abi.R_TRAJ_I):
+        gc.same_bits(e.region(rid), fresh.region(rid), "region %d after the refused calls" % rid)
