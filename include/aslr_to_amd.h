@@ -345,7 +345,16 @@ int aslr_calc(aslr_problem_t *p, void *stream);
 int aslr_calc_diff(aslr_problem_t *p, void *stream);
 /* SolverDDP.backwardPass / SolverBoxDDP.computeGains at regularisation
  * TRAJ_F[XREG] with gaps GAPS (used when TRAJ_I[FEASIBLE] == 0).  Reads DERIV, GAPS, US, KFF;
- * writes KGAIN, KFF, QU, VX, VXX, TRAJ_F[D1,D2,STOP,DG,DQ], TRAJ_I[STATUS]. */
+ * writes KGAIN, KFF, QU, VX, VXX, TRAJ_F[D1,D2,STOP,DG,DQ], TRAJ_I[STATUS].
+ * A trajectory whose sweep fails ("backward_error": a Cholesky pivot <= 0, a box QP that cannot factor its free block, or
+ * NaN / Inf / >= 1e30 in Vx, Vxx) gets ASLR_ST_BACKWARD_ERR or-ed into TRAJ_I[STATUS]; the stand-alone pass does not
+ * retry.  Its TRAJ_F[D1,D2,STOP,DG,DQ,XREG] stay as they were.  Of KGAIN, KFF, QU, VX, VXX the rows of the knots ABOVE the
+ * failing one (VX, VXX: the terminal knot included) hold what a successful sweep writes there; the rows of the failing
+ * knot and of every knot below it stay as they were when the gains of that knot fail (when its Vx / Vxx fail the test
+ * instead, KGAIN, KFF and QU of that one knot are written as well; no test reaches that branch, it is stated from the
+ * code).  VXXF, which only SolverFDDP's sweep of an infeasible trajectory writes, follows VX: the terminal knot and the knots
+ * above the failing one.  The other trajectories of the batch are not affected,
+ * whichever wave or block they share with it.  Every backward kernel keeps to this (tests/test_gpu_mixed_waves.py). */
 int aslr_backward_pass(aslr_problem_t *p, const aslr_solver_params_t *sp, void *stream);
 /* SolverDDP/FDDP/BoxDDP.forwardPass for all ASLR_NALPHA step lengths.
  * Reads XS, US, KGAIN, KFF, GAPS; writes XS_TRY, US_TRY, COST_TRY, TRAJ_F[COST_TRY0..] (NaN for a

@@ -152,22 +152,35 @@ def check_calc_and_calc_diff(oracle, low, seed=1):
     return e
 
 
-def run_backward(e, sp, us, deriv, gaps, xreg, feasible, k0=None):
-    """The inputs in place (k0: the stored k, SolverBoxDDP's warm start; None: zero), TI_STATUS cleared,
-    aslr_backward_pass -> dict(K, k, Qu, Vx, Vxx, d1, d2, stop, status)"""
+def run_backward(e, sp, us, deriv, gaps, xreg, feasible, k0=None, prefill=None):
+    """The inputs in place (xreg, feasible: one value or one per trajectory; k0: the stored k, SolverBoxDDP's warm start;
+    None: zero), TI_STATUS cleared, aslr_backward_pass -> dict(K, k, Qu, Vx, Vxx, d1, d2, stop, status, and Vxxf, dg, dq:
+    R_VXXF, TF_DG, TF_DQ, which SolverFDDP's sweep writes -- the oracle returns dg, dq as ITS d1, d2 under that solver).
+    prefill: a float64 whose bit pattern fills the TF_D1 / TF_D2 / TF_STOP / TF_DG / TF_DQ rows and KGAIN, QU, VX, VXX,
+    VXXF -- and KFF where no k0 is given -- before the launch, so that wrote(out[name], prefill) tells which entries the
+    launch wrote."""
+    import torch
     _upload(e, US=us, DERIV=deriv, GAPS=gaps)
+    if prefill is not None:
+        for rid in (_abi.R_KGAIN, _abi.R_QU, _abi.R_VX, _abi.R_VXX, _abi.R_VXXF):
+            e.region(rid).fill_(prefill)
+        for row in (_abi.TF_D1, _abi.TF_D2, _abi.TF_STOP, _abi.TF_DG, _abi.TF_DQ):
+            e.region(_abi.R_TRAJ_F)[row].fill_(prefill)
     if k0 is None:
-        e.region(_abi.R_KFF).zero_()
+        e.region(_abi.R_KFF).fill_(0.0 if prefill is None else prefill)
     else:
         _upload(e, KFF=k0)
-    e.region(_abi.R_TRAJ_F)[_abi.TF_XREG].fill_(xreg)
+    if np.ndim(xreg):
+        e.region(_abi.R_TRAJ_F)[_abi.TF_XREG].copy_(torch.as_tensor(np.asarray(xreg, dtype=np.float64)))
+    else:
+        e.region(_abi.R_TRAJ_F)[_abi.TF_XREG].fill_(xreg)
     _set_feasible(e, feasible)
     e.region(_abi.R_TRAJ_I)[_abi.TI_STATUS].fill_(0)
     e.backward_pass(sp)
     sync()
     out = dict(K=to_np(e.region(_abi.R_KGAIN)), k=to_np(e.region(_abi.R_KFF)), Qu=to_np(e.region(_abi.R_QU)),
-               Vx=to_np(e.region(_abi.R_VX)), Vxx=to_np(e.region(_abi.R_VXX)))
-    for fld, name in ((_abi.TF_D1, "d1"), (_abi.TF_D2, "d2"), (_abi.TF_STOP, "stop")):
+               Vx=to_np(e.region(_abi.R_VX)), Vxx=to_np(e.region(_abi.R_VXX)), Vxxf=to_np(e.region(_abi.R_VXXF)))
+    for fld, name in ((_abi.TF_D1, "d1"), (_abi.TF_D2, "d2"), (_abi.TF_STOP, "stop"), (_abi.TF_DG, "dg"), (_abi.TF_DQ, "dq")):
         out[name] = to_np(e.traj_f(fld))
     out["status"] = to_np(e.traj_i(_abi.TI_STATUS))
     return out
@@ -222,6 +235,33 @@ def assert_backward_matches(out, ref, tol, fields=BACKWARD_FIELDS):
     assert (np.asarray(out["status"]) & _abi.ST_BACKWARD_ERR == 0).all(), "ST_BACKWARD_ERR is set: %s" % out["status"]
     for name in fields:
         _assert_close(name, out[name], ref[name], tol)
+
+
+def per_trajectory(a, ok):
+    """the entries that belong to the trajectories of mask ok (axis 1 of the per-knot arrays, axis 0 of d1 / d2 / stop)"""
+    a = np.asarray(a)
+    return a[ok] if a.ndim == 1 else a[:, ok]
+
+
+def assert_backward_matches_where_ok(out, ref, tol, fields=BACKWARD_FIELDS):
+    """out: run_backward's dict; ref: the oracle's backward pass of a MIXED batch: it must fail on some trajectories and
+    not on all.  ST_BACKWARD_ERR must be set on exactly the trajectories the oracle fails on; on the others every field
+    matches as in assert_backward_matches.  -> the mask of the surviving trajectories"""
+    fail = np.asarray(ref["fail"]) != 0
+    assert fail.any(), "no mixed case: the oracle's backward pass fails on no trajectory"
+    assert not fail.all(), "no mixed case: the oracle's backward pass fails on every trajectory"
+    err = (np.asarray(out["status"]) & _abi.ST_BACKWARD_ERR) != 0
+    assert err[fail].all(), "ST_BACKWARD_ERR is missing on trajectories %s the oracle fails on" % np.nonzero(fail & ~err)[0]
+    assert not err[~fail].any(), "ST_BACKWARD_ERR is set on trajectories %s the oracle does not fail on" % np.nonzero(err & ~fail)[0]
+    for name in fields:
+        _assert_close(name, per_trajectory(out[name], ~fail), per_trajectory(ref[name], ~fail), tol)
+    return ~fail
+
+
+def wrote(a, prefill):
+    """-> bool per entry: the entry no longer holds the bit pattern of run_backward's prefill"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    return a.view(np.uint64) != np.array([prefill], dtype=np.float64).view(np.uint64)[0]
 
 
 def assert_forward_matches(XT, UT, cost_try_rows, oracle_forward, tol=1e-9):

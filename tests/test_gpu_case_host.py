@@ -139,3 +139,63 @@ def test_relerr_and_owned_copies():
         assert float(src[0, 0]) == 0.0
     view = np.arange(12.0).reshape(3, 4).T           # a permuted view comes back as an array of its own too
     assert not np.shares_memory(gc.to_np(view), view)
+
+
+def _mixed(case):
+    """the oracle's result with trajectory 1 declared failed (whatever its rows hold), and a "GPU" copy that says the same"""
+    ref = dict(case["backward"], fail=np.array([0, 1, 0]))
+    out = _backward_copy(case["backward"])
+    out["status"][1] = _abi.ST_BACKWARD_ERR
+    for name in gc.BACKWARD_FIELDS:        # (a failed sweep's leftovers are not compared)
+        if out[name].ndim == 1:
+            out[name][1] = np.nan
+        else:
+            out[name][:, 1] = -7.0
+    return out, ref
+
+
+def test_mixed_backward_comparison_passes_on_a_copy_and_ignores_the_failed_trajectory(case):
+    out, ref = _mixed(case)
+    ok = gc.assert_backward_matches_where_ok(out, ref, 1e-8)
+    assert ok.tolist() == [True, False, True]
+
+
+@pytest.mark.parametrize("field", gc.BACKWARD_FIELDS)
+@pytest.mark.parametrize("b", [0, 2])
+def test_mixed_backward_comparison_fails_on_one_wrong_entry_of_a_surviving_trajectory(case, field, b):
+    out, ref = _mixed(case)
+    index = (b,) if out[field].ndim == 1 else (out[field].shape[0] - 1, b) + (0,) * (out[field].ndim - 2)
+    out[field] = _off(out[field], index)
+    with pytest.raises(AssertionError, match=r"^%s mismatch" % field):
+        gc.assert_backward_matches_where_ok(out, ref, 1e-8)
+    out[field][index] = np.nan             # (what a sentinel left behind looks like)
+    with pytest.raises(AssertionError, match=r"^%s mismatch" % field):
+        gc.assert_backward_matches_where_ok(out, ref, 1e-8)
+
+
+def test_mixed_backward_comparison_holds_the_status_bits_to_the_oracles_fail_mask(case):
+    out, ref = _mixed(case)
+    out["status"][1] = _abi.ST_CONVERGED                       # missing on the failed one
+    with pytest.raises(AssertionError, match=r"ST_BACKWARD_ERR is missing on trajectories \[1\]"):
+        gc.assert_backward_matches_where_ok(out, ref, 1e-8)
+    out, ref = _mixed(case)
+    out["status"][2] = _abi.ST_BACKWARD_ERR                    # present on a surviving one
+    with pytest.raises(AssertionError, match=r"ST_BACKWARD_ERR is set on trajectories \[2\]"):
+        gc.assert_backward_matches_where_ok(out, ref, 1e-8)
+
+
+def test_mixed_backward_comparison_refuses_a_reference_that_is_not_mixed(case):
+    out, ref = _mixed(case)
+    out["status"][:] = _abi.ST_BACKWARD_ERR
+    with pytest.raises(AssertionError, match="fails on every trajectory"):
+        gc.assert_backward_matches_where_ok(out, dict(ref, fail=np.ones(3, dtype=np.int32)), 1e-8)
+    with pytest.raises(AssertionError, match="fails on no trajectory"):
+        gc.assert_backward_matches_where_ok(_backward_copy(case["backward"]), case["backward"], 1e-8)
+
+
+def test_wrote_tells_a_prefill_from_any_other_bits():
+    import _mixed_waves as mw
+    a = np.full((2, 3), mw.SENTINEL)
+    assert np.isnan(mw.SENTINEL) and not gc.wrote(a, mw.SENTINEL).any()
+    a[0, 1], a[1, 2] = np.nan, 0.0                             # another NaN counts as written
+    assert gc.wrote(a, mw.SENTINEL).tolist() == [[False, True, False], [False, False, True]]
