@@ -164,6 +164,10 @@ EXPORTED_SYMBOLS = [
     "aslr_mpc_run", "aslr_set_reference_path", "aslr_reference_row",
 ]
 
+# what include/aslr_to_amd_sens.h declares: an extension exported from the same library, kept apart from the base set so
+# that the base header, its symbol list and ABI_VERSION stay what existing bindings check against
+EXTENSION_SYMBOLS = ["aslr_cost_sensitivity"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -239,6 +243,8 @@ def load_library():
     lib.aslr_reference_row.argtypes = [vp, C.POINTER(i32)]
     lib.aslr_set_iteration_log.restype = C.c_int
     lib.aslr_set_iteration_log.argtypes = [vp, vp, i32]
+    lib.aslr_cost_sensitivity.restype = C.c_int
+    lib.aslr_cost_sensitivity.argtypes = [vp, vp, vp, vp, vp, vp]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

@@ -212,6 +212,18 @@ class ShootingProblem(object):
         e.calc_diff()
         return self._total_cost()
 
+    def cost_sensitivity(self, xs=None, us=None):
+        """Gradients of every trajectory's cost, controls held fixed, in its own spring stiffness, motor inertia and
+        initial state (engine.SensitivityResult: stiffness [B, nj] -- None for VSA --, motor_inertia [B, nj], x0 [B, nx],
+        costate [B, T+1, nx]) at the candidate (xs, us); neither given: at the candidate the engine holds, e.g. the
+        last solution.  One calcDiff sweep and one adjoint sweep on the device.  Exact for a candidate without gaps
+        (a rollout, a feasible solution); there, at a converged solution, also the gradient of the optimal cost.  This
+        shard's trajectories only (as the other getters)."""
+        e = self.engine
+        if xs is not None or us is not None:
+            e.set_candidate(xs, us)
+        return e.cost_sensitivity()
+
     def _total_cost(self):
         c = self.engine.region(_abi.R_COST).sum(dim=0)
         return float(c[0].item()) if self.batch == 1 else c
@@ -447,6 +459,11 @@ class SolverDDP(object):
         if frame_refs is not None:
             fr = np.array([f.as12() if hasattr(f, "as12") else np.asarray(f, dtype=np.float64).reshape(12) for f in frame_refs])
         return self.problem.engine.solve_pool(x0s, fr, sp, refill_every, poll_every, init_xs, init_us)
+
+    def cost_sensitivity(self):
+        """problem.cost_sensitivity() at this solver's solution (the committed xs / us of the last solve): per
+        trajectory dJ/dK, dJ/dB, dJ/dx0 and the costates."""
+        return self.problem.cost_sensitivity()
 
     def iteration_log(self):
         """numpy [iterations, LOG_COUNT, B] of the last solve (needs callbacks or `keep_log = True`), trimmed to the

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "aslr_common.hpp"
+#include "../../include/aslr_to_amd_sens.h"
 
 using namespace aslr;
 
@@ -253,6 +254,7 @@ struct aslr_problem {
   const double *own_frame_ref;
   int32_t own_planar_reach;
   bool has_placement; // some model of the problem has a frame-placement cost
+  std::vector<double> tp_host; // the table aslr_set_trajectory_params validated and uploaded last ([rows][B] like the region)
 };
 
 namespace {
@@ -867,7 +869,8 @@ int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, 
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(hipMemcpyAsync(region(p, ASLR_R_TRAJ_PARAMS), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st)); // (the staging buffer dies here)
+  HIP_TRY(hipStreamSynchronize(st));
+  p->tp_host.swap(h); // (kept: aslr_cost_sensitivity checks the stiffness rows on the host)
   switch_to(true);
   return ASLR_OK;
 }
@@ -910,6 +913,42 @@ int aslr_calc(aslr_problem_t *p, void *stream) {
 int aslr_calc_diff(aslr_problem_t *p, void *stream) {
   if (!p) return no_handle("aslr_calc_diff");
   return p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, static_cast<hipStream_t>(stream));
+}
+
+int aslr_cost_sensitivity(aslr_problem_t *p, double *dcost_dstiffness, double *dcost_dmotor_inertia, double *dcost_dx0,
+                          double *costate, void *stream) {
+  if (!p) return no_handle("aslr_cost_sensitivity");
+  if (!dcost_dstiffness && !dcost_dmotor_inertia && !dcost_dx0 && !costate)
+    return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: all four outputs are NULL: nothing to compute");
+  const bool sea = p->dam == ASLR_DAM_SEA, table = p->ks->traj_params;
+  if (dcost_dstiffness && !sea) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: dcost_dstiffness on a VSA model, which takes its stiffness from u");
+  const int B = p->desc.B, nj = p->nj, nm = p->desc.nmodels;
+  const aslr_model_t *M = p->desc.models;
+  AdjointArgs a;
+  memset(&a, 0, sizeof a);
+  for (int i = 0; i < nm; ++i) {
+    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: K and B of model %d must be diagonal", i);
+    a.dt[i] = M[i].dt;
+    for (int j = 0; j < nj; ++j) {
+      const double k = M[i].K[j * nj + j], bj = M[i].B[j * nj + j];
+      if (sea && !table && k == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: stiffness entry K[%d] of model %d is 0 (the stiffness term divides by it)", j, i);
+      if (bj == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: motor inertia entry B[%d] of model %d is 0", j, i);
+      a.K[i][j] = sea ? k : 0.0;
+      a.Binv[i][j] = 1.0 / bj;
+    }
+  }
+  if (sea && table)
+    for (int j = 0; j < nj; ++j)
+      for (int b = 0; b < B; ++b)
+        if (p->tp_host[(size_t)j * B + b] == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: stiffness entry [%d][%d] of the parameter table is 0 (the stiffness term divides by it)", b, j);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
+  const KArgs &k = p->k;
+  a.deriv = k.deriv; a.xs = k.xs; a.xnext = k.xnext; a.node_model = k.node_model;
+  a.traj_params = table ? reinterpret_cast<const double *>(region(p, ASLR_R_TRAJ_PARAMS)) : nullptr;
+  a.d_stiffness = dcost_dstiffness; a.d_motor_inertia = dcost_dmotor_inertia; a.d_x0 = dcost_dx0; a.costate = costate;
+  a.B = k.B; a.T = k.T;
+  return launch_adjoint(p->nx, p->nu, a, st);
 }
 
 int aslr_backward_pass(aslr_problem_t *p, const aslr_solver_params_t *sp, void *stream) {

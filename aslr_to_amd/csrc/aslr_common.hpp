@@ -184,6 +184,21 @@ template <int NJ, int DAM, bool TP = false> int launch_forward(const KArgs &k, c
 // hs: ASLR_BWD_HS (0: the size's default decomposition); mfma: ASLR_BLK_MFMA (block kernel of nx = 28 only)
 template <int NJ, int DAM, bool TP = false> int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
 
+// Adjoint sweep (aslr_cost_sensitivity, aslr_adjoint.inc.hpp): what adjoint_kernel reads and writes, by value.  The kernel
+// depends on the record shape (nx, nu) alone, and one template serves handles with and without a parameter table
+// (traj_params == nullptr: K and 1 / B of the node's model, below), so it has no row in the table of kernel sets.
+struct AdjointArgs {
+  const double *deriv, *xs, *xnext;
+  const int32_t *node_model;
+  const double *traj_params; // region TRAJ_PARAMS while a table is set, else nullptr
+  double *d_stiffness, *d_motor_inertia, *d_x0; // [nj][B], [nj][B], [nx][B]; each nullable
+  double *costate;                              // [T+1][B][nx]; nullable
+  int32_t B, T;
+  double dt[ASLR_MAX_MODELS];
+  double K[ASLR_MAX_MODELS][ASLR_MAX_NJ], Binv[ASLR_MAX_MODELS][ASLR_MAX_NJ]; // diagonals; K = 0: no stiffness term (VSA)
+};
+int launch_adjoint(int nx, int nu, const AdjointArgs &a, hipStream_t st);
+
 // the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
 struct KernelSet {
   int nj, dam;

@@ -27,6 +27,14 @@ class MpcResult(object):
         self.__dict__.update(fields)
 
 
+class SensitivityResult(object):
+    """What Engine.cost_sensitivity returns: batch-major device tensors -- stiffness [B, nj] (dJ/dK_j; None for a VSA model,
+    whose stiffness is a control), motor_inertia [B, nj] (dJ/dB_j), x0 [B, nx] (dJ/dx0) and costate [B, T+1, nx]."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class Engine(object):
     """ShootingProblem shard resident in HBM.  Region layouts: include/aslr_to_amd.h."""
 
@@ -277,6 +285,22 @@ class Engine(object):
         it = C.c_int32(0)
         self._call("aslr_solve", C.byref(sp), poll_every, self._stream(), C.byref(it))
         return it.value
+
+    def cost_sensitivity(self):
+        """Gradients of every trajectory's cost at the candidate in XS / US, controls held fixed, in its own spring
+        stiffness, motor inertia and initial state, by one calcDiff sweep and one adjoint sweep (aslr_cost_sensitivity,
+        include/aslr_to_amd_sens.h).  -> SensitivityResult.  Exact where the candidate has no gaps; at a converged
+        solution also the gradient of the optimal cost; with gaps the gradient of the linearisation about (xs, us)."""
+        torch = _torch()
+        nj = self.nx // 4
+        vsa = self.low.dam == _abi.DAM_VSA
+        with torch.cuda.device(self.device):
+            new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
+            dk, db, dx0, lam = (None if vsa else new(nj, self.B)), new(nj, self.B), new(self.nx, self.B), new(self.T + 1, self.B, self.nx)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._call("aslr_cost_sensitivity", ptr(dk), ptr(db), ptr(dx0), ptr(lam), self._stream())
+        return SensitivityResult(stiffness=None if dk is None else dk.t(), motor_inertia=db.t(), x0=dx0.t(),
+                                 costate=lam.permute(1, 0, 2))
 
     # ---- per-iteration log, frame placements, residuals ----
     def enable_iteration_log(self, capacity):

@@ -1,0 +1,201 @@
+"""aslr_cost_sensitivity on the GPU (include/aslr_to_amd_sens.h; adjoint_kernel, csrc/aslr_adjoint.inc.hpp) against
+tests/_sensitivity.py: the costates and the gradients in stiffness, motor inertia and x0 from the CPU oracle's records by
+the definition, none of the kernel's closed-form identities.
+
+Kernel outputs are held to 1e-9 relative, the per-kernel bound of the parity suites (max |a - b| / (1 + |b|)).  Shapes: the
+smallest that still leave a partial wave and a partial group of teams (B = 70 at nx = 8: 8 trajectories per wave), a wave
+with an empty team (B = 3 at nx = 28: 2 per wave), and the smallest problem there is (B = 1, T = 1)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import _gpu_case as gc
+import _ref_path
+import _sensitivity as sens
+from aslr_to_amd import _abi, crocoddyl, scenarios
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ("stiffness", "motor_inertia", "x0", "costate")
+GUARD, SENTINEL = 64, -7.25
+
+
+def _pendulum(fn, B, T):
+    sc = fn(T=T)
+    sc["x0"] = np.asarray(sc["x0"]) + np.random.default_rng(2).uniform(-0.3, 0.3, (B, 8))
+    return sc
+
+
+def _scenario(name, B, T, table):
+    if name.startswith("double_pendulum"):
+        sc = _pendulum(scenarios.SCENARIOS[name], B, T)
+    elif name == "talos_arm_vsa":
+        sc = scenarios.talos_arm_vsa(B=B, T=T, seed=4, tight=True)
+    else:
+        sc = scenarios.SCENARIOS[name](B=B, T=T, seed=4)
+    if table:
+        sc = scenarios.with_traj_params(sc, seed=5)
+    return sc
+
+
+# (scenario, table, B, T, reference path)
+CASES = [
+    ("two_dof_sea", True, 70, 5, False), ("two_dof_sea", False, 70, 5, False),
+    ("two_dof_sea", True, 1, 1, False), ("two_dof_sea", False, 1, 1, False),
+    ("two_dof_sea", True, 70, 5, True),
+    ("two_dof_vsa_boxddp", False, 70, 5, False),
+    ("double_pendulum", False, 9, 3, False), ("double_pendulum_nu1", False, 9, 3, False),
+    ("talos_arm_sea", True, 3, 4, False),
+    ("talos_arm_vsa", False, 3, 4, False),
+]
+
+
+def _case(name, table, B, T, path):
+    sc = _scenario(name, B, T, table)
+    if path:  # 4 rows from row 2 on: knots 0 and 1 read rows 2 and 3, the others hold the last row
+        sc = _ref_path.with_path(sc, _ref_path.random_path(sc, 4, 13), row0=2)
+    low = scenarios.lower(sc)
+    xs, us = gc.random_candidate(low, 3)
+    return sc, low, xs, us
+
+
+def _shapes(e):
+    nj = e.nx // 4
+    return {"stiffness": (nj, e.B), "motor_inertia": (nj, e.B), "x0": (e.nx, e.B), "costate": (e.T + 1, e.B, e.nx)}
+
+
+def _raw(e, which=FIELDS, expect=_abi.OK):
+    """aslr_cost_sensitivity with the outputs `which` (the others NULL), each in a buffer of the test's own with GUARD
+    sentinel words behind it.  -> dict of batch-major numpy arrays (the layout of tests/_sensitivity.expected); the guards
+    must be untouched.  expect != OK: -> the message of the refusal."""
+    import torch
+    bufs = {}
+    for k in which:
+        n = int(np.prod(_shapes(e)[k]))
+        bufs[k] = torch.full((n + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
+    ptr = lambda k: C.c_void_p(bufs[k].data_ptr()) if k in bufs else None
+    with torch.cuda.device(e.device):
+        rc = e.lib.aslr_cost_sensitivity(e.handle, ptr("stiffness"), ptr("motor_inertia"), ptr("x0"), ptr("costate"), e._stream())
+    gc.sync()
+    if expect != _abi.OK:
+        assert rc == expect, rc
+        for k, t in bufs.items():
+            assert (t == SENTINEL).all(), "%s was written by a refused call" % k
+        return e.lib.aslr_last_error().decode()
+    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
+    out = {}
+    for k, t in bufs.items():
+        a = gc.to_np(t)
+        n = a.size - GUARD
+        assert (a[n:] == SENTINEL).all(), "the guard behind %s was overwritten" % k
+        a = a[:n].reshape(_shapes(e)[k])
+        out[k] = a.transpose(1, 0, 2).copy() if k == "costate" else a.T.copy()
+    return out
+
+
+def _loaded(low, xs, us):
+    e = gc.engine(low)
+    gc._upload(e, XS=xs, US=us)
+    return e
+
+
+@pytest.mark.parametrize("name, table, B, T, path", CASES)
+def test_kernel_matches_the_definition_on_the_oracle_records(oracle, name, table, B, T, path):
+    """a random candidate (non-zero gaps: both sides linearise about the same point), all four outputs, through
+    Engine.cost_sensitivity"""
+    sc, low, xs, us = _case(name, table, B, T, path)
+    want = sens.expected(oracle, low, xs, us, path=low.ref_path if path else None)
+    e = _loaded(low, xs, us)
+    got = e.cost_sensitivity()
+    gc.sync()
+    if low.dam == _abi.DAM_VSA:
+        assert got.stiffness is None and want["stiffness"] is None
+    for k in FIELDS:
+        if want[k] is None:
+            continue
+        g = gc.to_np(getattr(got, k))
+        assert g.shape == want[k].shape, (k, g.shape, want[k].shape)
+        if not (T == 1 and k == "motor_inertia"):  # (T = 1: lambda_1 is the terminal cost's gradient, which has no motor
+            assert np.abs(want[k]).max() > 1e-3, k  #  entries here, so dJ/dB is exactly 0 on both sides)
+        gc._assert_close("%s %s" % (name, k), g, want[k], 1e-9)
+    if path:  # ... and the path is what the costs were evaluated against
+        plain = sens.expected(oracle, scenarios.lower(dict(sc, ref_path=None)), xs, us)
+        assert gc.relerr(plain["x0"], want["x0"]) > 1e-6
+
+
+@pytest.mark.parametrize("table", [True, False])
+def test_a_trajectory_does_not_depend_on_the_batch_it_is_in(table):
+    """trajectory b of the B = 70 batch against the same problem alone (B = 1, its own row of the table): bit for bit"""
+    sc, low, xs, us = _case("two_dof_sea", table, 70, 5, False)
+    batch = _raw(_loaded(low, xs, us))
+    for b in (0, 5, 7, 8, 63, 64, 69):
+        one = dict(sc, x0=sc["x0"][b:b + 1], frame_refs=sc["frame_refs"][b:b + 1])
+        if table:
+            one["traj_params"] = {k: (None if v is None else v[b:b + 1]) for k, v in sc["traj_params"].items()}
+        alone = _raw(_loaded(scenarios.lower(one), xs[:, b:b + 1], us[:, b:b + 1]))
+        for k in FIELDS:
+            np.testing.assert_array_equal(alone[k][0].view(np.uint64), batch[k][b].view(np.uint64), err_msg="%s of trajectory %d" % (k, b))
+
+
+@pytest.mark.parametrize("name, B, T", [("two_dof_sea", 70, 5), ("talos_arm_sea", 3, 4)])
+def test_every_output_is_optional(name, B, T):
+    """each output alone: the bits of the call with all four, and nothing written past any buffer (_raw checks the guards)"""
+    sc, low, xs, us = _case(name, True, B, T, False)
+    e = _loaded(low, xs, us)
+    full = _raw(e)
+    for k in FIELDS:
+        alone = _raw(e, which=(k,))
+        assert list(alone) == [k]
+        np.testing.assert_array_equal(alone[k].view(np.uint64), full[k].view(np.uint64), err_msg=k)
+
+
+def test_refusals_leave_a_live_handle_that_still_solves():
+    B = 4
+    vsa = _loaded(*_case("two_dof_vsa_boxddp", False, B, 5, False)[1:])
+    msg = _raw(vsa, expect=_abi.E_INVALID)
+    assert msg.startswith("aslr_cost_sensitivity:") and "VSA" in msg, msg
+    assert set(_raw(vsa, which=("motor_inertia", "x0", "costate"))) == {"motor_inertia", "x0", "costate"}
+    sc, low, xs, us = _case("two_dof_sea", True, B, 5, False)
+    sp = scenarios.solver_params(sc, maxiter=8)
+    _, fresh = gc.solve_gpu(low, sp)
+    e = _loaded(low, xs, us)
+    msg = _raw(e, which=(), expect=_abi.E_INVALID)
+    assert msg.startswith("aslr_cost_sensitivity:") and "NULL" in msg, msg
+    tp = {k: v for k, v in sc["traj_params"].items() if v is not None}
+    zero = np.array(tp["stiffness"])
+    zero[2, 1] = 0.0
+    e.set_trajectory_params(**dict(tp, stiffness=zero))
+    msg = _raw(e, expect=_abi.E_INVALID)
+    assert msg.startswith("aslr_cost_sensitivity:") and "stiffness" in msg and "table" in msg, msg
+    e.set_trajectory_params(**tp)
+    assert set(_raw(e)) == set(FIELDS)
+    e.set_candidate(None, None)
+    e.solve(sp)
+    gc.sync()
+    after = gc.solution(e)
+    for k in ("xs", "us", "traj_i"):
+        np.testing.assert_array_equal(after[k], fresh[k], err_msg=k)
+
+
+def test_python_facade_at_a_solution_matches_finite_differences_of_the_optimal_cost(oracle):
+    """SolverDDP.solve on the case of the optimum test of tests/test_sensitivity_host.py, then solver.cost_sensitivity():
+    its stiffness and inertia gradients against the oracle's finite differences of the converged cost, within the bound
+    recorded there; x0 is costate[:, 0], bit for bit."""
+    sc, sp = sens.optimum_case()
+    problem = crocoddyl.ShootingProblem(sc["x0"], sc["running"], sc["terminal"], frame_refs=sc["frame_refs"])
+    solver = crocoddyl.SolverDDP(problem)
+    solver.th_stop = sp.th_stop
+    assert solver.solve([], [], sp.maxiter)
+    got = solver.cost_sensitivity()
+    gc.sync()
+    fd = sens.optimum_fd(oracle)
+    for k in ("stiffness", "motor_inertia"):
+        err = sens.relerr(gc.to_np(getattr(got, k)), fd[k])
+        print("d%s: disagreement %.2e (bound %.1e)" % (k, err, 10 * sens.OPT_FD[1]))
+        assert err < 10 * sens.OPT_FD[1], (k, err)
+    assert tuple(got.costate.shape) == (sens.OPT_B, sens.OPT_T + 1, 8)
+    gc.same_bits(got.x0, got.costate[:, 0], "x0 is the first costate")
+    # ... and the same through the problem, with the candidate given
+    again = problem.cost_sensitivity(solver.xs, solver.us)
+    gc.same_bits(again.motor_inertia, got.motor_inertia, "the candidate given explicitly")
