@@ -168,6 +168,10 @@ EXPORTED_SYMBOLS = [
 # that the base header, its symbol list and ABI_VERSION stay what existing bindings check against
 EXTENSION_SYMBOLS = ["aslr_cost_sensitivity"]
 
+# what include/aslr_to_amd_policy.h declares: a second extension header, in a list of its own so that EXTENSION_SYMBOLS
+# keeps equalling what aslr_to_amd_sens.h declares
+POLICY_SYMBOLS = ["aslr_policy_rollout"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -245,6 +249,8 @@ def load_library():
     lib.aslr_set_iteration_log.argtypes = [vp, vp, i32]
     lib.aslr_cost_sensitivity.restype = C.c_int
     lib.aslr_cost_sensitivity.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.aslr_policy_rollout.restype = C.c_int
+    lib.aslr_policy_rollout.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

@@ -224,6 +224,36 @@ class ShootingProblem(object):
             e.set_candidate(xs, us)
         return e.cost_sensitivity()
 
+    def policy_rollout(self, xs, us, K, n_samples, plant_stiffness=None, plant_motor_inertia=None, dx0=None,
+                       disturbance=None, clamp=False, keep_trajectories=False):
+        """Closed-loop roll-outs of the policy u_t = us_t - K_t (x_t - xs_t) on n_samples perturbed plants per trajectory
+        (Engine.policy_rollout; aslr_policy_rollout): xs [B, T+1, nx], us [B, T, nu], K [B, T, nu, nx] (or without the
+        batch axis: the same for every trajectory; lists of per-knot arrays as the solvers return them do), all three
+        None: the policy the engine holds.  The engine's own XS / US / KGAIN are put back afterwards, so a solve in
+        progress is not disturbed.  -> engine.PolicyRolloutResult.  This shard's trajectories only."""
+        import torch
+        e = self.engine
+        if xs is None and us is None and K is None:
+            return e.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance, clamp, keep_trajectories)
+        if xs is None or us is None or K is None:
+            raise ValueError("policy_rollout: give xs, us and K together (or none of them: the engine's own policy)")
+        keep = [(r, e.region(r).clone()) for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN)]
+        try:
+            e.set_candidate(xs, us)
+            k = torch.as_tensor(np.asarray(K, dtype=np.float64) if not torch.is_tensor(K) else K, dtype=torch.float64, device=e.device)
+            if k.dim() == 3:
+                k = k.unsqueeze(0).expand(self.batch, -1, -1, -1)
+            if k.dim() == 4 and k.shape[2] == e.nu_user and e.nu_user != e.nu:  # padded controls: zero gain rows
+                k = torch.cat([k, torch.zeros(k.shape[:2] + (e.nu - e.nu_user, k.shape[3]), dtype=k.dtype, device=k.device)], dim=2)
+            if tuple(k.shape) != (self.batch, self.T, e.nu, e.nx):
+                raise ValueError("K must have shape [B=%d, T=%d, nu=%d, nx=%d]" % (self.batch, self.T, e.nu_user, e.nx))
+            e.region(_abi.R_KGAIN).copy_(k.permute(1, 0, 2, 3))
+            res = e.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance, clamp, keep_trajectories)
+        finally:
+            for r, t in keep:
+                e.region(r).copy_(t)
+        return res
+
     def _total_cost(self):
         c = self.engine.region(_abi.R_COST).sum(dim=0)
         return float(c[0].item()) if self.batch == 1 else c
@@ -464,6 +494,20 @@ class SolverDDP(object):
         """problem.cost_sensitivity() at this solver's solution (the committed xs / us of the last solve): per
         trajectory dJ/dK, dJ/dB, dJ/dx0 and the costates."""
         return self.problem.cost_sensitivity()
+
+    def policy_rollout(self, n_samples, plant_stiffness=None, plant_motor_inertia=None, dx0=None, disturbance=None,
+                       clamp=None, keep_trajectories=False):
+        """How the policy of the last solve (its xs, us and Riccati gains K) holds up on a plant that differs from the
+        model: n_samples = S closed loops per trajectory, u_t = us_t - K_t (x_t - xs_t), each on its own plant.  Batch-
+        major arrays or tensors, each optional: plant_stiffness / plant_motor_inertia [B, S, nj] (diagonals of K and B;
+        no plant_stiffness for a VSA model), dx0 [B, S, nx], disturbance [B, S, T, nx].  clamp: clamp the controls to the
+        box; None = iff this solver is SolverBoxDDP.  -> engine.PolicyRolloutResult: cost [B, S], failed_knot [B, S],
+        x_final [B, S, nx], and xs [B, S, T+1, nx] / us [B, S, T, nu] with keep_trajectories.  One launch on the device
+        that writes nothing into the solver's state (aslr_policy_rollout, include/aslr_to_amd_policy.h)."""
+        if clamp is None:
+            clamp = self._solver == _abi.SOLVER_BOXDDP
+        return self.problem.engine.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance,
+                                                  bool(clamp), keep_trajectories)
 
     def iteration_log(self):
         """numpy [iterations, LOG_COUNT, B] of the last solve (needs callbacks or `keep_log = True`), trimmed to the

@@ -199,6 +199,21 @@ struct AdjointArgs {
 };
 int launch_adjoint(int nx, int nu, const AdjointArgs &a, hipStream_t st);
 
+// Closed-loop policy roll-outs (aslr_policy_rollout, aslr_policy.inc.hpp): the caller's arrays, by value, beside the KArgs and
+// ModelLimits of the handle.  One template serves handles with and without a parameter table (`table`), as the adjoint
+// kernel does, so it has no row in the table of kernel sets either.
+struct PolicyArgs {
+  const double *plant_stiffness, *plant_motor_inertia; // [nj][S][B], each nullable
+  const double *dx0, *disturbance;                     // [S][B][nx], [S][T][B][nx], each nullable
+  double *cost;                                        // [S][B]; every output nullable
+  int32_t *failed_knot;                                // [S][B]
+  double *x_final, *xs_closed, *us_closed;             // [S][B][nx], [S][T+1][B][nx], [S][T][B][nu]
+  int32_t S, clamp;
+  int32_t table;    // a parameter table is set: K, 1 / B and the control box of a trajectory are its row
+  int32_t diagonal; // a plant array or a table is in use (every model's K and B is diagonal then): diagonals through ModelRegs::set_traj
+};
+int launch_policy_rollout(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st);
+
 // the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
 struct KernelSet {
   int nj, dam;

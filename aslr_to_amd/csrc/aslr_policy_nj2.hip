@@ -1,0 +1,2 @@
+// closed-loop policy roll-outs (aslr_policy_rollout): policy_rollout_kernel for nj = 2 (nx = 8; SEA and VSA, planar and 3-D chains)
+#include "aslr_policy.inc.hpp"

@@ -35,6 +35,15 @@ class SensitivityResult(object):
         self.__dict__.update(fields)
 
 
+class PolicyRolloutResult(object):
+    """What Engine.policy_rollout returns: batch-major device tensors -- cost [B, S] (NaN for a failed sample),
+    failed_knot [B, S] (int32; -1: none), x_final [B, S, nx] and, when kept, xs [B, S, T+1, nx] and us [B, S, T, nu] (the
+    models' own nu: padded controls are cut); xs and us are None otherwise."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class Engine(object):
     """ShootingProblem shard resident in HBM.  Region layouts: include/aslr_to_amd.h."""
 
@@ -301,6 +310,47 @@ class Engine(object):
         self._call("aslr_cost_sensitivity", ptr(dk), ptr(db), ptr(dx0), ptr(lam), self._stream())
         return SensitivityResult(stiffness=None if dk is None else dk.t(), motor_inertia=db.t(), x0=dx0.t(),
                                  costate=lam.permute(1, 0, 2))
+
+    def policy_rollout(self, n_samples, plant_stiffness=None, plant_motor_inertia=None, dx0=None, disturbance=None,
+                       clamp=False, keep_trajectories=False):
+        """Closed-loop roll-outs of the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), on n_samples = S perturbed
+        plants per trajectory (aslr_policy_rollout, include/aslr_to_amd_policy.h).  Batch-major arrays or tensors, each
+        optional: plant_stiffness, plant_motor_inertia [B, S, nj] (diagonals of the plant's K and B; None: the
+        trajectory's own), dx0 [B, S, nx] (added to x0), disturbance [B, S, T, nx] (added to the next state of every
+        knot).  clamp: clamp the control to the knot's box.  -> PolicyRolloutResult.  Writes nothing into the workspace.
+        Before any backward sweep K = 0 and the roll-out is open loop; a non-positive plant inertia is not checked (it
+        lives on the device) and shows up in failed_knot."""
+        torch = _torch()
+        S, B, T, nx, nu, nj = int(n_samples), self.B, self.T, self.nx, self.nu, self.nx // 4
+
+        def dev(v, shape, perm, name):
+            if v is None:
+                return None
+            t = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
+                                device=self.device)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, not %s" % (name, list(shape), list(t.shape)))
+            return t.permute(*perm).contiguous()
+
+        if S > 0:  # (S <= 0: the library refuses by name)
+            pk = dev(plant_stiffness, (B, S, nj), (2, 1, 0), "plant_stiffness")
+            pb = dev(plant_motor_inertia, (B, S, nj), (2, 1, 0), "plant_motor_inertia")
+            d0 = dev(dx0, (B, S, nx), (1, 0, 2), "dx0")
+            w = dev(disturbance, (B, S, T, nx), (1, 2, 0, 3), "disturbance")
+        else:
+            pk = pb = d0 = w = None
+        n = max(S, 0)
+        with torch.cuda.device(self.device):
+            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
+            cost, failed, xf = new(torch.float64, n, B), new(torch.int32, n, B), new(torch.float64, n, B, nx)
+            xs = new(torch.float64, n, T + 1, B, nx) if keep_trajectories else None
+            us = new(torch.float64, n, T, B, nu) if keep_trajectories else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._call("aslr_policy_rollout", S, ptr(pk), ptr(pb), ptr(d0), ptr(w), 1 if clamp else 0, ptr(cost), ptr(failed),
+                   ptr(xf), ptr(xs), ptr(us), self._stream())
+        return PolicyRolloutResult(cost=cost.t(), failed_knot=failed.t(), x_final=xf.permute(1, 0, 2),
+                                   xs=None if xs is None else xs.permute(2, 0, 1, 3),
+                                   us=None if us is None else self.cut_u(us.permute(2, 0, 1, 3)))
 
     # ---- per-iteration log, frame placements, residuals ----
     def enable_iteration_log(self, capacity):
