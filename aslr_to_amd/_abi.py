@@ -172,6 +172,9 @@ EXTENSION_SYMBOLS = ["aslr_cost_sensitivity"]
 # keeps equalling what aslr_to_amd_sens.h declares
 POLICY_SYMBOLS = ["aslr_policy_rollout"]
 
+# what include/aslr_to_amd_mpc_plant.h declares: a third extension header, in a list of its own for the same reason
+MPC_PLANT_SYMBOLS = ["aslr_mpc_run_plant"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -251,6 +254,8 @@ def load_library():
     lib.aslr_cost_sensitivity.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.aslr_policy_rollout.restype = C.c_int
     lib.aslr_policy_rollout.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.aslr_mpc_run_plant.restype = C.c_int
+    lib.aslr_mpc_run_plant.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

@@ -455,7 +455,8 @@ class SolverDDP(object):
         return bool(((st & _abi.ST_CONVERGED) != 0).all().item())
 
     def solve_mpc(self, n_steps, iters_per_step, init_xs=None, init_us=None, maxiter=100, isFeasible=False,
-                  disturbance=None, regInit=None):
+                  disturbance=None, regInit=None, hold=1, plant_stiffness=None, plant_motor_inertia=None, clamp=None,
+                  closed_cost=False):
         """A receding-horizon run of n_steps control steps on the device (aslr_mpc_run): `solve(init_xs, init_us,
         maxiter, isFeasible)` first, then per step -- apply us[0] to the plant (the first running model), add
         disturbance[:, s] ([B, n_steps, nx], optional) to its next state, shift the plan one knot,
@@ -463,7 +464,15 @@ class SolverDDP(object):
         round trip per step.  Callbacks are not replayed (the per-iteration log would be overwritten every step).
         With a reference path (ShootingProblem(frame_ref_path=) / set_reference_path) step s plans against the rows
         reference_row + s + t; afterwards problem.reference_row has grown by n_steps (MpcResult.reference_row).
-        -> engine.MpcResult; solver.xs / us are the last shifted plan."""
+        -> engine.MpcResult; solver.xs / us are the last shifted plan.
+
+        On a plant that differs from the model (aslr_mpc_run_plant; any of the following away from its default): hold = h
+        re-plans only every h knots and tracks with the Riccati gains of the last solve in between, u = us_j - K_j (x -
+        xs_j); plant_stiffness / plant_motor_inertia [B, nj] are the diagonals of the plant's K and B (no plant_stiffness
+        for a VSA model); clamp: clamp the applied controls to the box, None = iff this solver is SolverBoxDDP;
+        closed_cost: also sum the running costs of the applied knots.  disturbance is then [B, n_steps * h, nx], the
+        result holds n_steps * h applied knots, closed_cost [B], failed_knot [B] and hold, and the reference row grows
+        by n_steps * h (Engine.mpc_run_plant)."""
         e = self.problem.engine
         sp = self._sp
         sp.maxiter = int(maxiter)
@@ -471,7 +480,12 @@ class SolverDDP(object):
         sp.reg_init = float("nan") if regInit is None else float(regInit)
         e.set_candidate(init_xs, init_us)
         e.enable_iteration_log(0)
-        return e.mpc_run(sp, n_steps, sp.maxiter, iters_per_step, disturbance)
+        if hold == 1 and plant_stiffness is None and plant_motor_inertia is None and clamp is None and not closed_cost:
+            return e.mpc_run(sp, n_steps, sp.maxiter, iters_per_step, disturbance)
+        if clamp is None:
+            clamp = self._solver == _abi.SOLVER_BOXDDP
+        return e.mpc_run_plant(sp, n_steps, sp.maxiter, iters_per_step, hold, plant_stiffness, plant_motor_inertia,
+                               disturbance, bool(clamp), bool(closed_cost))
 
     def solve_pool(self, x0s, frame_refs=None, maxiter=100, isFeasible=False, regInit=None, refill_every=4,
                    poll_every=16, init_xs=None, init_us=None):

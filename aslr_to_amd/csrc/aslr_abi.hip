@@ -8,6 +8,7 @@
 #include "aslr_common.hpp"
 #include "../../include/aslr_to_amd_sens.h"
 #include "../../include/aslr_to_amd_policy.h"
+#include "../../include/aslr_to_amd_mpc_plant.h"
 
 using namespace aslr;
 
@@ -196,6 +197,61 @@ __global__ void __launch_bounds__(64) mpc_advance_kernel(KArgs a, MpcDev m) {
     a.xs[bx + tid] = xp;
     const_cast<double *>(a.x0)[bx + tid] = xp;
     if (m.x_last) m.x_last[bx + tid] = xp;
+  }
+  // ---- reset: the next solve starts from zeroed gaps and gains ----
+  zero_column(a.gaps, T + 1, B, b, nx, tid);
+  zero_column(a.vxxf, T + 1, B, b, nx, tid);
+  zero_column(a.kff, T, B, b, nu, tid);
+}
+
+// aslr_mpc_run_plant: the same between two solves when the plant phase was mpc_plant_kernel's -- `h` knots applied and
+// recorded there, the plant's state left in xplus ([B][nx]: the row of x_closed behind the step's last record) -- so what is
+// left here is the step's statistics, the shift by h rows and the reset.  A kernel of its own: mpc_advance_kernel and
+// shift_column stay the code aslr_mpc_run's bit-level tests pin.
+struct MpcHoldDev {
+  int32_t nx, nu, h;
+  const double *xplus;
+  double *stat_f;               // [4][B] of this step
+  int32_t *stat_i;              // [2][B]
+};
+// rows [0, n) of trajectory b's column take row min(t + h, last), where last >= n is the row the clamped tail repeats (T of
+// xs with n = T, T - 1 of us with n = T - 1).  shift_column's argument, restated for h rows: entry e = t w + i reads entry
+// e + h w, or its image in row `last` once t + h passes it.  Within a round every load precedes the barrier and every store
+// follows it.  Across rounds a store of this round touches entries below e0 + 64 kStage only, and a later round reads (a)
+// unclamped sources e' + h w with e' >= e0 + 64 kStage, above everything stored so far, or (b) row `last`, which no round
+// stores to (destinations end at row n - 1 < last): the several destination rows of the tail all read that one untouched row.
+__device__ void shift_column_hold(double *base, int n, int B, int b, int w, int tid, int h, int last) {
+  const int ne = n * w;
+  for (int e0 = 0; e0 < ne; e0 += 64 * kStage) { // (block-uniform trip count)
+    double v[kStage] = {};
+    ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
+      const int e = e0 + 64 * k + tid, t = e / w, i = e - t * w;
+      if (e < ne) v[k] = base[((size_t)min(t + h, last) * B + b) * w + i];
+    }
+    __syncthreads();
+    ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
+      const int e = e0 + 64 * k + tid, t = e / w, i = e - t * w;
+      if (e < ne) base[((size_t)t * B + b) * w + i] = v[k];
+    }
+  }
+}
+__global__ void __launch_bounds__(64) mpc_advance_hold_kernel(KArgs a, MpcHoldDev m) {
+  const int b = blockIdx.x, tid = threadIdx.x, B = a.B, T = a.T, nx = m.nx, nu = m.nu;
+  const size_t bx = (size_t)b * nx; // knot 0 of trajectory b
+  double xp = 0.0;
+  if (tid < nx) xp = m.xplus[bx + tid];
+  if (tid < 4) {
+    const int row = tid == 0 ? ASLR_TF_COST : tid == 1 ? ASLR_TF_STOP : tid == 2 ? ASLR_TF_XREG : ASLR_TF_STEP;
+    m.stat_f[(size_t)tid * B + b] = a.traj_f[(size_t)row * B + b];
+  }
+  if (tid < 2) m.stat_i[(size_t)tid * B + b] = a.traj_i[(size_t)(tid == 0 ? ASLR_TI_ITER : ASLR_TI_STATUS) * B + b];
+  // ---- shift: xs[t] <- xs[min(t + h, T)] (t < T), us[t] <- us[min(t + h, T - 1)] (t < T - 1); then xs[0] <- x+ ----
+  shift_column_hold(a.xs, T, B, b, nx, tid, m.h, T);
+  shift_column_hold(a.us, T - 1, B, b, nu, tid, m.h, T - 1);
+  __syncthreads(); // (knot 0 was written by the shift, possibly by other lanes)
+  if (tid < nx) {
+    a.xs[bx + tid] = xp;
+    const_cast<double *>(a.x0)[bx + tid] = xp;
   }
   // ---- reset: the next solve starts from zeroed gaps and gains ----
   zero_column(a.gaps, T + 1, B, b, nx, tid);
@@ -708,6 +764,16 @@ int pool_flush_and_count(const aslr_problem *p, const KArgs &k, const PoolDev &p
   return ASLR_OK;
 }
 
+// what aslr_mpc_run refuses, under the name of the entry point that was called (aslr_mpc_run_plant refuses the same)
+int mpc_refusals(const char *fn, const aslr_problem *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc) {
+  if (!p || !sp || !mpc) return fail(ASLR_E_INVALID, "%s: NULL argument: %s", fn, !p ? "the problem handle p" : !sp ? "sp" : "mpc");
+  if (mpc->n_steps < 1 || mpc->first_maxiter < 1 || mpc->iters_per_step < 1) return fail(ASLR_E_INVALID, "%s: n_steps, first_maxiter and iters_per_step must be >= 1", fn);
+  if (!mpc->x_closed || !mpc->u_closed || !mpc->stat_f || !mpc->stat_i) return fail(ASLR_E_INVALID, "%s: x_closed, u_closed, stat_f and stat_i must be given", fn);
+  if (!p->uniform_running) return fail(ASLR_E_INVALID, "%s: the running knots use more than one action model: shifting the plan needs one (references that vary along the horizon: aslr_set_reference_path)", fn);
+  if (p->k.iter_log) return fail(ASLR_E_INVALID, "%s: an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)", fn);
+  return solver_unsupported(fn, p, sp->solver);
+}
+
 } // namespace
 
 extern "C" {
@@ -1089,12 +1155,7 @@ int aslr_solve(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t poll_e
 }
 
 int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, void *stream) {
-  if (!p || !sp || !mpc) return fail(ASLR_E_INVALID, "aslr_mpc_run: NULL argument: %s", !p ? "the problem handle p" : !sp ? "sp" : "mpc");
-  if (mpc->n_steps < 1 || mpc->first_maxiter < 1 || mpc->iters_per_step < 1) return fail(ASLR_E_INVALID, "aslr_mpc_run: n_steps, first_maxiter and iters_per_step must be >= 1");
-  if (!mpc->x_closed || !mpc->u_closed || !mpc->stat_f || !mpc->stat_i) return fail(ASLR_E_INVALID, "aslr_mpc_run: x_closed, u_closed, stat_f and stat_i must be given");
-  if (!p->uniform_running) return fail(ASLR_E_INVALID, "aslr_mpc_run: the running knots use more than one action model: shifting the plan needs one (references that vary along the horizon: aslr_set_reference_path)");
-  if (p->k.iter_log) return fail(ASLR_E_INVALID, "aslr_mpc_run: an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)");
-  if (int rc = solver_unsupported("aslr_mpc_run", p, sp->solver)) return rc;
+  if (int rc = mpc_refusals("aslr_mpc_run", p, sp, mpc)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t B = p->desc.B, nx = p->nx, nu = p->nu;
   const int32_t row0 = p->k.ref_row0;
@@ -1122,6 +1183,60 @@ int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_m
     HIP_TRY(hipGetLastError());
   }
   if (p->ref_path_set) p->k.ref_row0 = row0 + mpc->n_steps; // (the next run, or a solve, carries on where this one ended)
+  return ASLR_OK;
+}
+
+int aslr_mpc_run_plant(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, int hold,
+                       const double *plant_stiffness, const double *plant_motor_inertia, int clamp, double *closed_cost,
+                       int32_t *failed_knot, void *stream) {
+  const char *fn = "aslr_mpc_run_plant";
+  if (int rc = mpc_refusals(fn, p, sp, mpc)) return rc;
+  const int T = p->desc.T;
+  if (hold < 1 || hold > T) return fail(ASLR_E_INVALID, "%s: hold = %d must lie in [1, T = %d]", fn, hold, T);
+  if (p->nj != 2)
+    return fail(ASLR_E_INVALID, "%s: the plant kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint form is not built; aslr_mpc_run serves it)", fn, p->nj);
+  if (plant_stiffness && p->dam != ASLR_DAM_SEA)
+    return fail(ASLR_E_INVALID, "%s: plant_stiffness on a VSA model, which takes its stiffness from u", fn);
+  if (plant_stiffness || plant_motor_inertia)
+    for (int i = 0; i < p->desc.nmodels; ++i)
+      if (!is_diagonal(p->nj, p->desc.models[i].K) || !is_diagonal(p->nj, p->desc.models[i].B))
+        return fail(ASLR_E_INVALID, "%s: a plant argument needs diagonal K and B, and those of model %d are not", fn, i);
+  const long long N = (long long)mpc->n_steps * hold;
+  const int32_t row0 = p->k.ref_row0;
+  if (N > INT32_MAX || (p->ref_path_set && row0 > (long long)INT32_MAX - N - T))
+    return fail(ASLR_E_INVALID, "%s: n_steps * hold, or the reference row after them, would overflow: reposition the row with aslr_set_reference_path", fn);
+  // nothing asked of the plant phase that the one-knot calc launch does not do: the launches of aslr_mpc_run
+  if (hold == 1 && !plant_stiffness && !plant_motor_inertia && !closed_cost && !failed_knot && !clamp) return aslr_mpc_run(p, sp, mpc, stream);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t B = p->desc.B, nx = p->nx, nu = p->nu;
+  const bool table = p->ks->traj_params;
+  for (int s = 0; s < mpc->n_steps; ++s) {
+    const size_t k0 = (size_t)s * hold; // the applied knot this step starts with
+    // with a reference path the window slides hold rows per control step: the solve of step s plans against rows
+    // row0 + k0 + t, its plant phase applies knot j against row row0 + k0 + j (by value in the argument block, as aslr_mpc_run)
+    KArgs ks = p->k;
+    if (p->ref_path_set) ks.ref_row0 = row0 + (int32_t)k0;
+    if (int rc = iterate(p, sp, true, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, st, IterOpts{ks, 0, true, nullptr})) return rc;
+    if (int rc = aslr_finalize(p, stream)) return rc;
+    MpcPlantArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.plant_stiffness = plant_stiffness; pa.plant_motor_inertia = plant_motor_inertia;
+    pa.disturbance = mpc->disturbance ? mpc->disturbance + k0 * B * nx : nullptr;
+    pa.x_rec = mpc->x_closed + k0 * B * nx;
+    pa.u_rec = mpc->u_closed + k0 * B * nu;
+    pa.closed_cost = closed_cost; pa.failed_knot = failed_knot;
+    pa.hold = hold; pa.k0 = (int32_t)k0; pa.first = s == 0; pa.clamp = clamp != 0;
+    pa.table = table; pa.diagonal = table || plant_stiffness || plant_motor_inertia;
+    if (int rc = launch_mpc_plant(p->nj, p->dam, ks, p->limits, pa, st)) return rc;
+    MpcHoldDev m;
+    m.nx = p->nx; m.nu = p->nu; m.h = hold;
+    m.xplus = mpc->x_closed + (k0 + hold) * B * nx; // (the plant kernel left x+ in the row behind its last record)
+    m.stat_f = mpc->stat_f + (size_t)s * 4 * B;
+    m.stat_i = mpc->stat_i + (size_t)s * 2 * B;
+    hipLaunchKernelGGL(mpc_advance_hold_kernel, dim3(p->desc.B), dim3(64), 0, st, p->k, m);
+    HIP_TRY(hipGetLastError());
+  }
+  if (p->ref_path_set) p->k.ref_row0 = row0 + (int32_t)N;
   return ASLR_OK;
 }
 

@@ -214,6 +214,21 @@ struct PolicyArgs {
 };
 int launch_policy_rollout(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st);
 
+// The plant phase of one control step of aslr_mpc_run_plant (aslr_mpc_plant.inc.hpp): the caller's arrays, by value, beside
+// the KArgs and ModelLimits of the handle; `table` and `diagonal` as in PolicyArgs.  Like the policy kernel it has no row in
+// the table of kernel sets.
+struct MpcPlantArgs {
+  const double *plant_stiffness, *plant_motor_inertia; // [nj][B], each nullable
+  const double *disturbance;                           // [hold][B][nx] of this step, nullable
+  double *x_rec, *u_rec;                               // x_closed[s hold] ([hold + 1] rows are written), u_closed[s hold]
+  double *closed_cost;                                 // [B], nullable: started in the first step, continued after
+  int32_t *failed_knot;                                // [B], nullable: likewise
+  int32_t hold, k0;                                    // knots applied per step; the applied-knot index of this step's first
+  int32_t first, clamp;                                // first: step 0 of the run
+  int32_t table, diagonal;
+};
+int launch_mpc_plant(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
+
 // the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
 struct KernelSet {
   int nj, dam;

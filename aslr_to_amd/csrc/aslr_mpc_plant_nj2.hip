@@ -1,0 +1,2 @@
+// the plant phase of aslr_mpc_run_plant: mpc_plant_kernel for nj = 2 (nx = 8; SEA and VSA, planar and 3-D chains)
+#include "aslr_mpc_plant.inc.hpp"

@@ -21,7 +21,9 @@ def _torch():
 class MpcResult(object):
     """What Engine.mpc_run returns: batch-major device tensors, views of the time-major arrays the kernels wrote --
     xs_closed [B, n+1, nx], us_closed [B, n, nu_user], and per step's solve iters, status (int32), cost, stop, x_reg,
-    step [B, n]; reference_row (int): the row of the reference path knot 0 reads after the run (0 without a path)."""
+    step [B, n]; reference_row (int): the row of the reference path knot 0 reads after the run (0 without a path).
+    Engine.mpc_run_plant returns the same with N = n * hold applied knots in xs_closed [B, N+1, nx] and us_closed
+    [B, N, nu_user], plus closed_cost [B] (None when not asked for), failed_knot [B] (int32; -1: none) and hold."""
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
@@ -479,6 +481,53 @@ class Engine(object):
         return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
                          status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t(),
                          reference_row=self.reference_row)
+
+    def mpc_run_plant(self, sp, n_steps, first_maxiter, iters_per_step, hold=1, plant_stiffness=None, plant_motor_inertia=None,
+                      disturbance=None, clamp=False, closed_cost=True):
+        """mpc_run on a plant of its own (aslr_mpc_run_plant, include/aslr_to_amd_mpc_plant.h): every control step solves
+        as mpc_run does, then applies `hold` knots of the plan to the plant -- the first control as it is, the later ones
+        with the Riccati feedback u = us_j - K_j (x - xs_j) -- and shifts the plan by hold.  Batch-major arrays or tensors,
+        each optional: plant_stiffness, plant_motor_inertia [B, nj] (diagonals of the plant's K and B; None: the
+        trajectory's own), disturbance [B, N, nx] with N = n_steps * hold (added to the next state of every applied knot).
+        clamp: clamp the applied control to the box.  -> MpcResult with xs_closed [B, N+1, nx], us_closed [B, N, nu_user], the
+        per-step fields of mpc_run, closed_cost [B] (the running costs of the applied knots, NaN for a failed trajectory;
+        None with closed_cost=False), failed_knot [B] and hold.  A non-positive plant inertia is not checked (it lives on
+        the device) and shows up in failed_knot."""
+        torch = _torch()
+        n, h, nj = int(n_steps), int(hold), self.nx // 4
+        N = max(n, 0) * max(h, 0)
+
+        def dev(v, shape, perm, name):
+            if v is None:
+                return None
+            t = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
+                                device=self.device)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must have shape %s, not %s" % (name, list(shape), list(t.shape)))
+            return t.permute(*perm).contiguous()
+
+        with torch.cuda.device(self.device):
+            pk = dev(plant_stiffness, (self.B, nj), (1, 0), "plant_stiffness")
+            pb = dev(plant_motor_inertia, (self.B, nj), (1, 0), "plant_motor_inertia")
+            dist = dev(disturbance, (self.B, N, self.nx), (1, 0, 2), "disturbance")
+            m = max(n, 0)
+            xc = torch.zeros((N + 1, self.B, self.nx), dtype=torch.float64, device=self.device)
+            uc = torch.zeros((N, self.B, self.nu), dtype=torch.float64, device=self.device)
+            sf = torch.zeros((m, 4, self.B), dtype=torch.float64, device=self.device)
+            si = torch.zeros((m, 2, self.B), dtype=torch.int32, device=self.device)
+            cc = torch.zeros((self.B,), dtype=torch.float64, device=self.device) if closed_cost else None
+            fk = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
+        mpc = _abi.Mpc()
+        mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, int(first_maxiter), int(iters_per_step)
+        mpc.disturbance = dist.data_ptr() if dist is not None else None
+        mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = xc.data_ptr(), uc.data_ptr(), sf.data_ptr(), si.data_ptr()
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._call("aslr_mpc_run_plant", C.byref(sp), C.byref(mpc), h, ptr(pk), ptr(pb), 1 if clamp else 0, ptr(cc), ptr(fk),
+                   self._stream())
+        torch.cuda.synchronize(self.device)  # (the time-major copies of the inputs die on return)
+        return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
+                         status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t(),
+                         reference_row=self.reference_row, closed_cost=cc, failed_knot=fk, hold=h)
 
     def traj_f(self, row):
         return self.region(_abi.R_TRAJ_F)[row]

@@ -6,7 +6,15 @@ n_steps = 50, iters_per_step = 2, first solve 2 iterations, disturbance U(-1e-3,
 Both start from the empty candidate on a fresh handle each repetition (a run moves X0), are warmed up once and then
 timed REPS times, alternating (a) and (b), wall clock around a device synchronisation; the medians and the spread are
 reported in one JSON line.
-usage: python tools/time_mpc.py [B] [T] [n_steps] [iters_per_step] [reps]"""
+usage: python tools/time_mpc.py [B] [T] [n_steps] [iters_per_step] [reps]
+
+With a sixth argument `plant` the comparison is instead between aslr_mpc_run and aslr_mpc_run_plant on the same shape
+(include/aslr_to_amd_mpc_plant.h), alternating per repetition:
+  (a) mpc:          Engine.mpc_run, n_steps control steps (the one-knot calc launch + mpc_advance_kernel between solves);
+  (c) plant hold=1: Engine.mpc_run_plant with the motor-inertia plant given (within +-20 % of the model's) and the closed cost
+                    requested, n_steps control steps (mpc_plant_kernel + mpc_advance_hold_kernel between solves);
+  (d) plant hold=4: the same with hold = 4 and n_steps / 4 control steps, reported per control step and per APPLIED KNOT.
+usage: python tools/time_mpc.py 4096 100 48 3 7 plant"""
 import json
 import os
 import sys
@@ -40,17 +48,43 @@ def host(e):
     torch.cuda.synchronize()
 
 
-def timed(fn):
+def timed(fn, steps=N):
     e = Engine(low)
     e.set_candidate(None, None)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     fn(e)
-    ms = (time.perf_counter() - t0) * 1e3 / N
+    ms = (time.perf_counter() - t0) * 1e3 / steps
     e.close()
     return ms
 
 
+def plant_mode():
+    nj = low.nj
+    diag_b = np.array([low.desc.models[0].B[j * nj + j] for j in range(nj)])   # (the scenario has no table: the model's diagonal)
+    pb = diag_b * np.random.default_rng(11).uniform(0.8, 1.2, (B, nj))
+    assert N % 4 == 0, "n_steps must be a multiple of 4 for the hold = 4 run"
+    runs = {"mpc": (N, lambda e: e.mpc_run(sp, N, PER, PER, dist_bm)),
+            "plant_hold1": (N, lambda e: e.mpc_run_plant(sp, N, PER, PER, 1, None, pb, dist_bm, True, True)),
+            "plant_hold4": (N // 4, lambda e: e.mpc_run_plant(sp, N // 4, PER, PER, 4, None, pb, dist_bm, True, True))}
+    ms = {k: [] for k in runs}
+    for rep in range(REPS + 1):   # (repetition 0 is the warm-up)
+        for k, (steps, fn) in runs.items():
+            t = timed(fn, steps)
+            if rep:
+                ms[k].append(t)
+    out = dict(B=B, T=T, n_steps=N, iters_per_step=PER, reps=REPS, gpu=torch.cuda.get_device_name(0))
+    for k, v in ms.items():
+        out[k + "_ms_per_step"] = float(np.median(v))
+        out[k + "_ms_min_max"] = [min(v), max(v)]
+    out["plant_hold4_ms_per_applied_knot"] = out["plant_hold4_ms_per_step"] / 4
+    out["plant_hold1_over_mpc"] = out["plant_hold1_ms_per_step"] / out["mpc_ms_per_step"]
+    print(json.dumps(out))
+
+
+if len(sys.argv) > 6 and sys.argv[6] == "plant":
+    plant_mode()
+    sys.exit(0)
 for fn in (device, host):   # warm-up: code objects, torch's copy kernels, the allocator
     timed(fn)
 a, b = [], []
