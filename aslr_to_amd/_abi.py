@@ -89,6 +89,13 @@ class TrajParams(C.Structure):
                 ("u_ub", C.POINTER(_d))]
 
 
+class PoolParams(C.Structure):
+    """aslr_pool_params_t (include/aslr_to_amd_pool_params.h): nullable HOST tables [P][nj] / [P][nu] with one row per pool
+    problem, and the DEVICE scratch [2 nj + 2 nu][P] the call uploads the lowered table to (aslr_solve_pool_params)."""
+    _fields_ = [("stiffness", C.POINTER(_d)), ("motor_inertia", C.POINTER(_d)), ("u_lb", C.POINTER(_d)),
+                ("u_ub", C.POINTER(_d)), ("params_dev", C.c_void_p)]
+
+
 class Mpc(C.Structure):
     """aslr_mpc_t: a receding-horizon run (aslr_mpc_run); device pointers, time-major arrays."""
     _fields_ = [("n_steps", _i), ("first_maxiter", _i), ("iters_per_step", _i), ("_pad0", _i),
@@ -175,6 +182,9 @@ POLICY_SYMBOLS = ["aslr_policy_rollout"]
 # what include/aslr_to_amd_mpc_plant.h declares: a third extension header, in a list of its own for the same reason
 MPC_PLANT_SYMBOLS = ["aslr_mpc_run_plant"]
 
+# what include/aslr_to_amd_pool_params.h declares: a fourth extension header, in a list of its own for the same reason
+POOL_PARAMS_SYMBOLS = ["aslr_solve_pool_params"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -256,6 +266,9 @@ def load_library():
     lib.aslr_policy_rollout.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.aslr_mpc_run_plant.restype = C.c_int
     lib.aslr_mpc_run_plant.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    lib.aslr_solve_pool_params.restype = C.c_int
+    lib.aslr_solve_pool_params.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Pool), C.POINTER(PoolParams), i32, i32, vp,
+                                           C.POINTER(i32)]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

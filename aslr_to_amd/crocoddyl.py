@@ -488,12 +488,15 @@ class SolverDDP(object):
                                disturbance, bool(clamp), bool(closed_cost))
 
     def solve_pool(self, x0s, frame_refs=None, maxiter=100, isFeasible=False, regInit=None, refill_every=4,
-                   poll_every=16, init_xs=None, init_us=None):
+                   poll_every=16, init_xs=None, init_us=None, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
         """Solve MANY problems of this solver's structure (per-problem x0 and, optionally, frame-placement targets as
         pinocchio.SE3 or [P, 12] arrays), each from a cold start to its own stop, streaming them through the problem's
         trajectory slots (the loop `for x0 in x0s: solver.solve([], [], maxiter)` of a script, run on the device:
         aslr_solve_pool).  -> dict of torch tensors: xs [P, T+1, nx], us [P, T, nu], cost, stop, x_reg, step, iters,
-        status [P], and batch_iters."""
+        status [P], and batch_iters.
+        stiffness / motor_inertia [P, nj], u_lb / u_ub [P, nu], each optional: problem j is solved with row j of every given
+        field, i.e. with action models whose K, B and control box are that row's (a design sweep streamed through the slots:
+        aslr_solve_pool_params); a field left out keeps the models' constant."""
         sp = self._sp
         sp.maxiter = int(maxiter)
         sp.is_feasible = 1 if isFeasible else 0
@@ -502,7 +505,8 @@ class SolverDDP(object):
         fr = None
         if frame_refs is not None:
             fr = np.array([f.as12() if hasattr(f, "as12") else np.asarray(f, dtype=np.float64).reshape(12) for f in frame_refs])
-        return self.problem.engine.solve_pool(x0s, fr, sp, refill_every, poll_every, init_xs, init_us)
+        return self.problem.engine.solve_pool(x0s, fr, sp, refill_every, poll_every, init_xs, init_us, stiffness,
+                                              motor_inertia, u_lb, u_ub)
 
     def cost_sensitivity(self):
         """problem.cost_sensitivity() at this solver's solution (the committed xs / us of the last solve): per

@@ -6,9 +6,11 @@
 #include <vector>
 
 #include "aslr_common.hpp"
+#include "aslr_pool_params.hpp"
 #include "../../include/aslr_to_amd_sens.h"
 #include "../../include/aslr_to_amd_policy.h"
 #include "../../include/aslr_to_amd_mpc_plant.h"
+#include "../../include/aslr_to_amd_pool_params.h"
 
 using namespace aslr;
 
@@ -692,6 +694,9 @@ struct IterOpts {
   int maxiter_traj; // SolverDev::maxiter_traj (pool solves)
   bool full_first;  // the first sweep of this call evaluates every knot of every trajectory (diff_mode)
   hipEvent_t *ev;   // four events around calcDiff / backward / forward of one whole-shard iteration, or nullptr
+  // the first sweep of this call writes the model-only record chunks whatever the handle's mark says (aslr_solve_pool_params:
+  // the refill before it has given slots other parameters, and those chunks depend on them)
+  bool fresh_first = false;
 };
 
 int record(hipEvent_t *ev, int i, hipStream_t st) {
@@ -700,14 +705,17 @@ int record(hipEvent_t *ev, int i, hipStream_t st) {
 }
 
 // one lock-step iteration of the trajectories [b0, b1) on stream st
-int iterate_range(aslr_problem *p, const aslr_solver_params_t *sp, bool first, bool full, const IterOpts &o, int b0, int b1, hipStream_t st) {
+// (fresh: IterOpts::fresh_first applies to this iteration)
+int iterate_range(aslr_problem *p, const aslr_solver_params_t *sp, bool first, bool full, const IterOpts &o, int b0, int b1, hipStream_t st, bool fresh = false) {
   KArgs k = o.k;
   k.b0 = b0; k.b1 = b1;
   int rc = first ? launch_init_state(k, sp, st) : ASLR_OK;
   SolverDev sd = to_dev(sp, 0, 0);
   sd.maxiter_traj = o.maxiter_traj;
+  int mode = diff_mode(p, k, kModeCommit | kModeSolver, full);
+  if (fresh) mode &= ~kModeSkipConst;
   if (!rc) rc = record(o.ev, 0, st);
-  if (!rc) rc = p->ks->calc(k, true, diff_mode(p, k, kModeCommit | kModeSolver, full), sp->th_gaptol, st);
+  if (!rc) rc = p->ks->calc(k, true, mode, sp->th_gaptol, st);
   if (!rc) rc = record(o.ev, 1, st);
   if (!rc) rc = launch_backward(p, k, sd, st);
   if (!rc) rc = record(o.ev, 2, st);
@@ -720,7 +728,7 @@ int iterate_range(aslr_problem *p, const aslr_solver_params_t *sp, bool first, b
 int iterate(aslr_problem *p, const aslr_solver_params_t *sp, bool first, int n, hipStream_t st, const IterOpts &o) {
   if (p->nsub <= 1 || o.ev) { // (timed: the whole shard on the caller's stream, whatever aslr_set_subshards says)
     for (int it = 0; it < n; ++it)
-      if (int rc = iterate_range(p, sp, first && it == 0, o.full_first && it == 0, o, 0, p->desc.B, st)) return rc;
+      if (int rc = iterate_range(p, sp, first && it == 0, o.full_first && it == 0, o, 0, p->desc.B, st, o.fresh_first && it == 0)) return rc;
     return ASLR_OK;
   }
   // Each sub-shard runs its n iterations on its own stream with no synchronisation between sub-shards (trajectories
@@ -731,7 +739,7 @@ int iterate(aslr_problem *p, const aslr_solver_params_t *sp, bool first, int n, 
   for (int s = 1; s < p->nsub; ++s) HIP_TRY(hipStreamWaitEvent(p->sub_stream[s], p->sub_fork, 0));
   for (int it = 0; it < n; ++it)
     for (int s = 0; s < p->nsub; ++s)
-      if (int rc = iterate_range(p, sp, first && it == 0, o.full_first && it == 0, o, p->sub_b[s], p->sub_b[s + 1], s == 0 ? st : p->sub_stream[s])) return rc;
+      if (int rc = iterate_range(p, sp, first && it == 0, o.full_first && it == 0, o, p->sub_b[s], p->sub_b[s + 1], s == 0 ? st : p->sub_stream[s], o.fresh_first && it == 0)) return rc;
   for (int s = 1; s < p->nsub; ++s) { // join: st waits for every sub-shard stream
     HIP_TRY(hipEventRecord(p->sub_join[s], p->sub_stream[s]));
     HIP_TRY(hipStreamWaitEvent(st, p->sub_join[s], 0));
@@ -772,6 +780,56 @@ int mpc_refusals(const char *fn, const aslr_problem *p, const aslr_solver_params
   if (!p->uniform_running) return fail(ASLR_E_INVALID, "%s: the running knots use more than one action model: shifting the plan needs one (references that vary along the horizon: aslr_set_reference_path)", fn);
   if (p->k.iter_log) return fail(ASLR_E_INVALID, "%s: an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)", fn);
   return solver_unsupported(fn, p, sp->solver);
+}
+
+// The parameter table of `n` columns -- the trajectories of the shard (aslr_set_trajectory_params) or the problems of a pool
+// (aslr_solve_pool_params) -- validated against the models and lowered to the layout of region TRAJ_PARAMS, [rows][n]: K,
+// 1 / B (formed here, on the host), u_lb, u_ub.  tp's arrays are HOST [n][nj] / [n][nu].  fn: the entry point a refusal names.
+int build_param_rows(const char *fn, const aslr_problem *p, const aslr_traj_params_t *tp, int n, std::vector<double> *out) {
+  const int nj = p->nj, nu = p->nu, nm = p->desc.nmodels;
+  const aslr_model_t *M = p->desc.models;
+  if (tp->stiffness && p->dam == ASLR_DAM_VSA) return fail(ASLR_E_INVALID, "%s: a VSA model takes its stiffness from u: no stiffness table", fn);
+  bool any_limits = false;
+  for (int i = 0; i < nm; ++i) {
+    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "%s: K and B of every model must be diagonal", fn);
+    any_limits = any_limits || M[i].has_u_limits;
+  }
+  if ((tp->u_lb || tp->u_ub) && !any_limits) return fail(ASLR_E_INVALID, "%s: u_lb / u_ub given, but no model of the problem has control limits", fn);
+  // a field left out keeps the models' constant: one value per column, so the models must agree on it
+  const aslr_model_t *ML = nullptr; // a model with limits (their source when a bound is left out)
+  for (int i = 0; i < nm; ++i) {
+    for (int j = 0; j < nj; ++j) {
+      if (!tp->stiffness && p->dam == ASLR_DAM_SEA && M[i].K[j * nj + j] != M[0].K[j * nj + j]) return fail(ASLR_E_INVALID, "%s: the models differ in K: give the stiffness table", fn);
+      if (!tp->motor_inertia && M[i].B[j * nj + j] != M[0].B[j * nj + j]) return fail(ASLR_E_INVALID, "%s: the models differ in B: give the motor_inertia table", fn);
+    }
+    if (!M[i].has_u_limits) continue;
+    if (!ML) ML = &M[i];
+    for (int c = 0; c < nu; ++c) {
+      if (!tp->u_lb && M[i].u_lb[c] != ML->u_lb[c]) return fail(ASLR_E_INVALID, "%s: the models differ in u_lb: give the u_lb table", fn);
+      if (!tp->u_ub && M[i].u_ub[c] != ML->u_ub[c]) return fail(ASLR_E_INVALID, "%s: the models differ in u_ub: give the u_ub table", fn);
+    }
+  }
+  const int rows = traj_params_rows_c(nj, nu);
+  std::vector<double> h((size_t)rows * n);
+  for (int b = 0; b < n; ++b) {
+    for (int j = 0; j < nj; ++j) {
+      const double k = p->dam == ASLR_DAM_VSA ? 0.0 : (tp->stiffness ? tp->stiffness[(size_t)b * nj + j] : M[0].K[j * nj + j]);
+      const double bi = tp->motor_inertia ? tp->motor_inertia[(size_t)b * nj + j] : M[0].B[j * nj + j];
+      if (!std::isfinite(k)) return fail(ASLR_E_INVALID, "%s: stiffness entries must be finite", fn);
+      if (!(std::isfinite(bi) && bi > 0.0)) return fail(ASLR_E_INVALID, "%s: motor_inertia entries must be finite and > 0", fn);
+      h[(size_t)j * n + b] = k;
+      h[(size_t)(nj + j) * n + b] = 1.0 / bi;
+    }
+    for (int c = 0; c < nu; ++c) {
+      const double lb = tp->u_lb ? tp->u_lb[(size_t)b * nu + c] : (ML ? ML->u_lb[c] : 0.0);
+      const double ub = tp->u_ub ? tp->u_ub[(size_t)b * nu + c] : (ML ? ML->u_ub[c] : 0.0);
+      if (!(lb <= ub)) return fail(ASLR_E_INVALID, "%s: u_lb <= u_ub must hold in every entry (no NaN)", fn);
+      h[(size_t)(2 * nj + c) * n + b] = lb;
+      h[(size_t)(2 * nj + nu + c) * n + b] = ub;
+    }
+  }
+  out->swap(h);
+  return ASLR_OK;
 }
 
 } // namespace
@@ -892,48 +950,8 @@ int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, 
     p->const_written = false;
   };
   if (!tp) { switch_to(false); return ASLR_OK; }
-  const int B = p->desc.B, nj = p->nj, nu = p->nu, nm = p->desc.nmodels;
-  const aslr_model_t *M = p->desc.models;
-  if (tp->stiffness && p->dam == ASLR_DAM_VSA) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: a VSA model takes its stiffness from u: no stiffness table");
-  bool any_limits = false;
-  for (int i = 0; i < nm; ++i) {
-    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: K and B of every model must be diagonal");
-    any_limits = any_limits || M[i].has_u_limits;
-  }
-  if ((tp->u_lb || tp->u_ub) && !any_limits) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: u_lb / u_ub given, but no model of the problem has control limits");
-  // a field left out keeps the models' constant: one value per column, so the models must agree on it
-  const aslr_model_t *ML = nullptr; // a model with limits (their source when a bound is left out)
-  for (int i = 0; i < nm; ++i) {
-    for (int j = 0; j < nj; ++j) {
-      if (!tp->stiffness && p->dam == ASLR_DAM_SEA && M[i].K[j * nj + j] != M[0].K[j * nj + j]) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: the models differ in K: give the stiffness table");
-      if (!tp->motor_inertia && M[i].B[j * nj + j] != M[0].B[j * nj + j]) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: the models differ in B: give the motor_inertia table");
-    }
-    if (!M[i].has_u_limits) continue;
-    if (!ML) ML = &M[i];
-    for (int c = 0; c < nu; ++c) {
-      if (!tp->u_lb && M[i].u_lb[c] != ML->u_lb[c]) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: the models differ in u_lb: give the u_lb table");
-      if (!tp->u_ub && M[i].u_ub[c] != ML->u_ub[c]) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: the models differ in u_ub: give the u_ub table");
-    }
-  }
-  const int rows = traj_params_rows_c(nj, nu);
-  std::vector<double> h((size_t)rows * B);
-  for (int b = 0; b < B; ++b) {
-    for (int j = 0; j < nj; ++j) {
-      const double k = p->dam == ASLR_DAM_VSA ? 0.0 : (tp->stiffness ? tp->stiffness[(size_t)b * nj + j] : M[0].K[j * nj + j]);
-      const double bi = tp->motor_inertia ? tp->motor_inertia[(size_t)b * nj + j] : M[0].B[j * nj + j];
-      if (!std::isfinite(k)) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: stiffness entries must be finite");
-      if (!(std::isfinite(bi) && bi > 0.0)) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: motor_inertia entries must be finite and > 0");
-      h[(size_t)j * B + b] = k;
-      h[(size_t)(nj + j) * B + b] = 1.0 / bi;
-    }
-    for (int c = 0; c < nu; ++c) {
-      const double lb = tp->u_lb ? tp->u_lb[(size_t)b * nu + c] : (ML ? ML->u_lb[c] : 0.0);
-      const double ub = tp->u_ub ? tp->u_ub[(size_t)b * nu + c] : (ML ? ML->u_ub[c] : 0.0);
-      if (!(lb <= ub)) return fail(ASLR_E_INVALID, "aslr_set_trajectory_params: u_lb <= u_ub must hold in every entry (no NaN)");
-      h[(size_t)(2 * nj + c) * B + b] = lb;
-      h[(size_t)(2 * nj + nu + c) * B + b] = ub;
-    }
-  }
+  std::vector<double> h;
+  if (int rc = build_param_rows("aslr_set_trajectory_params", p, tp, p->desc.B, &h)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   HIP_TRY(hipMemcpyAsync(region(p, ASLR_R_TRAJ_PARAMS), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1309,6 +1327,110 @@ int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const asl
   if (iters_done) *iters_done = it;
   if (rc) return rc;
   if (fin_total < pool->P) return fail(ASLR_E_INVALID, "aslr_solve_pool: %d of %d problems finished within the iteration bound", fin_total, pool->P);
+  return launch_reset_accepted(p->k, st);
+}
+
+// aslr_solve_pool with per-problem K, 1 / B and control box (include/aslr_to_amd_pool_params.h).
+// The loop is aslr_solve_pool's, restated rather than shared so that the older call stays the code its tests pin.  What
+// differs: the refill kernel also hands a slot its problem's column of the parameter table, the TP kernel set iterates while
+// the call runs, and the first calcDiff sweep after EVERY refill launches without kModeSkipConst (IterOpts::fresh_first).
+int aslr_solve_pool_params(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool,
+                           const aslr_pool_params_t *pp, int32_t refill_every, int32_t poll_every, void *stream,
+                           int32_t *iters_done) {
+  if (!pp || (!pp->stiffness && !pp->motor_inertia && !pp->u_lb && !pp->u_ub))
+    return aslr_solve_pool(p, sp, pool, refill_every, poll_every, stream, iters_done);
+  const char *fn = "aslr_solve_pool_params";
+  // ---- what aslr_solve_pool refuses, under this call's name ----
+  if (!p) return no_handle(fn);
+  if (!sp || !pool) return fail(ASLR_E_INVALID, "%s: %s is NULL", fn, !sp ? "sp" : "pool");
+  if (pool->P <= 0) return fail(ASLR_E_INVALID, "%s: pool->P = %d must be >= 1", fn, pool->P);
+  if (!pool->x0 || !pool->xs_out || !pool->us_out || !pool->stat_f || !pool->stat_i || !pool->slot_problem || !pool->counters)
+    return fail(ASLR_E_INVALID, "%s: x0, xs_out, us_out, stat_f, stat_i, slot_problem and counters of the pool must be given", fn);
+  if (sp->maxiter <= 0 || sp->fixed_iterations)
+    return fail(ASLR_E_INVALID, "%s: sp->maxiter = %d must be >= 1 and sp->fixed_iterations = %d must be 0 (slots stop by themselves)", fn, sp->maxiter, sp->fixed_iterations);
+  if (pool->frame_ref && !p->k.frame_ref)
+    return fail(ASLR_E_INVALID, "%s: per-problem frame references need a problem created with a frame_ref table", fn);
+  // ---- its own ----
+  if (p->ks->traj_params)
+    return fail(ASLR_E_INVALID, "%s: the handle has a per-trajectory parameter table set (the refill overwrites region TRAJ_PARAMS: the table would be lost); clear it with aslr_set_trajectory_params(p, NULL, stream), or give its rows in pp", fn);
+  if (p->ref_path_set)
+    return fail(ASLR_E_INVALID, "%s: the handle has a reference path set (a pool problem would inherit its slot's path); clear it with aslr_set_reference_path(p, NULL, 0, 0, stream)", fn);
+  if (int rc = solver_unsupported(fn, p, sp->solver)) return rc;
+  if (!pp->params_dev) return fail(ASLR_E_INVALID, "%s: params_dev is NULL while a parameter field is given (DEVICE scratch of [2 nj + 2 nu][P] doubles)", fn);
+  const KernelSet *tp_set = find_kernel_set(p->nj, p->dam, true), *plain_set = p->ks;
+  if (!tp_set) return fail(ASLR_E_INVALID, "%s: no per-trajectory-parameter kernels for (nj=%d, dam=%d)", fn, p->nj, p->dam);
+  const aslr_traj_params_t tp{pp->stiffness, pp->motor_inertia, pp->u_lb, pp->u_ub};
+  std::vector<double> h; // [rows][P]
+  if (int rc = build_param_rows(fn, p, &tp, pool->P, &h)) return rc;
+
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int B = p->desc.B;
+  if (refill_every <= 0) refill_every = 4;
+  if (poll_every <= 0) poll_every = 4 * refill_every;
+  if (poll_every > sp->maxiter + refill_every) poll_every = sp->maxiter + refill_every; // (a short maxiter must still be polled)
+  HIP_TRY(hipMemcpyAsync(pp->params_dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st)); // (h is pageable: the copy is staged, and the vector may die at any return below)
+  PoolParamsDev pl;
+  pl.P = pool->P; pl.nx = p->nx; pl.nu = p->nu; pl.rows = traj_params_rows_c(p->nj, p->nu);
+  pl.x0 = pool->x0; pl.frame_ref = pool->frame_ref; pl.xs_out = pool->xs_out; pl.us_out = pool->us_out;
+  pl.xs_init = pool->xs_init; pl.us_init = pool->us_init;
+  pl.stat_f = pool->stat_f; pl.stat_i = pool->stat_i; pl.slot_problem = pool->slot_problem; pl.counters = pool->counters;
+  pl.params = pp->params_dev;
+  pl.traj_params = reinterpret_cast<double *>(region(p, ASLR_R_TRAJ_PARAMS));
+  // every slot starts idle; the first refill hands out the first B problems
+  HIP_TRY(hipMemsetAsync(pool->slot_problem, 0xFF, sizeof(int32_t) * B, st));
+  HIP_TRY(hipMemsetAsync(pool->counters, 0, sizeof(int32_t) * 2, st));
+  HIP_TRY(hipMemsetAsync(p->k.traj_i + (size_t)ASLR_TI_DONE * B, 0, sizeof(int32_t) * B, st));
+  double *save = reinterpret_cast<double *>(region(p, ASLR_R_POOL_SAVE)); // (the handle's own x0 / frame_ref, as aslr_solve_pool)
+  HIP_TRY(hipMemcpyAsync(save, p->k.x0, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st));
+  if (p->k.frame_ref) HIP_TRY(hipMemcpyAsync(save + (size_t)B * p->nx, p->k.frame_ref, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st));
+  // While the call runs the handle iterates with the kernels that read TRAJ_PARAMS.  The model-only record chunks in place
+  // belong to the models' constants: the mark is cleared, so the first sweep that covers every slot sets it again.
+  p->ks = tp_set;
+  p->const_written = false;
+  IterOpts o{p->k, sp->maxiter, pool->P >= B, nullptr};
+  o.k.iter_log = nullptr; o.k.log_cap = 0; // (a slot's iteration index restarts with every problem)
+  if (pool->frame_ref) o.k.planar_reach = 0; // (pool targets take the general log map)
+  // Every round starts with a refill, and a refilled slot may hold another design than before: the round's first sweep
+  // writes every record chunk of the trajectories it evaluates (a refilled slot has RECALC set and DONE clear, so
+  // calc_kernel passes each of its knots through the store path without SKIPC; the sweeps in between keep the skip)
+  o.fresh_first = true;
+  const auto refill = [&]() { return launch_pool_refill_params(o.k, pl, reg_start(sp), sp->is_feasible, st); };
+  const auto flush_and_count = [&](int32_t *fin) -> int {
+    if (int rc = refill()) return rc;
+    HIP_TRY(hipMemcpyAsync(p->h_done, pl.counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *fin = p->h_done[0];
+    return ASLR_OK;
+  };
+  int it = 0, rc = ASLR_OK;
+  const long long cap = ((long long)(pool->P + B - 1) / B + 1) * (long long)(sp->maxiter + refill_every);
+  while (it < cap) {
+    rc = refill();
+    if (!rc) rc = iterate(p, sp, false, refill_every, st, o);
+    if (rc) break;
+    o.full_first = false; // (later rounds evaluate the refilled slots only)
+    it += refill_every;
+    if (it % poll_every < refill_every) {
+      int32_t fin = 0;
+      rc = flush_and_count(&fin);
+      if (rc || fin >= pool->P) break;
+    }
+  }
+  int32_t fin_total = -1;
+  if (!rc) rc = flush_and_count(&fin_total);
+  {
+    hipError_t e = hipMemcpyAsync(const_cast<double *>(p->k.x0), save, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && p->k.frame_ref) e = hipMemcpyAsync(const_cast<double *>(p->k.frame_ref), save + (size_t)B * p->nx, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess && !rc) rc = fail(ASLR_E_HIP, "%s: putting the handle's x0 / frame_ref back failed: %s", fn, hipGetErrorString(e));
+  }
+  // back on the models' constants; the record chunks in place belong to the last designs of the slots: the next sweep of
+  // the handle rewrites them (as after aslr_set_trajectory_params)
+  p->ks = plain_set;
+  p->const_written = false;
+  if (iters_done) *iters_done = it;
+  if (rc) return rc;
+  if (fin_total < pool->P) return fail(ASLR_E_INVALID, "%s: %d of %d problems finished within the iteration bound", fn, fin_total, pool->P);
   return launch_reset_accepted(p->k, st);
 }
 

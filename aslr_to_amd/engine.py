@@ -404,12 +404,17 @@ class Engine(object):
                        C.c_void_p(du.data_ptr()), C.c_void_p(r.data_ptr()), self._stream())
         return r[:, :nr].cpu().numpy()
 
-    def solve_pool(self, x0s, frame_refs, sp, refill_every=4, poll_every=16, xs_init=None, us_init=None):
+    def solve_pool(self, x0s, frame_refs, sp, refill_every=4, poll_every=16, xs_init=None, us_init=None, stiffness=None,
+                   motor_inertia=None, u_lb=None, u_ub=None):
         """A pool of P problems of this engine's structure solved through its B slots, each to its own convergence
         (aslr_solve_pool: stopped slots are flushed and refilled on the device; every problem is cold-started).
         x0s [P, nx], frame_refs [P, 12] or None, xs_init [P, T+1, nx] / us_init [P, T, nu] or None = zeros (host or
         device).  -> dict of device tensors: xs [P, T+1, nx],
-        us [P, T, nu], cost / stop / x_reg / step [P], iters / status [P] (int32), and batch_iters (int)."""
+        us [P, T, nu], cost / stop / x_reg / step [P], iters / status [P] (int32), and batch_iters (int).
+        stiffness / motor_inertia [P, nj], u_lb / u_ub [P, nu] (or the models' own narrower nu, padded as lower_traj_params
+        says), host arrays, each optional: problem j is solved with row j of every given field, a field left out keeps the
+        models' constant (aslr_solve_pool_params: a design sweep through the pool).  With all four None the call is
+        aslr_solve_pool as before; otherwise the result also holds params, the lowered table [2 nj + 2 nu, P] on the device."""
         torch = _torch()
         with torch.cuda.device(self.device):
             x0 = torch.as_tensor(x0s, dtype=torch.float64, device=self.device).contiguous()
@@ -444,6 +449,20 @@ class Engine(object):
         pool.xs_init = xi.data_ptr() if xi is not None else None
         pool.us_init = ui.data_ptr() if ui is not None else None
         it = C.c_int32(0)
+        low = self.low
+        tp = lower_traj_params(low.desc, low.nj, low.nu, self.nu_user, low.dam, stiffness, motor_inertia, u_lb, u_ub, rows=P)
+        if tp is not None:
+            with torch.cuda.device(self.device):
+                params = torch.empty((2 * low.nj + 2 * low.nu, P), dtype=torch.float64, device=self.device)
+            pp = _abi.PoolParams()
+            for name, a in tp.items():
+                setattr(pp, name, a.ctypes.data_as(C.POINTER(C.c_double)))
+            pp.params_dev = params.data_ptr()
+            self._call("aslr_solve_pool_params", C.byref(sp), C.byref(pool), C.byref(pp), int(refill_every), int(poll_every),
+                       self._stream(), C.byref(it))
+            torch.cuda.synchronize(self.device)
+            return dict(xs=xs, us=self.cut_u(us), cost=sf[:, 0], stop=sf[:, 1], x_reg=sf[:, 2], step=sf[:, 3], iters=si[:, 0],
+                        status=si[:, 1], batch_iters=it.value, params=params)
         self._call("aslr_solve_pool", C.byref(sp), C.byref(pool), int(refill_every), int(poll_every), self._stream(),
                    C.byref(it))
         torch.cuda.synchronize(self.device)

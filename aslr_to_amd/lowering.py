@@ -53,16 +53,18 @@ def lower_reference_path(desc, path, row0=0):
 TRAJ_PARAM_FIELDS = ("stiffness", "motor_inertia", "u_lb", "u_ub")
 
 
-def lower_traj_params(desc, nj, nu, nu_user, dam, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
+def lower_traj_params(desc, nj, nu, nu_user, dam, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None, rows=None):
     """Validate a per-trajectory parameter table against a lowered description (the checks aslr_set_trajectory_params
     repeats on its side) and bring it to the device's sizes: -> dict of C-contiguous float64 arrays, stiffness /
     motor_inertia [B, nj] and u_lb / u_ub [B, nu], holding the given fields only; None when no field is given.
     Bounds of width nu_user < nu (one-command pendulum actuation) are padded with the box the models give their padded
-    commands, [-1, 1] (models._DifferentialBase.lower): the padded commands stay at zero inside it."""
+    commands, [-1, 1] (models._DifferentialBase.lower): the padded commands stay at zero inside it.
+    rows: the number of rows when it is not the shard's B -- the P problems of a pool (Engine.solve_pool)."""
     given = dict(stiffness=stiffness, motor_inertia=motor_inertia, u_lb=u_lb, u_ub=u_ub)
     if all(v is None for v in given.values()):
         return None
-    B = desc.B
+    B = desc.B if rows is None else int(rows)
+    per = "trajectory" if rows is None else "pool problem"
     models = [desc.models[i] for i in range(desc.nmodels)]
     out = {}
     for name, v in given.items():
@@ -72,9 +74,9 @@ def lower_traj_params(desc, nj, nu, nu_user, dam, stiffness=None, motor_inertia=
         # accepted widths (the first one is named in the messages) and the width on the device
         widths, width = ((nj,), nj) if name in ("stiffness", "motor_inertia") else ((nu_user, nu), nu)
         if a.ndim != 2 or a.shape[0] != B:
-            raise ValueError("%s needs one row per trajectory ([%d, %d]), got shape %r" % (name, B, widths[0], a.shape))
+            raise ValueError("%s needs one row per %s ([%d, %d]), got shape %r" % (name, per, B, widths[0], a.shape))
         if a.shape[1] not in widths:
-            raise ValueError("%s must have %d entries per trajectory, got %d" % (name, widths[0], a.shape[1]))
+            raise ValueError("%s must have %d entries per %s, got %d" % (name, widths[0], per, a.shape[1]))
         if a.shape[1] < width:
             a = np.concatenate([a, np.full((B, width - a.shape[1]), -1.0 if name == "u_lb" else 1.0)], axis=1)
         out[name] = np.ascontiguousarray(a)
@@ -99,6 +101,24 @@ def lower_traj_params(desc, nj, nu, nu_user, dam, stiffness=None, motor_inertia=
             if np.any(M != np.diag(np.diag(M))):
                 raise ValueError("per-trajectory parameters need diagonal K and B: %s of action model %d is not" % (nm, i))
     return out
+
+
+def param_table(desc, nj, nu, dam, tp, rows):
+    """The table the library builds from the fields `tp` (what lower_traj_params returned) for `rows` columns, in the layout
+    of region TRAJ_PARAMS and of aslr_pool_params_t.params_dev: float64 [2 nj + 2 nu, rows], row-major -- K, 1 / B (the
+    reciprocal formed on the host, as the library forms it), u_lb, u_ub; a field left out repeats the models' constant
+    (model 0's K and B, the first limited model's box, zeros without one; K = 0 for VSA).  Host arithmetic only: the
+    library lowers the fields itself, this is its statement in numpy for checks and tools."""
+    tp = tp or {}
+    m0 = desc.models[0]
+    limited = [desc.models[i] for i in range(desc.nmodels) if desc.models[i].has_u_limits]
+    diag = lambda M: np.array(M[:nj * nj], dtype=np.float64).reshape(nj, nj).diagonal()
+    const = dict(stiffness=diag(m0.K), motor_inertia=diag(m0.B),
+                 u_lb=np.array(limited[0].u_lb[:nu], dtype=np.float64) if limited else np.zeros(nu),
+                 u_ub=np.array(limited[0].u_ub[:nu], dtype=np.float64) if limited else np.zeros(nu))
+    col = {k: (np.asarray(tp[k], dtype=np.float64) if k in tp else np.tile(const[k], (rows, 1))) for k in TRAJ_PARAM_FIELDS}
+    k = np.zeros((rows, nj)) if dam == _abi.DAM_VSA else col["stiffness"]
+    return np.ascontiguousarray(np.concatenate([k, 1.0 / col["motor_inertia"], col["u_lb"], col["u_ub"]], axis=1).T)
 
 
 def lower_problem(x0s, running_models, terminal_model, frame_refs=None, stiffness=None, motor_inertia=None, u_lb=None,

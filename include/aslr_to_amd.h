@@ -310,7 +310,8 @@ typedef struct aslr_traj_params {
  * aslr_calc_diff, aslr_backward_pass, aslr_forward_pass, aslr_iterate*, aslr_solve and aslr_quasi_static, sub-shards
  * included.  aslr_dam_eval / aslr_dam_residuals keep the MODELS' constants (they evaluate a model at arbitrary points,
  * not a trajectory), and aslr_solve_pool declines a handle with a table set (ASLR_E_INVALID: a pool problem would inherit
- * the parameters of whatever slot it lands in).  Returns ASLR_E_INVALID with a message (aslr_last_error) for a bad table;
+ * the parameters of whatever slot it lands in); a pool whose PROBLEMS carry their own parameters is aslr_solve_pool_params
+ * (aslr_to_amd_pool_params.h), which takes one row per problem instead.  Returns ASLR_E_INVALID with a message (aslr_last_error) for a bad table;
  * the handle is then left as it was. */
 int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, void *stream);
 
@@ -382,7 +383,8 @@ int aslr_solve(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t poll_e
  * handle's own are kept in POOL_SAVE and put back before the call returns, so a later aslr_solve / rollout sees the
  * problems the handle was created with.  XS / US / the per-trajectory state are left with the last slot contents
  * (every solver entry point re-initialises them from its own arguments).  A handle with a reference path set
- * (aslr_set_reference_path) is declined, like one with a parameter table.  Pool targets always take the general SE(3)
+ * (aslr_set_reference_path) is declined, like one with a parameter table (per-problem parameters: aslr_solve_pool_params,
+ * aslr_to_amd_pool_params.h).  Pool targets always take the general SE(3)
  * log map (the opt-in closed-form reach residual is validated for the create-time references only).  The call fails
  * (ASLR_E_INVALID, aslr_last_error) if fewer than P problems were flushed within its iteration bound. */
 typedef struct aslr_pool {
