@@ -185,6 +185,9 @@ MPC_PLANT_SYMBOLS = ["aslr_mpc_run_plant"]
 # what include/aslr_to_amd_pool_params.h declares: a fourth extension header, in a list of its own for the same reason
 POOL_PARAMS_SYMBOLS = ["aslr_solve_pool_params"]
 
+# what include/aslr_to_amd_cov.h declares: a fifth extension header, in a list of its own for the same reason
+COV_SYMBOLS = ["aslr_policy_covariance"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -269,6 +272,8 @@ def load_library():
     lib.aslr_solve_pool_params.restype = C.c_int
     lib.aslr_solve_pool_params.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Pool), C.POINTER(PoolParams), i32, i32, vp,
                                            C.POINTER(i32)]
+    lib.aslr_policy_covariance.restype = C.c_int
+    lib.aslr_policy_covariance.argtypes = [vp] * 9
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

@@ -231,12 +231,30 @@ class ShootingProblem(object):
         batch axis: the same for every trajectory; lists of per-knot arrays as the solvers return them do), all three
         None: the policy the engine holds.  The engine's own XS / US / KGAIN are put back afterwards, so a solve in
         progress is not disturbed.  -> engine.PolicyRolloutResult.  This shard's trajectories only."""
-        import torch
         e = self.engine
         if xs is None and us is None and K is None:
             return e.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance, clamp, keep_trajectories)
         if xs is None or us is None or K is None:
             raise ValueError("policy_rollout: give xs, us and K together (or none of them: the engine's own policy)")
+        return self._with_policy(xs, us, K, lambda: e.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0,
+                                                                     disturbance, clamp, keep_trajectories))
+
+    def policy_covariance(self, xs, us, K, sigma0=None, noise_var=None, keep_cov=False):
+        """First-order state and control covariance under the policy u_t = us_t - K_t (x_t - xs_t) (Engine.policy_covariance;
+        aslr_policy_covariance): xs, us, K as policy_rollout takes them, all three None: the policy the engine holds.  The
+        engine's own XS / US / KGAIN are put back afterwards.  -> engine.PolicyCovarianceResult.  This shard's
+        trajectories only."""
+        e = self.engine
+        if xs is None and us is None and K is None:
+            return e.policy_covariance(sigma0, noise_var, keep_cov)
+        if xs is None or us is None or K is None:
+            raise ValueError("policy_covariance: give xs, us and K together (or none of them: the engine's own policy)")
+        return self._with_policy(xs, us, K, lambda: e.policy_covariance(sigma0, noise_var, keep_cov))
+
+    def _with_policy(self, xs, us, K, call):
+        """call() with (xs, us, K) in the engine's XS / US / KGAIN; the engine's own are put back afterwards"""
+        import torch
+        e = self.engine
         keep = [(r, e.region(r).clone()) for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN)]
         try:
             e.set_candidate(xs, us)
@@ -248,11 +266,10 @@ class ShootingProblem(object):
             if tuple(k.shape) != (self.batch, self.T, e.nu, e.nx):
                 raise ValueError("K must have shape [B=%d, T=%d, nu=%d, nx=%d]" % (self.batch, self.T, e.nu_user, e.nx))
             e.region(_abi.R_KGAIN).copy_(k.permute(1, 0, 2, 3))
-            res = e.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance, clamp, keep_trajectories)
+            return call()
         finally:
             for r, t in keep:
                 e.region(r).copy_(t)
-        return res
 
     def _total_cost(self):
         c = self.engine.region(_abi.R_COST).sum(dim=0)
@@ -526,6 +543,17 @@ class SolverDDP(object):
             clamp = self._solver == _abi.SOLVER_BOXDDP
         return self.problem.engine.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance,
                                                   bool(clamp), keep_trajectories)
+
+    def policy_covariance(self, sigma0=None, noise_var=None, keep_cov=False):
+        """What the policy of the last solve (its xs, us and Riccati gains K) does to uncertainty, to first order and without
+        samples: the state covariance Sigma_{t+1} = A_t Sigma_t A_t^T + diag(noise_var_t), A_t = Fx_t - Fu_t K_t, from
+        Sigma_0 = sigma0 ([B, nx, nx] or [nx, nx], symmetric) and process noise of variance noise_var ([B, T, nx], [B, nx]
+        or [nx]; noise t enters x_{t+1}), at least one of the two.  -> engine.PolicyCovarianceResult: x_var [B, T+1, nx],
+        u_var [B, T, nu] (compare its square root with the distance of us to the control box), cov_final [B, nx, nx],
+        cost_increase [B] (the expected cost of the spread in the solver's quadratic model) and cov [B, T+1, nx, nx] with
+        keep_cov.  Every model size, the 7-joint arms included.  One calcDiff sweep and one forward sweep on the device
+        (aslr_policy_covariance, include/aslr_to_amd_cov.h); the box is not applied."""
+        return self.problem.engine.policy_covariance(sigma0, noise_var, keep_cov)
 
     def iteration_log(self):
         """numpy [iterations, LOG_COUNT, B] of the last solve (needs callbacks or `keep_log = True`), trimmed to the

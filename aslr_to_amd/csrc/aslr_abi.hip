@@ -11,6 +11,7 @@
 #include "../../include/aslr_to_amd_policy.h"
 #include "../../include/aslr_to_amd_mpc_plant.h"
 #include "../../include/aslr_to_amd_pool_params.h"
+#include "../../include/aslr_to_amd_cov.h"
 
 using namespace aslr;
 
@@ -565,6 +566,8 @@ int upload_initial(aslr_problem *p, const aslr_problem_desc_t *d, const DevDesc 
   if (e == hipSuccess) e = zero(ASLR_R_DERIV);
   if (e == hipSuccess) e = zero(ASLR_R_KFF);
   if (e == hipSuccess) e = zero(ASLR_R_VXXF);
+  // before any backward sweep the stored policy is open loop (aslr_policy_rollout, aslr_policy_covariance read KGAIN)
+  if (e == hipSuccess) e = zero(ASLR_R_KGAIN);
   if (e == hipSuccess) e = hipStreamSynchronize(st); // the host staging buffers die on return
   if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&p->h_done), sizeof(int32_t) * d->B, 0);
   if (e != hipSuccess) return fail(ASLR_E_HIP, "aslr_problem_create: upload failed: %s", hipGetErrorString(e));
@@ -1034,6 +1037,27 @@ int aslr_cost_sensitivity(aslr_problem_t *p, double *dcost_dstiffness, double *d
   a.d_stiffness = dcost_dstiffness; a.d_motor_inertia = dcost_dmotor_inertia; a.d_x0 = dcost_dx0; a.costate = costate;
   a.B = k.B; a.T = k.T;
   return launch_adjoint(p->nx, p->nu, a, st);
+}
+
+int aslr_policy_covariance(aslr_problem_t *p, const double *sigma0, const double *noise_var, double *x_var, double *u_var,
+                           double *cov_final, double *cov, double *cost_increase, void *stream) {
+  if (!p) return no_handle("aslr_policy_covariance");
+  if (!x_var && !u_var && !cov_final && !cov && !cost_increase)
+    return fail(ASLR_E_INVALID, "aslr_policy_covariance: all five outputs are NULL: nothing to compute");
+  if (!sigma0 && !noise_var)
+    return fail(ASLR_E_INVALID, "aslr_policy_covariance: sigma0 and noise_var are both NULL: nothing to propagate");
+  if (!has_covariance_kernel(p->nx, p->nu)) // (before the calcDiff sweep: a refusal writes nothing)
+    return fail(ASLR_E_INVALID, "aslr_policy_covariance: no covariance kernel for records of (nx = %d, nu = %d)", p->nx, p->nu);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
+  const KArgs &k = p->k;
+  CovarianceArgs a;
+  memset(&a, 0, sizeof a);
+  a.deriv = k.deriv; a.kgain = k.kgain;
+  a.sigma0 = sigma0; a.noise_var = noise_var;
+  a.x_var = x_var; a.u_var = u_var; a.cov_final = cov_final; a.cov = cov; a.cost_increase = cost_increase;
+  a.B = k.B; a.T = k.T;
+  return launch_covariance(p->nx, p->nu, a, st);
 }
 
 int aslr_policy_rollout(aslr_problem_t *p, int n_samples, const double *plant_stiffness, const double *plant_motor_inertia,

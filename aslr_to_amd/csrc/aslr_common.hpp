@@ -199,6 +199,17 @@ struct AdjointArgs {
 };
 int launch_adjoint(int nx, int nu, const AdjointArgs &a, hipStream_t st);
 
+// Closed-loop covariance sweep (aslr_policy_covariance, aslr_covariance.inc.hpp): what covariance_kernel reads and writes, by
+// value.  Like the adjoint kernel it depends on the record shape (nx, nu) alone and has no row in the table of kernel sets.
+struct CovarianceArgs {
+  const double *deriv, *kgain;
+  const double *sigma0, *noise_var;                         // [B][nx][nx], [T][B][nx]; each nullable (zero)
+  double *x_var, *u_var, *cov_final, *cov, *cost_increase; // [T+1][B][nx], [T][B][nu], [B][nx][nx], [T+1][B][nx][nx], [B]; each nullable
+  int32_t B, T;
+};
+bool has_covariance_kernel(int nx, int nu);
+int launch_covariance(int nx, int nu, const CovarianceArgs &a, hipStream_t st);
+
 // Closed-loop policy roll-outs (aslr_policy_rollout, aslr_policy.inc.hpp): the caller's arrays, by value, beside the KArgs and
 // ModelLimits of the handle.  One template serves handles with and without a parameter table (`table`), as the adjoint
 // kernel does, so it has no row in the table of kernel sets either.

@@ -46,6 +46,15 @@ class PolicyRolloutResult(object):
         self.__dict__.update(fields)
 
 
+class PolicyCovarianceResult(object):
+    """What Engine.policy_covariance returns: batch-major device tensors -- x_var [B, T+1, nx] (diagonal of Sigma_t), u_var
+    [B, T, nu] (diagonal of K Sigma K^T; the models' own nu: padded controls are cut), cov_final [B, nx, nx] (Sigma_T),
+    cost_increase [B] and, when kept, cov [B, T+1, nx, nx] (every Sigma_t); cov is None otherwise."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class Engine(object):
     """ShootingProblem shard resident in HBM.  Region layouts: include/aslr_to_amd.h."""
 
@@ -353,6 +362,54 @@ class Engine(object):
         return PolicyRolloutResult(cost=cost.t(), failed_knot=failed.t(), x_final=xf.permute(1, 0, 2),
                                    xs=None if xs is None else xs.permute(2, 0, 1, 3),
                                    us=None if us is None else self.cut_u(us.permute(2, 0, 1, 3)))
+
+    def policy_covariance(self, sigma0=None, noise_var=None, keep_cov=False):
+        """First-order state and control covariance under the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), by
+        one calcDiff sweep and one forward sweep (aslr_policy_covariance, include/aslr_to_amd_cov.h): Sigma_{t+1} =
+        A_t Sigma_t A_t^T + diag(noise_var_t) with A_t = Fx_t - Fu_t K_t.  Batch-major arrays or tensors, at least one of
+        them: sigma0 [B, nx, nx] or [nx, nx] (symmetric), noise_var [B, T, nx], [B, nx] or [nx] (>= 0; noise t enters
+        x_{t+1}); the shorter forms are broadcast.  -> PolicyCovarianceResult.  Side effects: those of calc_diff.  Before
+        any backward sweep K = 0 and the result is the open-loop covariance; the control box is not applied."""
+        torch = _torch()
+        B, T, nx, nu = self.B, self.T, self.nx, self.nu
+
+        def dev(v, name):
+            if v is None:
+                return None
+            return torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
+                                   device=self.device)
+
+        with torch.cuda.device(self.device):
+            s0, w = dev(sigma0, "sigma0"), dev(noise_var, "noise_var")
+            if s0 is not None:
+                if s0.dim() == 2:
+                    s0 = s0.unsqueeze(0).expand(B, -1, -1)
+                if tuple(s0.shape) != (B, nx, nx):
+                    raise ValueError("sigma0 must have shape [B=%d, nx=%d, nx] or [nx, nx], not %s" % (B, nx, list(s0.shape)))
+                if not torch.equal(s0, s0.transpose(1, 2)):
+                    raise ValueError("sigma0 must be symmetric")
+                if bool((torch.diagonal(s0, dim1=1, dim2=2) < 0).any()):
+                    raise ValueError("sigma0 has a negative variance on its diagonal")
+                s0 = s0.contiguous()
+            if w is not None:
+                if w.dim() == 1:
+                    w = w.unsqueeze(0).expand(B, -1)
+                if w.dim() == 2:
+                    w = w.unsqueeze(1).expand(-1, T, -1)
+                if tuple(w.shape) != (B, T, nx):
+                    raise ValueError("noise_var must have shape [B=%d, T=%d, nx=%d], [B, nx] or [nx], not %s"
+                                     % (B, T, nx, list(w.shape)))
+                if bool((w < 0).any()):
+                    raise ValueError("noise_var has a negative variance")
+                w = w.permute(1, 0, 2).contiguous()
+            new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
+            xv, uv, cf, ci = new(T + 1, B, nx), new(T, B, nu), new(B, nx, nx), new(B)
+            cov = new(T + 1, B, nx, nx) if keep_cov else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._call("aslr_policy_covariance", ptr(s0), ptr(w), ptr(xv), ptr(uv), ptr(cf), ptr(cov), ptr(ci), self._stream())
+        torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
+        return PolicyCovarianceResult(x_var=xv.permute(1, 0, 2), u_var=self.cut_u(uv.permute(1, 0, 2)), cov_final=cf,
+                                      cost_increase=ci, cov=None if cov is None else cov.permute(1, 0, 2, 3))
 
     # ---- per-iteration log, frame placements, residuals ----
     def enable_iteration_log(self, capacity):
