@@ -188,6 +188,9 @@ POOL_PARAMS_SYMBOLS = ["aslr_solve_pool_params"]
 # what include/aslr_to_amd_cov.h declares: a fifth extension header, in a list of its own for the same reason
 COV_SYMBOLS = ["aslr_policy_covariance"]
 
+# what include/aslr_to_amd_plant_sens.h declares: a sixth extension header, in a list of its own for the same reason
+PLANT_SENS_SYMBOLS = ["aslr_policy_plant_sensitivity"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -274,6 +277,8 @@ def load_library():
                                            C.POINTER(i32)]
     lib.aslr_policy_covariance.restype = C.c_int
     lib.aslr_policy_covariance.argtypes = [vp] * 9
+    lib.aslr_policy_plant_sensitivity.restype = C.c_int
+    lib.aslr_policy_plant_sensitivity.argtypes = [vp] * 12
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

@@ -251,6 +251,18 @@ class ShootingProblem(object):
             raise ValueError("policy_covariance: give xs, us and K together (or none of them: the engine's own policy)")
         return self._with_policy(xs, us, K, lambda: e.policy_covariance(sigma0, noise_var, keep_cov))
 
+    def policy_plant_sensitivity(self, xs, us, K, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
+        """First-order sensitivity of the closed loop under the policy u_t = us_t - K_t (x_t - xs_t) to the plant's spring
+        stiffness and motor inertia (Engine.policy_plant_sensitivity; aslr_policy_plant_sensitivity): xs, us, K as
+        policy_rollout takes them, all three None: the policy the engine holds.  The engine's own XS / US / KGAIN are put
+        back afterwards.  -> engine.PlantSensitivityResult.  This shard's trajectories only."""
+        e = self.engine
+        if xs is None and us is None and K is None:
+            return e.policy_plant_sensitivity(stiffness_var, motor_inertia_var, keep_trajectories)
+        if xs is None or us is None or K is None:
+            raise ValueError("policy_plant_sensitivity: give xs, us and K together (or none of them: the engine's own policy)")
+        return self._with_policy(xs, us, K, lambda: e.policy_plant_sensitivity(stiffness_var, motor_inertia_var, keep_trajectories))
+
     def _with_policy(self, xs, us, K, call):
         """call() with (xs, us, K) in the engine's XS / US / KGAIN; the engine's own are put back afterwards"""
         import torch
@@ -554,6 +566,19 @@ class SolverDDP(object):
         keep_cov.  Every model size, the 7-joint arms included.  One calcDiff sweep and one forward sweep on the device
         (aslr_policy_covariance, include/aslr_to_amd_cov.h); the box is not applied."""
         return self.problem.engine.policy_covariance(sigma0, noise_var, keep_cov)
+
+    def policy_plant_sensitivity(self, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
+        """Where the policy of the last solve (its xs, us and Riccati gains K) ends up on an arm whose springs or motors are
+        not the model's, to first order and without samples: S_t = dx_t/dtheta for theta = (diag K, diag B) under
+        u_t = us_t - K_t (x_t - xs_t), S_{t+1} = (Fx_t - Fu_t K_t) S_t + G_t from S_0 = 0.  -> engine.PlantSensitivityResult:
+        dx_final_dstiffness, dx_final_dmotor_inertia [B, nx, nj], dcost_dstiffness, dcost_dmotor_inertia [B, nj] (the cost
+        of the closed loop, the feedback's corrections included), with stiffness_var / motor_inertia_var ([B, nj] or [nj],
+        variances of independent parameter errors) x_var [B, T+1, nx] and u_var [B, T, nu], and with keep_trajectories
+        dxs_dstiffness, dxs_dmotor_inertia [B, T+1, nx, nj].  A relative error r in K_j moves x_T by
+        r * K_j * dx_final_dstiffness[:, :, j].  Every model size, the 7-joint arms included; the stiffness fields are None
+        for a VSA model.  One calcDiff sweep and one forward sweep on the device (aslr_policy_plant_sensitivity,
+        include/aslr_to_amd_plant_sens.h); the box is not applied."""
+        return self.problem.engine.policy_plant_sensitivity(stiffness_var, motor_inertia_var, keep_trajectories)
 
     def iteration_log(self):
         """numpy [iterations, LOG_COUNT, B] of the last solve (needs callbacks or `keep_log = True`), trimmed to the

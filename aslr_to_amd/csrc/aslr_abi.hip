@@ -12,6 +12,7 @@
 #include "../../include/aslr_to_amd_mpc_plant.h"
 #include "../../include/aslr_to_amd_pool_params.h"
 #include "../../include/aslr_to_amd_cov.h"
+#include "../../include/aslr_to_amd_plant_sens.h"
 
 using namespace aslr;
 
@@ -1058,6 +1059,54 @@ int aslr_policy_covariance(aslr_problem_t *p, const double *sigma0, const double
   a.x_var = x_var; a.u_var = u_var; a.cov_final = cov_final; a.cov = cov; a.cost_increase = cost_increase;
   a.B = k.B; a.T = k.T;
   return launch_covariance(p->nx, p->nu, a, st);
+}
+
+int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var, const double *motor_inertia_var,
+                                  double *dx_dstiffness, double *dx_dmotor_inertia, double *dxT_dstiffness,
+                                  double *dxT_dmotor_inertia, double *dcost_dstiffness, double *dcost_dmotor_inertia,
+                                  double *x_var, double *u_var, void *stream) {
+  if (!p) return no_handle("aslr_policy_plant_sensitivity");
+  if (!dx_dstiffness && !dx_dmotor_inertia && !dxT_dstiffness && !dxT_dmotor_inertia && !dcost_dstiffness &&
+      !dcost_dmotor_inertia && !x_var && !u_var)
+    return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: all eight outputs are NULL: nothing to compute");
+  const bool sea = p->dam == ASLR_DAM_SEA, table = p->ks->traj_params;
+  if (!sea && (stiffness_var || dx_dstiffness || dxT_dstiffness || dcost_dstiffness))
+    return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: a stiffness argument on a VSA model, which takes its stiffness from u");
+  if ((x_var || u_var) && !stiffness_var && !motor_inertia_var)
+    return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: x_var or u_var with stiffness_var and motor_inertia_var both NULL: no variance to propagate");
+  if (!has_plant_sens_kernel(p->nx, p->nu)) // (before the calcDiff sweep: a refusal writes nothing)
+    return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: no kernel for records of (nx = %d, nu = %d)", p->nx, p->nu);
+  // the stiffness columns are computed when an output of theirs, or their variance in x_var / u_var, is asked for
+  const bool stiff = dx_dstiffness || dxT_dstiffness || dcost_dstiffness || (stiffness_var && (x_var || u_var));
+  const int B = p->desc.B, nj = p->nj, nm = p->desc.nmodels;
+  const aslr_model_t *M = p->desc.models;
+  PlantSensArgs a;
+  memset(&a, 0, sizeof a);
+  for (int i = 0; i < nm; ++i) {
+    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: K and B of model %d must be diagonal", i);
+    a.dt[i] = M[i].dt;
+    for (int j = 0; j < nj; ++j) {
+      const double k = M[i].K[j * nj + j], bj = M[i].B[j * nj + j];
+      if (stiff && !table && k == 0.0) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: stiffness entry K[%d] of model %d is 0 (the stiffness term divides by it)", j, i);
+      if (bj == 0.0) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: motor inertia entry B[%d] of model %d is 0", j, i);
+      a.K[i][j] = sea ? k : 0.0;
+      a.Binv[i][j] = 1.0 / bj;
+    }
+  }
+  if (stiff && table)
+    for (int j = 0; j < nj; ++j)
+      for (int b = 0; b < B; ++b)
+        if (p->tp_host[(size_t)j * B + b] == 0.0) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: stiffness entry [%d][%d] of the parameter table is 0 (the stiffness term divides by it)", b, j);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
+  const KArgs &k = p->k;
+  a.deriv = k.deriv; a.kgain = k.kgain; a.xs = k.xs; a.xnext = k.xnext; a.node_model = k.node_model;
+  a.traj_params = table ? reinterpret_cast<const double *>(region(p, ASLR_R_TRAJ_PARAMS)) : nullptr;
+  a.stiffness_var = stiffness_var; a.motor_inertia_var = motor_inertia_var;
+  a.dx_k = dx_dstiffness; a.dx_b = dx_dmotor_inertia; a.dxT_k = dxT_dstiffness; a.dxT_b = dxT_dmotor_inertia;
+  a.dcost_k = dcost_dstiffness; a.dcost_b = dcost_dmotor_inertia; a.x_var = x_var; a.u_var = u_var;
+  a.B = k.B; a.T = k.T; a.stiff = stiff;
+  return launch_plant_sens(p->nx, p->nu, a, st);
 }
 
 int aslr_policy_rollout(aslr_problem_t *p, int n_samples, const double *plant_stiffness, const double *plant_motor_inertia,

@@ -210,6 +210,26 @@ struct CovarianceArgs {
 bool has_covariance_kernel(int nx, int nu);
 int launch_covariance(int nx, int nu, const CovarianceArgs &a, hipStream_t st);
 
+// Tangent sweep (aslr_policy_plant_sensitivity, aslr_plant_sens.inc.hpp): what plant_sens_kernel reads and writes, by value.
+// The parameters of a trajectory are taken as AdjointArgs has them; like the adjoint kernel it depends on the record shape
+// alone and has no row in the table of kernel sets.
+struct PlantSensArgs {
+  const double *deriv, *kgain, *xs, *xnext;
+  const int32_t *node_model;
+  const double *traj_params;                       // region TRAJ_PARAMS while a table is set, else nullptr
+  const double *stiffness_var, *motor_inertia_var; // [nj][B]; each nullable (zero)
+  double *dx_k, *dx_b;                             // [T+1][B][nx][nj]; every output nullable
+  double *dxT_k, *dxT_b;                           // [B][nx][nj]
+  double *dcost_k, *dcost_b;                       // [nj][B]
+  double *x_var, *u_var;                           // [T+1][B][nx], [T][B][nu]
+  int32_t B, T;
+  int32_t stiff; // the stiffness columns are computed (some stiffness quantity is asked for)
+  double dt[ASLR_MAX_MODELS];
+  double K[ASLR_MAX_MODELS][ASLR_MAX_NJ], Binv[ASLR_MAX_MODELS][ASLR_MAX_NJ]; // diagonals
+};
+bool has_plant_sens_kernel(int nx, int nu);
+int launch_plant_sens(int nx, int nu, const PlantSensArgs &a, hipStream_t st);
+
 // Closed-loop policy roll-outs (aslr_policy_rollout, aslr_policy.inc.hpp): the caller's arrays, by value, beside the KArgs and
 // ModelLimits of the handle.  One template serves handles with and without a parameter table (`table`), as the adjoint
 // kernel does, so it has no row in the table of kernel sets either.

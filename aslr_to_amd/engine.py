@@ -55,6 +55,16 @@ class PolicyCovarianceResult(object):
         self.__dict__.update(fields)
 
 
+class PlantSensitivityResult(object):
+    """What Engine.policy_plant_sensitivity returns: batch-major device tensors -- dx_final_dstiffness,
+    dx_final_dmotor_inertia [B, nx, nj] (dx_T/dK_j, dx_T/dB_j), dcost_dstiffness, dcost_dmotor_inertia [B, nj], x_var
+    [B, T+1, nx] and u_var [B, T, nu] (the models' own nu; both None when no variance was given) and, when kept,
+    dxs_dstiffness, dxs_dmotor_inertia [B, T+1, nx, nj] (None otherwise).  The stiffness fields are None for a VSA model."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class Engine(object):
     """ShootingProblem shard resident in HBM.  Region layouts: include/aslr_to_amd.h."""
 
@@ -410,6 +420,50 @@ class Engine(object):
         torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
         return PolicyCovarianceResult(x_var=xv.permute(1, 0, 2), u_var=self.cut_u(uv.permute(1, 0, 2)), cov_final=cf,
                                       cost_increase=ci, cov=None if cov is None else cov.permute(1, 0, 2, 3))
+
+    def policy_plant_sensitivity(self, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
+        """First-order sensitivity of the closed loop under the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), to
+        the plant's spring stiffness and motor inertia, by one calcDiff sweep and one forward (tangent) sweep
+        (aslr_policy_plant_sensitivity, include/aslr_to_amd_plant_sens.h): S_{t+1} = (Fx_t - Fu_t K_t) S_t + G_t from S_0 = 0,
+        S_t = dx_t/dtheta.  stiffness_var, motor_inertia_var: [B, nj] or [nj] variances (>= 0) of independent parameter
+        errors; with at least one of them the result carries x_var and u_var.  -> PlantSensitivityResult; the stiffness
+        fields are None for a VSA model, which refuses stiffness_var.  Side effects: those of calc_diff.  Before any backward
+        sweep K = 0 and dcost_* are what cost_sensitivity returns; the control box is not applied."""
+        torch = _torch()
+        B, T, nx, nu, nj = self.B, self.T, self.nx, self.nu, self.nx // 4
+        vsa = self.low.dam == _abi.DAM_VSA
+        if vsa and stiffness_var is not None:
+            raise ValueError("stiffness_var on a VSA model, which takes its stiffness from u")
+
+        def var(v, name):
+            if v is None:
+                return None
+            v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
+                                device=self.device)
+            if v.dim() == 1:
+                v = v.unsqueeze(0).expand(B, -1)
+            if tuple(v.shape) != (B, nj):
+                raise ValueError("%s must have shape [B=%d, nj=%d] or [nj], not %s" % (name, B, nj, list(v.shape)))
+            if bool((v < 0).any()):
+                raise ValueError("%s has a negative variance" % name)
+            return v.t().contiguous()
+
+        with torch.cuda.device(self.device):
+            vk, vb = var(stiffness_var, "stiffness_var"), var(motor_inertia_var, "motor_inertia_var")
+            new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
+            both = lambda *shape: (None if vsa else new(*shape), new(*shape))
+            (fk, fb), (ck, cb) = both(B, nx, nj), both(nj, B)
+            tk, tb = both(T + 1, B, nx, nj) if keep_trajectories else (None, None)
+            xv, uv = (new(T + 1, B, nx), new(T, B, nu)) if (vk is not None or vb is not None) else (None, None)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._call("aslr_policy_plant_sensitivity", ptr(vk), ptr(vb), ptr(tk), ptr(tb), ptr(fk), ptr(fb), ptr(ck), ptr(cb),
+                   ptr(xv), ptr(uv), self._stream())
+        torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
+        bm = lambda t, *perm: None if t is None else t.permute(*perm)
+        return PlantSensitivityResult(dx_final_dstiffness=fk, dx_final_dmotor_inertia=fb, dcost_dstiffness=bm(ck, 1, 0),
+                                      dcost_dmotor_inertia=bm(cb, 1, 0), x_var=bm(xv, 1, 0, 2),
+                                      u_var=None if uv is None else self.cut_u(uv.permute(1, 0, 2)),
+                                      dxs_dstiffness=bm(tk, 1, 0, 2, 3), dxs_dmotor_inertia=bm(tb, 1, 0, 2, 3))
 
     # ---- per-iteration log, frame placements, residuals ----
     def enable_iteration_log(self, capacity):

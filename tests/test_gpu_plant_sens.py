@@ -1,0 +1,402 @@
+"""aslr_policy_plant_sensitivity on the GPU (include/aslr_to_amd_plant_sens.h; plant_sens_kernel,
+csrc/aslr_plant_sens.inc.hpp) against tests/_plant_sens.py: the definition in numpy with full matrices on the oracle's
+records, fed the DEVICE's own gains so that only this sweep is compared.
+
+Kernel outputs are held to 1e-9 in the measure max |a - b| / max |b| per output array and trajectory (cv.relerr);
+tests/test_plant_sens_host.py shows that the inputs are conditioned for it and pins the definition on the oracle alone.
+Shapes (tests/_covariance.CASES): the smallest that leave a partial wave of teams (B = 9 at nx = 8: 8 trajectories per wave;
+B = 3 at nx = 28: 2 per wave) and the smallest problem there is (B = 1, T = 1).  Every output sits in a buffer of the test's
+own, followed by guard words that must survive."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import _covariance as cv
+import _gpu_case as gc
+import _plant_sens as ps
+import _policy as pol
+import _sensitivity as sens
+import _traj_oracle
+from aslr_to_amd import _abi, crocoddyl, scenarios
+
+pytestmark = pytest.mark.gpu
+
+FIELDS = ps.OUTPUTS   # in the order of the C arguments
+GUARD, SENTINEL = 64, -7.25
+_TO_BATCH_MAJOR = {"dx_dstiffness": (1, 0, 2, 3), "dx_dmotor_inertia": (1, 0, 2, 3), "dxT_dstiffness": (0, 1, 2),
+                   "dxT_dmotor_inertia": (0, 1, 2), "dcost_dstiffness": (1, 0), "dcost_dmotor_inertia": (1, 0),
+                   "x_var": (1, 0, 2), "u_var": (1, 0, 2)}
+MOTOR = tuple(k for k in FIELDS if k.endswith("motor_inertia"))
+VAR_SEED = 37
+
+
+def _shapes(e):
+    nj = e.nx // 4
+    return {"dx_dstiffness": (e.T + 1, e.B, e.nx, nj), "dx_dmotor_inertia": (e.T + 1, e.B, e.nx, nj),
+            "dxT_dstiffness": (e.B, e.nx, nj), "dxT_dmotor_inertia": (e.B, e.nx, nj), "dcost_dstiffness": (nj, e.B),
+            "dcost_dmotor_inertia": (nj, e.B), "x_var": (e.T + 1, e.B, e.nx), "u_var": (e.T, e.B, e.nu)}
+
+
+def _fields(low):
+    """the outputs a model has: no stiffness ones for VSA"""
+    return tuple(k for k in FIELDS if ps.has_stiffness(low) or not k.endswith("stiffness"))
+
+
+def _raw(e, stiffness_var, motor_inertia_var, which=None, expect=_abi.OK):
+    """aslr_policy_plant_sensitivity with the batch-major variances [B, nj] (None: NULL) and the outputs `which` (default:
+    all the model has; the others NULL), each output in a buffer with GUARD sentinel words behind it.  -> dict of batch-major
+    numpy arrays (the layout of tests/_plant_sens.expected; u_var with the device's nu); the guards must be untouched.
+    expect != OK: -> the message of the refusal."""
+    import torch
+    if which is None:
+        which = _fields(e.low)
+    dev = lambda v: None if v is None else torch.as_tensor(np.ascontiguousarray(np.asarray(v).T), dtype=torch.float64, device=e.device)
+    vk, vb = dev(stiffness_var), dev(motor_inertia_var)
+    bufs, n_of = {}, {}
+    for k in which:
+        n_of[k] = int(np.prod(_shapes(e)[k]))
+        bufs[k] = torch.full((n_of[k] + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    with torch.cuda.device(e.device):
+        rc = e.lib.aslr_policy_plant_sensitivity(e.handle, ptr(vk), ptr(vb), *[ptr(bufs.get(k)) for k in FIELDS], e._stream())
+    gc.sync()
+    if expect != _abi.OK:
+        assert rc == expect, rc
+        for k, t in bufs.items():
+            assert (t == SENTINEL).all(), "%s was written by a refused call" % k
+        return e.lib.aslr_last_error().decode()
+    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
+    out = {}
+    for k, t in bufs.items():
+        a = gc.to_np(t)
+        assert (a[n_of[k]:] == SENTINEL).all(), "the guard behind %s was overwritten" % k
+        out[k] = np.ascontiguousarray(np.transpose(a[:n_of[k]].reshape(_shapes(e)[k]), _TO_BATCH_MAJOR[k]))
+    return out
+
+
+def _same(a, b, what):
+    assert set(a) == set(b), (what, sorted(a), sorted(b))
+    for k in a:
+        np.testing.assert_array_equal(a[k].view(np.uint64), b[k].view(np.uint64), err_msg="%s: %s" % (what, k))
+
+
+def _with_gains(c):
+    """a fresh engine with the case's candidate in XS / US and the gains of one aslr_calc_diff + aslr_backward_pass on it in
+    KGAIN (the case's own solver: SolverBoxDDP where the scenario has one) -> engine, K [T, B, nu, nx]"""
+    low = c["low"]
+    e = gc.engine(low)
+    deriv = gc.run_calc_diff(e, c["xs"], c["us"])[2]
+    out = gc.run_backward(e, c["sp"], c["us"], deriv, np.zeros((low.T + 1, low.B, low.nx)), pol.XREG, 1)
+    assert (out["status"] & _abi.ST_BACKWARD_ERR == 0).all(), out["status"]
+    assert np.abs(out["K"]).max() > 1e-3
+    return e, out["K"]
+
+
+@pytest.fixture(scope="module")
+def cases(oracle):
+    """the seeded inputs of every case, built once (the open-loop candidate comes from the oracle) and never changed; var:
+    the seeded variances (stiffness or None, motor inertia)"""
+    made = {}
+    for key in ps.CASES:
+        made[key] = cv.case(oracle, key)
+        made[key]["var"] = ps.variances(made[key]["low"], VAR_SEED)
+    return made
+
+
+@pytest.fixture(scope="module")
+def loaded(cases):
+    """key -> (engine with the candidate and its gains in place, the device's K), made on first use and shared: the call
+    under test changes nothing it reads"""
+    made = {}
+
+    def get(key):
+        if key not in made:
+            made[key] = _with_gains(cases[key])
+        return made[key]
+    return get
+
+
+@pytest.mark.parametrize("key", sorted(ps.CASES))
+def test_kernel_matches_the_definition(oracle, cases, loaded, key):
+    c = cases[key]
+    low = c["low"]
+    e, K = loaded(key)
+    vk, vb = c["var"]
+    got = _raw(e, vk, vb)
+    want = ps.expected(oracle, low, c["xs"], c["us"], K, vk, vb)
+    assert set(got) == set(_fields(low))
+    for k in got:
+        assert got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
+        err = cv.relerr(got[k], want[k])   # (a trajectory whose reference is all zero must match exactly)
+        print("%s %s: %.2e (max |reference| %.2e)" % (key, k, err, np.abs(want[k]).max()))
+        assert err < 1e-9, (k, err)
+    assert np.abs(want["dxT_dmotor_inertia"]).max() > 1e-3 and np.abs(want["x_var"]).max() > 1e-6
+    if low.T > 1:
+        assert np.abs(want["u_var"]).max() > 1e-6 and np.abs(want["dcost_dmotor_inertia"]).max() > 1e-3
+    else:   # T = 1: S_0 = 0, so V_0 = 0 on both sides
+        assert (got["u_var"] == 0.0).all()
+    if key in ("vsa_box", "arm_vsa"):   # gains after a BoxDDP backward sweep: some rows are zero, and so is their variance
+        zero = np.abs(K).max(axis=-1) == 0.0
+        assert zero.any() and not zero.all()
+        assert (got["u_var"].transpose(1, 0, 2)[zero] == 0.0).all()
+    if key == "nu1":
+        assert (got["u_var"][..., 1] == 0.0).all()   # the padded control
+    if getattr(low, "ref_path", None) is not None:   # ... and the path is what the records were evaluated against
+        plain = scenarios.lower(dict(c["sc"], ref_path=None))
+        other = ps.expected(oracle, plain, c["xs"], c["us"], K, vk, vb)
+        assert cv.relerr(other["dcost_dmotor_inertia"], want["dcost_dmotor_inertia"]) > 1e-6
+
+
+@pytest.mark.parametrize("key", ["sea", "arm_sea", "arm_vsa"])
+def test_every_output_is_optional(cases, loaded, key):
+    """each output alone: the bits of the call with all of them, and nothing written past any buffer (_raw checks the
+    guards).  The motor-inertia outputs alone, without a stiffness variance, run the kernel without the stiffness columns:
+    the same bits again, also for x_var and u_var against a call that computes those columns for dx_dstiffness only"""
+    c = cases[key]
+    e, _ = loaded(key)
+    vk, vb = c["var"]
+    full = _raw(e, vk, vb)
+    for k in full:
+        _same(_raw(e, vk, vb, which=(k,)), {k: full[k]}, "alone")
+    _same(_raw(e, None, vb, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia only")
+    if vk is not None:
+        _same(_raw(e, vk, None, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia outputs, stiffness variance")
+        lean = _raw(e, None, vb, which=MOTOR + ("x_var", "u_var"))
+        wide = _raw(e, None, vb, which=MOTOR + ("x_var", "u_var", "dx_dstiffness"))
+        _same(lean, {k: wide[k] for k in lean}, "variances with and without the stiffness columns")
+        _same({"dx_dstiffness": wide["dx_dstiffness"]}, {"dx_dstiffness": full["dx_dstiffness"]}, "stiffness columns")
+        assert cv.relerr(lean["x_var"], full["x_var"]) > 1e-6   # (the stiffness variance is what was left out)
+
+
+@pytest.mark.parametrize("key", ["sea", "arm_sea", "arm_vsa"])
+def test_a_trajectory_does_not_depend_on_where_it_sits(cases, loaded, key):
+    """trajectory B - 1 of the batch (the one behind the last full wave of teams) against the same trajectory alone in a
+    B = 1 engine (tests/_traj_oracle.single: its row of the table in the models) with the batch's gains uploaded: bit for
+    bit"""
+    c = cases[key]
+    low = c["low"]
+    e, K = loaded(key)
+    vk, vb = c["var"]
+    batch = _raw(e, vk, vb)
+    b = low.B - 1
+    e1 = gc.engine(_traj_oracle.single(low, b))
+    gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
+    alone = _raw(e1, None if vk is None else vk[b:b + 1], vb[b:b + 1])
+    _same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
+
+
+@pytest.mark.parametrize("key", ["sea", "arm_vsa"])
+def test_the_outputs_are_consistent_with_each_other(cases, loaded, key):
+    """dxT_* is dx_*[T], bit for bit; on a fresh handle (K = 0) dcost_* agrees with aslr_cost_sensitivity on the same handle
+    to 1e-9 (the tangent and the adjoint sweep are dual) and u_var is exactly 0"""
+    c = cases[key]
+    low = c["low"]
+    e, _ = loaded(key)
+    vk, vb = c["var"]
+    got = _raw(e, vk, vb)
+    for kind in ps.KINDS:
+        if "dx_d" + kind in got:
+            np.testing.assert_array_equal(got["dx_d" + kind][:, low.T].copy().view(np.uint64), got["dxT_d" + kind].view(np.uint64))
+    fresh = gc.engine(low)
+    gc._upload(fresh, XS=c["xs"], US=c["us"])
+    open_loop = _raw(fresh, vk, vb)
+    adjoint = fresh.cost_sensitivity()
+    gc.sync()
+    for kind in ps.KINDS:
+        if "dcost_d" + kind not in open_loop:
+            assert adjoint.stiffness is None
+            continue
+        ref = gc.to_np(getattr(adjoint, kind))
+        err = cv.relerr(open_loop["dcost_d" + kind], ref)
+        print("%s open loop dcost_d%s against the adjoint sweep: %.2e (max |reference| %.2e)" % (key, kind, err, np.abs(ref).max()))
+        assert err < 1e-9, (kind, err)
+        assert np.abs(ref).max() > 1e-3
+    assert (open_loop["u_var"] == 0.0).all()
+    assert cv.relerr(open_loop["dxT_dmotor_inertia"], got["dxT_dmotor_inertia"]) > 1e-3   # ... the gains closed the loop above
+
+
+def test_the_sweep_agrees_with_sampled_plants(cases, loaded):
+    """the 2-joint sea case: the device's own aslr_policy_rollout, clamp off, on plants theta_p (1 +- h), two samples per
+    parameter; central differences of x_final and of the cost against dx_final_* and dcost_*, within ten times the
+    disagreement tests/_plant_sens.FD records for that step (the definition against the oracle's closed loop)"""
+    c = cases["sea"]
+    low = c["low"]
+    e, _ = loaded("sea")
+    h, measured, _ = ps.FD["sea"]
+    B, nj = low.B, low.nj
+    k0 = np.array([pol.nominal_diag(low, b, "K") for b in range(B)])
+    b0 = np.array([pol.nominal_diag(low, b, "B") for b in range(B)])
+    S = 4 * nj
+    pk, pb = np.repeat(k0[:, None, :], S, axis=1), np.repeat(b0[:, None, :], S, axis=1)
+    for p in range(2 * nj):
+        arr = pk if p < nj else pb
+        arr[:, 2 * p, p % nj] *= 1.0 + h
+        arr[:, 2 * p + 1, p % nj] *= 1.0 - h
+    got = _raw(e, None, None, which=("dxT_dstiffness", "dxT_dmotor_inertia", "dcost_dstiffness", "dcost_dmotor_inertia"))
+    res = e.policy_rollout(S, plant_stiffness=pk, plant_motor_inertia=pb, clamp=False)
+    gc.sync()
+    assert (gc.to_np(res.failed_knot) < 0).all()
+    xf, cost = gc.to_np(res.x_final), gc.to_np(res.cost)
+    for kind, th, p0 in (("stiffness", k0, 0), ("motor_inertia", b0, nj)):
+        dxT, dJ = np.zeros((B, low.nx, nj)), np.zeros((B, nj))
+        for j in range(nj):
+            step = 2.0 * h * th[:, j]
+            dxT[:, :, j] = (xf[:, 2 * (p0 + j)] - xf[:, 2 * (p0 + j) + 1]) / step[:, None]
+            dJ[:, j] = (cost[:, 2 * (p0 + j)] - cost[:, 2 * (p0 + j) + 1]) / step
+        for name, fd in (("dxT_d" + kind, dxT), ("dcost_d" + kind, dJ)):
+            err = cv.relerr(got[name], fd)
+            print("%s against sampled plants: %.2e (bound %.1e)" % (name, err, 10 * measured))
+            assert err < 10 * measured, (name, err)
+
+
+def test_the_call_has_the_side_effects_of_calc_diff(cases):
+    """3 iterations, the call (both variances, all outputs), 3 more iterations: XS, US, TRAJ_F and TRAJ_I are, bit for bit,
+    those of 3 iterations, aslr_calc_diff, 3 iterations on a fresh engine"""
+    c = cases["vsa_box"]
+    low, sp = c["low"], c["sp"]
+    runs = []
+    for call in (lambda e: _raw(e, *c["var"]), lambda e: e.calc_diff()):
+        e = gc.engine(low)
+        e.set_candidate(None, None)
+        e.iterate_n(sp, True, 3)
+        call(e)
+        e.iterate_n(sp, False, 3)
+        gc.sync()
+        runs.append(gc.solution(e))
+    assert (runs[1]["traj_i"][_abi.TI_ITER] > 3).any()
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)
+
+
+def _refused(e, vk, vb, which, *words):
+    msg = _raw(e, vk, vb, which=which, expect=_abi.E_INVALID)
+    assert msg.startswith("aslr_policy_plant_sensitivity:") and all(w in msg for w in words), msg
+
+
+def test_refusals_write_nothing_and_leave_a_live_handle_that_still_solves(cases, loaded):
+    """every refusal of the header that a handle can be brought to (the four record shapes are all a handle can have today)"""
+    c = cases["sea"]
+    sc, low = c["sc"], c["low"]
+    vk, vb = c["var"]
+    sp = scenarios.solver_params(sc, maxiter=8)
+    _, fresh = gc.solve_gpu(low, sp)
+    e, K = _with_gains(c)
+    ok = _raw(e, vk, vb)
+    _refused(e, vk, vb, (), "outputs", "NULL")
+    _refused(e, None, None, ("x_var",), "stiffness_var", "motor_inertia_var")
+    _refused(e, None, None, ("dxT_dmotor_inertia", "u_var"), "stiffness_var", "motor_inertia_var")
+    # a zero in the stiffness rows of the table: refused when a stiffness quantity is asked for, and only then
+    tp = {k: v for k, v in sc["traj_params"].items() if v is not None}
+    zero = np.array(tp["stiffness"])
+    zero[2, 1] = 0.0
+    e.set_trajectory_params(**dict(tp, stiffness=zero))
+    _refused(e, vk, vb, None, "stiffness", "table")
+    _refused(e, vk, None, ("x_var",), "stiffness", "table")
+    assert set(_raw(e, None, vb, which=MOTOR + ("x_var", "u_var"))) == set(MOTOR + ("x_var", "u_var"))
+    e.set_trajectory_params(**tp)
+    gc._upload(e, XS=c["xs"], US=c["us"], KGAIN=K)
+    _same(_raw(e, vk, vb), ok, "the handle after the refusals")
+    # ... in the models: a zero stiffness, a K and a B that are not diagonal
+    nj = low.nj
+    lb = sens.moved(low, 0, "K", 1, 0.0)
+    e0 = gc.engine(lb)
+    gc._upload(e0, XS=c["xs"][:, :1], US=c["us"][:, :1])
+    _refused(e0, vk[:1], vb[:1], None, "stiffness", "K[1]")
+    assert set(_raw(e0, None, vb[:1], which=MOTOR)) == set(MOTOR)
+    for field in ("K", "B"):
+        lb = _traj_oracle.single(scenarios.lower(dict(sc, traj_params=None)), 0)
+        for i in range(lb.desc.nmodels):
+            getattr(lb.desc.models[i], field)[0 * nj + 1] = 1e-3
+        _refused(gc.engine(lb), None, vb[:1], MOTOR, "diagonal")
+    # a VSA model refuses every stiffness argument, input or output
+    v = cases["vsa_box"]
+    ev, _ = loaded("vsa_box")
+    vvb = v["var"][1]
+    assert v["var"][0] is None
+    _refused(ev, vvb, vvb, _fields(v["low"]), "VSA")
+    for k in ("dx_dstiffness", "dxT_dstiffness", "dcost_dstiffness"):
+        _refused(ev, None, vvb, (k,), "VSA")
+    assert set(_raw(ev, None, vvb)) == set(_fields(v["low"]))
+    # ... and the handle still solves as a fresh one does
+    e.set_candidate(None, None)
+    e.solve(sp)
+    gc.sync()
+    after = gc.solution(e)
+    for k in ("xs", "us", "traj_i"):
+        np.testing.assert_array_equal(after[k], fresh[k], err_msg=k)
+
+
+def test_python_facade(cases):
+    """solver.policy_plant_sensitivity on two_dof_sea, B = 3, T = 8: the documented shapes and the bits of the raw call on the
+    same engine; [nj] variances are broadcast; no variance: x_var and u_var are None; problem.policy_plant_sensitivity at a
+    stored policy puts the engine's own back; a VSA model has None in the stiffness fields and refuses stiffness_var;
+    double_pendulum_nu1 returns u_var with nu = 1; a negative variance and a wrong shape raise"""
+    B, T, nx, nj = 3, 8, 8, 2
+    sc = scenarios.two_dof_sea(B=B, T=T, seed=4)
+    problem = crocoddyl.ShootingProblem(sc["x0"], sc["running"], sc["terminal"], frame_refs=sc["frame_refs"])
+    solver = crocoddyl.SolverDDP(problem)
+    solver.solve([], [], 20)
+    e = problem.engine
+    vk, vb = ps.variances(e.low, 53)
+    res = solver.policy_plant_sensitivity(vk, vb, keep_trajectories=True)
+    gc.sync()
+    for name in ("dx_final_dstiffness", "dx_final_dmotor_inertia"):
+        assert tuple(getattr(res, name).shape) == (B, nx, nj), name
+    for name in ("dcost_dstiffness", "dcost_dmotor_inertia"):
+        assert tuple(getattr(res, name).shape) == (B, nj), name
+    for name in ("dxs_dstiffness", "dxs_dmotor_inertia"):
+        assert tuple(getattr(res, name).shape) == (B, T + 1, nx, nj), name
+    assert tuple(res.x_var.shape) == (B, T + 1, nx) and tuple(res.u_var.shape) == (B, T, 2)
+    raw = _raw(e, vk, vb)
+    names = {"dx_final_dstiffness": "dxT_dstiffness", "dx_final_dmotor_inertia": "dxT_dmotor_inertia",
+             "dxs_dstiffness": "dx_dstiffness", "dxs_dmotor_inertia": "dx_dmotor_inertia", "dcost_dstiffness": "dcost_dstiffness",
+             "dcost_dmotor_inertia": "dcost_dmotor_inertia", "x_var": "x_var", "u_var": "u_var"}
+    for name, k in names.items():
+        np.testing.assert_array_equal(gc.to_np(getattr(res, name)).view(np.uint64), raw[k].view(np.uint64), err_msg=name)
+    lean = solver.policy_plant_sensitivity()
+    assert lean.x_var is None and lean.u_var is None and lean.dxs_dstiffness is None and lean.dxs_dmotor_inertia is None
+    gc.same_bits(lean.dx_final_dstiffness, res.dx_final_dstiffness, "without variances")
+    gc.same_bits(lean.dcost_dmotor_inertia, res.dcost_dmotor_inertia, "without variances")
+    # broadcasting
+    one = solver.policy_plant_sensitivity(vk[0], vb[0])
+    tiled = solver.policy_plant_sensitivity(np.tile(vk[0], (B, 1)), np.tile(vb[0], (B, 1)))
+    for k in ("x_var", "u_var"):
+        gc.same_bits(getattr(one, k), getattr(tiled, k), "broadcast [nj]: %s" % k)
+    # ... at a stored policy, through the problem: the same bits, and the engine's own policy is back afterwards
+    xs, us, K = (e.region(r).clone() for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN))
+    for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
+        e.region(r).fill_(0.25)
+    again = problem.policy_plant_sensitivity(xs.permute(1, 0, 2), us.permute(1, 0, 2), K.permute(1, 0, 2, 3), vk, vb)
+    gc.same_bits(again.x_var, res.x_var, "the stored policy given explicitly")
+    gc.same_bits(again.dcost_dstiffness, res.dcost_dstiffness, "the stored policy given explicitly")
+    for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
+        assert (e.region(r) == 0.25).all()
+    # refusals of the facade
+    neg = np.array(vb)
+    neg[2, 1] = -1e-3
+    with pytest.raises(ValueError, match="negative"):
+        solver.policy_plant_sensitivity(vk, neg)
+    with pytest.raises(ValueError, match="shape"):
+        solver.policy_plant_sensitivity(vk, np.ones((B, nj + 1)))
+    with pytest.raises(ValueError, match="together"):
+        problem.policy_plant_sensitivity(xs.permute(1, 0, 2), None, None)
+    # a VSA model: None in the stiffness fields, stiffness_var refused
+    vsc = scenarios.two_dof_vsa_boxddp(B=B, T=T, seed=4)
+    vp = crocoddyl.ShootingProblem(vsc["x0"], vsc["running"], vsc["terminal"], frame_refs=vsc["frame_refs"])
+    vs = crocoddyl.SolverBoxDDP(vp)
+    vs.solve([], [], 5)
+    rv = vs.policy_plant_sensitivity(motor_inertia_var=vb[0])
+    gc.sync()
+    assert rv.dx_final_dstiffness is None and rv.dcost_dstiffness is None and rv.dxs_dstiffness is None
+    assert tuple(rv.dx_final_dmotor_inertia.shape) == (B, nx, nj) and tuple(rv.u_var.shape) == (B, T, 4)
+    with pytest.raises(ValueError, match="VSA"):
+        vs.policy_plant_sensitivity(stiffness_var=vb[0])
+    # padded controls are cut
+    psc = cases["nu1"]["sc"]
+    pp = crocoddyl.ShootingProblem(psc["x0"], psc["running"], psc["terminal"], frame_refs=psc["frame_refs"])
+    psolver = crocoddyl.SolverDDP(pp)
+    psolver.solve([], [], 3)
+    r1 = psolver.policy_plant_sensitivity(motor_inertia_var=np.ones(2))
+    gc.sync()
+    assert tuple(r1.u_var.shape) == (3, cases["nu1"]["low"].T, 1) and tuple(r1.x_var.shape) == (3, cases["nu1"]["low"].T + 1, 8)
