@@ -103,6 +103,16 @@ class Mpc(C.Structure):
                 ("stat_f", C.c_void_p), ("stat_i", C.c_void_p)]
 
 
+class Design(C.Structure):
+    """aslr_design_t (include/aslr_to_amd_design.h): a design descent (aslr_design_descent); device pointers, rows [2 nj][B]."""
+    _fields_ = [("n_steps", _i), ("first_maxiter", _i), ("iters_per_step", _i), ("opt_stiffness", _i),
+                ("opt_motor_inertia", _i), ("_pad0", _i), ("eta0", _d), ("grow", _d), ("shrink", _d), ("c1", _d),
+                ("max_rel", _d), ("lo", C.c_void_p), ("hi", C.c_void_p), ("theta_best", C.c_void_p),
+                ("cost_best", C.c_void_p), ("xs_best", C.c_void_p), ("us_best", C.c_void_p), ("hist_f", C.c_void_p),
+                ("hist_i", C.c_void_p), ("theta_hist", C.c_void_p), ("g_acc", C.c_void_p), ("eta", C.c_void_p),
+                ("grad", C.c_void_p)]
+
+
 class Region(C.Structure):
     _fields_ = [("offset", C.c_int64), ("bytes", C.c_int64)]
 
@@ -190,6 +200,9 @@ COV_SYMBOLS = ["aslr_policy_covariance"]
 
 # what include/aslr_to_amd_plant_sens.h declares: a sixth extension header, in a list of its own for the same reason
 PLANT_SENS_SYMBOLS = ["aslr_policy_plant_sensitivity"]
+
+# what include/aslr_to_amd_design.h declares: a seventh extension header, in a list of its own for the same reason
+DESIGN_SYMBOLS = ["aslr_design_descent"]
 
 
 def load_library():
@@ -279,6 +292,8 @@ def load_library():
     lib.aslr_policy_covariance.argtypes = [vp] * 9
     lib.aslr_policy_plant_sensitivity.restype = C.c_int
     lib.aslr_policy_plant_sensitivity.argtypes = [vp] * 12
+    lib.aslr_design_descent.restype = C.c_int
+    lib.aslr_design_descent.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Design), vp]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

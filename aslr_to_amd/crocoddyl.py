@@ -537,6 +537,43 @@ class SolverDDP(object):
         return self.problem.engine.solve_pool(x0s, fr, sp, refill_every, poll_every, init_xs, init_us, stiffness,
                                               motor_inertia, u_lb, u_ub)
 
+    def optimize_design(self, n_steps, iters_per_step, init_xs=None, init_us=None, maxiter=100, stiffness_bounds=None,
+                        motor_inertia_bounds=None, eta0=0.05, grow=2.0, shrink=0.5, c1=1e-4, max_rel=0.25, keep_history=False):
+        """Improve every trajectory's own spring stiffness and motor inertia by n_steps steps of a bounded descent on the
+        device (aslr_design_descent, include/aslr_to_amd_design.h): `solve(init_xs, init_us, maxiter)` at the design the
+        problem holds (its parameter table, else the models' constants), then per step -- the gradient of cost_sensitivity,
+        an Armijo test (c1) against the accepted design, the next design a step of eta in log theta (at most max_rel per
+        entry, inside the bounds; eta grows after an accepted step and shrinks after a rejected one), `solve(xs, us,
+        iters_per_step)` from the accepted plan -- the loop a script writes around solver.solve and cost_sensitivity, without
+        a host round trip per step.  stiffness_bounds / motor_inertia_bounds: (lo, hi), each [B, nj], [nj] or a scalar; a
+        field whose bounds are None is not optimised (no stiffness_bounds for a VSA model).  -> engine.DesignResult
+        (stiffness, motor_inertia, cost, xs, us and, with keep_history, the per-step histories); solver.xs / us and the
+        problem's parameter table are left on the accepted design.  Callbacks are not replayed."""
+        p = self.problem
+        e = p.engine
+        sp = self._sp
+        sp.maxiter = int(maxiter)
+        sp.is_feasible = 0
+        sp.reg_init = float("nan")
+        lo, hi = p.rows
+
+        def shard(bounds):  # whole-batch [B, nj] entries -> this rank's rows
+            if bounds is None or len(bounds) != 2:
+                return bounds
+            return tuple(v[lo:hi] if np.ndim(v) == 2 and len(v) == p.batch_total else v for v in bounds)
+
+        e.set_candidate(init_xs, init_us)
+        e.enable_iteration_log(0)
+        r = e.design_descent(sp, n_steps, sp.maxiter, iters_per_step, shard(stiffness_bounds), shard(motor_inertia_bounds),
+                             eta0, grow, shrink, c1, max_rel, keep_history)
+        # the problem's own record of the table follows the engine's (a later engine of this problem starts from it)
+        low = p.lowered
+        old = low.traj_params or {}
+        low.traj_params = lower_traj_params(low.desc, low.nj, low.nu, low.nu_user, low.dam,
+                                            None if r.stiffness is None else r.stiffness.cpu().numpy(),
+                                            r.motor_inertia.cpu().numpy(), old.get("u_lb"), old.get("u_ub"))
+        return r
+
     def cost_sensitivity(self):
         """problem.cost_sensitivity() at this solver's solution (the committed xs / us of the last solve): per
         trajectory dJ/dK, dJ/dB, dJ/dx0 and the costates."""

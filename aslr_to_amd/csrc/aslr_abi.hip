@@ -13,6 +13,7 @@
 #include "../../include/aslr_to_amd_pool_params.h"
 #include "../../include/aslr_to_amd_cov.h"
 #include "../../include/aslr_to_amd_plant_sens.h"
+#include "../../include/aslr_to_amd_design.h"
 
 using namespace aslr;
 
@@ -316,6 +317,7 @@ struct aslr_problem {
   int32_t own_planar_reach;
   bool has_placement; // some model of the problem has a frame-placement cost
   std::vector<double> tp_host; // the table aslr_set_trajectory_params validated and uploaded last ([rows][B] like the region)
+  std::vector<double> tp_b_host; // ... and the motor inertia it was built from ([nj][B]: the table holds the reciprocals only)
 };
 
 namespace {
@@ -836,6 +838,41 @@ int build_param_rows(const char *fn, const aslr_problem *p, const aslr_traj_para
   return ASLR_OK;
 }
 
+// The two sweeps behind aslr_cost_sensitivity, shared with aslr_design_descent: calcDiff on (XS, US) as aslr_calc_diff runs it,
+// then adjoint_kernel with the diagonals of the models (the table's rows while one is set) into the outputs given (each
+// nullable).  Refuses nothing: the callers have checked what they must (diagonal K and B, no zero the kernel divides by).
+int adjoint_sweeps(aslr_problem *p, double *d_stiffness, double *d_motor_inertia, double *d_x0, double *costate, hipStream_t st) {
+  const int nj = p->nj, nm = p->desc.nmodels;
+  const bool sea = p->dam == ASLR_DAM_SEA;
+  const aslr_model_t *M = p->desc.models;
+  AdjointArgs a;
+  memset(&a, 0, sizeof a);
+  for (int i = 0; i < nm; ++i) {
+    a.dt[i] = M[i].dt;
+    for (int j = 0; j < nj; ++j) {
+      a.K[i][j] = sea ? M[i].K[j * nj + j] : 0.0;
+      a.Binv[i][j] = 1.0 / M[i].B[j * nj + j];
+    }
+  }
+  if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
+  const KArgs &k = p->k;
+  a.deriv = k.deriv; a.xs = k.xs; a.xnext = k.xnext; a.node_model = k.node_model;
+  a.traj_params = p->ks->traj_params ? reinterpret_cast<const double *>(region(p, ASLR_R_TRAJ_PARAMS)) : nullptr;
+  a.d_stiffness = d_stiffness; a.d_motor_inertia = d_motor_inertia; a.d_x0 = d_x0; a.costate = costate;
+  a.B = k.B; a.T = k.T;
+  return launch_adjoint(p->nx, p->nu, a, st);
+}
+
+// the motor inertia behind the reciprocal rows of build_param_rows, [nj][n]
+std::vector<double> motor_inertia_rows(const aslr_problem *p, const aslr_traj_params_t *tp, int n) {
+  const int nj = p->nj;
+  std::vector<double> bd((size_t)nj * n);
+  for (int b = 0; b < n; ++b)
+    for (int j = 0; j < nj; ++j)
+      bd[(size_t)j * n + b] = tp->motor_inertia ? tp->motor_inertia[(size_t)b * nj + j] : p->desc.models[0].B[j * nj + j];
+  return bd;
+}
+
 } // namespace
 
 extern "C" {
@@ -960,6 +997,7 @@ int aslr_set_trajectory_params(aslr_problem_t *p, const aslr_traj_params_t *tp, 
   HIP_TRY(hipMemcpyAsync(region(p, ASLR_R_TRAJ_PARAMS), h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st));
   p->tp_host.swap(h); // (kept: aslr_cost_sensitivity checks the stiffness rows on the host)
+  p->tp_b_host = motor_inertia_rows(p, tp, p->desc.B); // (kept: aslr_design_descent starts from B itself)
   switch_to(true);
   return ASLR_OK;
 }
@@ -1013,31 +1051,19 @@ int aslr_cost_sensitivity(aslr_problem_t *p, double *dcost_dstiffness, double *d
   if (dcost_dstiffness && !sea) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: dcost_dstiffness on a VSA model, which takes its stiffness from u");
   const int B = p->desc.B, nj = p->nj, nm = p->desc.nmodels;
   const aslr_model_t *M = p->desc.models;
-  AdjointArgs a;
-  memset(&a, 0, sizeof a);
   for (int i = 0; i < nm; ++i) {
     if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: K and B of model %d must be diagonal", i);
-    a.dt[i] = M[i].dt;
     for (int j = 0; j < nj; ++j) {
       const double k = M[i].K[j * nj + j], bj = M[i].B[j * nj + j];
       if (sea && !table && k == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: stiffness entry K[%d] of model %d is 0 (the stiffness term divides by it)", j, i);
       if (bj == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: motor inertia entry B[%d] of model %d is 0", j, i);
-      a.K[i][j] = sea ? k : 0.0;
-      a.Binv[i][j] = 1.0 / bj;
     }
   }
   if (sea && table)
     for (int j = 0; j < nj; ++j)
       for (int b = 0; b < B; ++b)
         if (p->tp_host[(size_t)j * B + b] == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: stiffness entry [%d][%d] of the parameter table is 0 (the stiffness term divides by it)", b, j);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
-  const KArgs &k = p->k;
-  a.deriv = k.deriv; a.xs = k.xs; a.xnext = k.xnext; a.node_model = k.node_model;
-  a.traj_params = table ? reinterpret_cast<const double *>(region(p, ASLR_R_TRAJ_PARAMS)) : nullptr;
-  a.d_stiffness = dcost_dstiffness; a.d_motor_inertia = dcost_dmotor_inertia; a.d_x0 = dcost_dx0; a.costate = costate;
-  a.B = k.B; a.T = k.T;
-  return launch_adjoint(p->nx, p->nu, a, st);
+  return adjoint_sweeps(p, dcost_dstiffness, dcost_dmotor_inertia, dcost_dx0, costate, static_cast<hipStream_t>(stream));
 }
 
 int aslr_policy_covariance(aslr_problem_t *p, const double *sigma0, const double *noise_var, double *x_var, double *u_var,
@@ -1329,6 +1355,139 @@ int aslr_mpc_run_plant(aslr_problem_t *p, const aslr_solver_params_t *sp, const 
   }
   if (p->ref_path_set) p->k.ref_row0 = row0 + (int32_t)N;
   return ASLR_OK;
+}
+
+// aslr_design_descent (include/aslr_to_amd_design.h): per outer step the launches of a solve that
+// never polls, aslr_finalize, the two sweeps of aslr_cost_sensitivity and design_step_kernel (aslr_design.hip).
+namespace {
+
+// design_step_kernel's argument block for step s of the run d describes on handle p
+DesignStepArgs design_step_args(aslr_problem *p, const aslr_design_t *d, int s, bool last) {
+  const size_t B = p->desc.B, rows = 2 * (size_t)p->nj;
+  const KArgs &k = p->k;
+  DesignStepArgs a;
+  memset(&a, 0, sizeof a);
+  a.xs = k.xs; a.us = k.us; a.gaps = k.gaps; a.vxxf = k.vxxf; a.kff = k.kff; a.traj_f = k.traj_f;
+  a.traj_params = reinterpret_cast<double *>(region(p, ASLR_R_TRAJ_PARAMS));
+  a.lo = d->lo; a.hi = d->hi; a.grad = d->grad;
+  a.theta = d->theta_best; a.cost_best = d->cost_best; a.xs_best = d->xs_best; a.us_best = d->us_best;
+  a.g_acc = d->g_acc; a.eta = d->eta;
+  a.hist_f = d->hist_f ? d->hist_f + (size_t)s * 3 * B : nullptr;
+  a.hist_i = d->hist_i ? d->hist_i + (size_t)s * B : nullptr;
+  a.theta_hist = d->theta_hist ? d->theta_hist + (size_t)s * rows * B : nullptr;
+  a.B = k.B; a.T = k.T; a.nx = p->nx; a.nu = p->nu; a.nj = p->nj;
+  a.s = s; a.last = last;
+  a.opt_k = d->opt_stiffness != 0; a.opt_b = d->opt_motor_inertia != 0;
+  a.eta0 = d->eta0; a.grow = d->grow; a.shrink = d->shrink; a.c1 = d->c1; a.max_rel = d->max_rel;
+  return a;
+}
+
+// the sweeps of aslr_cost_sensitivity on a handle with a table set, the gradients of the optimised fields into d->grad.
+// (No look at the stiffness rows on the host: inside the run they live on the device, and the bounds keep them positive.)
+int design_gradient(aslr_problem *p, const aslr_design_t *d, hipStream_t st) {
+  return adjoint_sweeps(p, d->opt_stiffness ? d->grad : nullptr, d->opt_motor_inertia ? d->grad + (size_t)p->nj * p->desc.B : nullptr,
+                        nullptr, nullptr, st);
+}
+
+} // namespace
+
+int aslr_design_descent(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_design_t *d, void *stream) {
+  const char *fn = "aslr_design_descent";
+  if (!p || !sp || !d) return fail(ASLR_E_INVALID, "%s: NULL argument: %s", fn, !p ? "the problem handle p" : !sp ? "sp" : "d");
+  if (d->n_steps < 1 || d->first_maxiter < 1 || d->iters_per_step < 1) return fail(ASLR_E_INVALID, "%s: n_steps, first_maxiter and iters_per_step must be >= 1", fn);
+  const bool opt_k = d->opt_stiffness != 0, opt_b = d->opt_motor_inertia != 0;
+  if (!opt_k && !opt_b) return fail(ASLR_E_INVALID, "%s: neither opt_stiffness nor opt_motor_inertia is set: nothing to optimise", fn);
+  if (opt_k && p->dam != ASLR_DAM_SEA) return fail(ASLR_E_INVALID, "%s: opt_stiffness on a VSA model, which takes its stiffness from u", fn);
+  if (!d->lo || !d->hi || !d->theta_best || !d->cost_best || !d->xs_best || !d->us_best || !d->g_acc || !d->eta || !d->grad)
+    return fail(ASLR_E_INVALID, "%s: lo, hi, theta_best, cost_best, xs_best, us_best, g_acc, eta and grad must be given", fn);
+  if (!(d->eta0 > 0.0) || !std::isfinite(d->eta0)) return fail(ASLR_E_INVALID, "%s: eta0 = %g must be finite and > 0", fn, d->eta0);
+  if (!(d->grow >= 1.0) || !std::isfinite(d->grow)) return fail(ASLR_E_INVALID, "%s: grow = %g must be finite and >= 1", fn, d->grow);
+  if (!(d->shrink > 0.0 && d->shrink < 1.0)) return fail(ASLR_E_INVALID, "%s: shrink = %g must lie in (0, 1)", fn, d->shrink);
+  if (!(d->c1 > 0.0 && d->c1 < 1.0)) return fail(ASLR_E_INVALID, "%s: c1 = %g must lie in (0, 1)", fn, d->c1);
+  if (!(d->max_rel > 0.0 && d->max_rel < 1.0)) return fail(ASLR_E_INVALID, "%s: max_rel = %g must lie in (0, 1)", fn, d->max_rel);
+  if (p->k.iter_log) return fail(ASLR_E_INVALID, "%s: an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)", fn);
+  if (int rc = solver_unsupported(fn, p, sp->solver)) return rc;
+  const int B = p->desc.B, nj = p->nj, nm = p->desc.nmodels;
+  const bool sea = p->dam == ASLR_DAM_SEA, had_table = p->ks->traj_params;
+  for (int i = 0; i < nm; ++i)
+    if (!is_diagonal(nj, p->desc.models[i].K) || !is_diagonal(nj, p->desc.models[i].B)) return fail(ASLR_E_INVALID, "%s: K and B of model %d must be diagonal", fn, i);
+  const KernelSet *tp_set = find_kernel_set(nj, p->dam, true);
+  if (!tp_set) return fail(ASLR_E_INVALID, "%s: no per-trajectory-parameter kernels for (nj=%d, dam=%d)", fn, nj, p->dam);
+  // ---- the initial design: the handle's table, or the models' constants lowered as aslr_set_trajectory_params lowers them ----
+  std::vector<double> rows, bdiag;
+  if (had_table) { rows = p->tp_host; bdiag = p->tp_b_host; }
+  else {
+    const aslr_traj_params_t none{nullptr, nullptr, nullptr, nullptr};
+    if (int rc = build_param_rows(fn, p, &none, B, &rows)) return rc;
+    bdiag = motor_inertia_rows(p, &none, B);
+  }
+  const size_t half = (size_t)nj * B;
+  std::vector<double> theta0(2 * half);
+  for (size_t i = 0; i < half; ++i) { theta0[i] = sea ? rows[i] : 0.0; theta0[half + i] = bdiag[i]; }
+  for (int j = 0; j < nj; ++j)
+    for (int b = 0; b < B; ++b) {
+      if (sea && !(theta0[(size_t)j * B + b] > 0.0)) return fail(ASLR_E_INVALID, "%s: stiffness entry [%d][%d] of the initial design is not positive", fn, b, j);
+      if (!(theta0[half + (size_t)j * B + b] > 0.0)) return fail(ASLR_E_INVALID, "%s: motor inertia entry [%d][%d] of the initial design is not positive", fn, b, j);
+    }
+  // ---- the bounds of the optimised fields, read back to be checked (before anything else is enqueued) ----
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::vector<double> lo(2 * half), hi(2 * half);
+  const size_t r0 = opt_k ? 0 : half, r1 = opt_b ? 2 * half : half;
+  HIP_TRY(hipMemcpyAsync(lo.data() + r0, d->lo + r0, sizeof(double) * (r1 - r0), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(hi.data() + r0, d->hi + r0, sizeof(double) * (r1 - r0), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (size_t i = r0; i < r1; ++i) {
+    const int r = (int)(i / B), b = (int)(i % B);
+    if (!(lo[i] > 0.0 && lo[i] <= hi[i] && std::isfinite(hi[i]))) return fail(ASLR_E_INVALID, "%s: bounds [%d][%d] are (%g, %g): 0 < lo <= hi must hold, finite", fn, b, r, lo[i], hi[i]);
+    if (!(lo[i] <= theta0[i] && theta0[i] <= hi[i])) return fail(ASLR_E_INVALID, "%s: entry [%d][%d] of the initial design, %g, lies outside its bounds [%g, %g]", fn, b, r, theta0[i], lo[i], hi[i]);
+  }
+  // ---- in place: the table (when the handle had none), theta_0.  The copies are staged from `rows` and `theta0`, which
+  // live until this function returns, and every return below follows a synchronisation of the stream ----
+  const auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) -> int { // (HIP_TRY would name the lambda)
+    const hipError_t ce = hipMemcpyAsync(dst, src, bytes, kind, st);
+    return ce == hipSuccess ? ASLR_OK : fail(ASLR_E_HIP, "%s: hipMemcpyAsync -> %s", fn, hipGetErrorString(ce));
+  };
+  const auto enqueue = [&]() -> int {
+    if (!had_table)
+      if (int rc = copy(region(p, ASLR_R_TRAJ_PARAMS), rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice)) return rc;
+    if (int rc = copy(d->theta_best, theta0.data(), sizeof(double) * theta0.size(), hipMemcpyHostToDevice)) return rc;
+    if (!had_table) {
+      p->tp_host = rows; p->tp_b_host = bdiag;
+      p->ks = tp_set;
+    }
+    p->const_written = false;
+    aslr_solver_params_t sps = *sp;
+    for (int s = 0; s < d->n_steps; ++s) {
+      if (s > 0) sps.is_feasible = 0; // the plan was made under other parameters
+      // a solve as aslr_solve enqueues it when the host never polls; its first sweep rewrites the model-only record chunks,
+      // which depend on the candidate the step kernel has just put into the table
+      IterOpts o{p->k, 0, true, nullptr};
+      o.fresh_first = true;
+      if (int rc = iterate(p, &sps, true, s == 0 ? d->first_maxiter : d->iters_per_step, st, o)) return rc;
+      if (int rc = aslr_finalize(p, stream)) return rc;
+      if (int rc = design_gradient(p, d, st)) return rc;
+      if (int rc = launch_design_step(design_step_args(p, d, s, s == d->n_steps - 1), st)) return rc;
+    }
+    // the table holds theta_acc now: the host copies follow it
+    if (int rc = copy(p->tp_host.data(), region(p, ASLR_R_TRAJ_PARAMS), sizeof(double) * p->tp_host.size(), hipMemcpyDeviceToHost)) return rc;
+    return copy(p->tp_b_host.data(), d->theta_best + half, sizeof(double) * half, hipMemcpyDeviceToHost);
+  };
+  const int rc = enqueue();
+  const hipError_t e = hipStreamSynchronize(st); // the call's one wait after the bounds check (also after a failed launch)
+  p->const_written = false; // the record chunks in place belong to the last candidate
+  if (rc) return rc;
+  if (e != hipSuccess) return fail(ASLR_E_HIP, "%s: hipStreamSynchronize -> %s", fn, hipGetErrorString(e));
+  return ASLR_OK;
+}
+
+// One launch of design_step_kernel on the handle's state, for the kernel-level test (tests/test_gpu_design.py): no header
+// declares it and nothing is checked beyond the pointers -- the caller has put every buffer of d in place.
+int aslr_debug_design_step(aslr_problem_t *p, const aslr_design_t *d, int32_t s, int32_t last, void *stream) {
+  if (!p || !d) return fail(ASLR_E_INVALID, "aslr_debug_design_step: NULL argument");
+  aslr_design_t one = *d; // (the history pointers are taken as those of THIS step)
+  DesignStepArgs a = design_step_args(p, &one, 0, last != 0);
+  a.s = s;
+  return launch_design_step(a, static_cast<hipStream_t>(stream));
 }
 
 int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool, int32_t refill_every,

@@ -260,6 +260,27 @@ struct MpcPlantArgs {
 };
 int launch_mpc_plant(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
 
+// One outer step of aslr_design_descent (aslr_design.hip): what design_step_kernel reads and writes, by value.  The workspace
+// pointers are the handle's; everything else is the caller's (include/aslr_to_amd_design.h).  Like the adjoint kernel it
+// depends on no model size at compile time and has no row in the table of kernel sets.
+struct DesignStepArgs {
+  double *xs, *us, *gaps, *vxxf, *kff;     // XS / US are copied to or from the best plan; the others are zeroed
+  const double *traj_f;                    // TF_COST: the cost of the finalized candidate
+  double *traj_params;                     // region TRAJ_PARAMS: column b takes the next candidate
+  const double *lo, *hi, *grad;            // [2 nj][B]: bounds, the gradient at the candidate
+  double *theta, *cost_best;               // [2 nj][B], [B]: the accepted design and its cost
+  double *xs_best, *us_best;               // [T+1][B][nx], [T][B][nu]
+  double *g_acc, *eta;                     // [2 nj][B], [B]; eta < 0 marks a frozen trajectory
+  double *hist_f;                          // [3][B] of this step, nullable
+  int32_t *hist_i;                         // [B] of this step, nullable
+  double *theta_hist;                      // [2 nj][B] of this step, nullable
+  int32_t B, T, nx, nu, nj;
+  int32_t s, last;                         // the step index; last: the table takes the accepted design, not a candidate
+  int32_t opt_k, opt_b;
+  double eta0, grow, shrink, c1, max_rel;
+};
+int launch_design_step(const DesignStepArgs &a, hipStream_t st);
+
 // the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
 struct KernelSet {
   int nj, dam;

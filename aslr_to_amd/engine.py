@@ -65,6 +65,17 @@ class PlantSensitivityResult(object):
         self.__dict__.update(fields)
 
 
+class DesignResult(object):
+    """What Engine.design_descent returns: batch-major device tensors -- stiffness [B, nj] (the accepted diag K; None for a
+    VSA model), motor_inertia [B, nj] (the accepted diag B), cost [B], xs [B, T+1, nx], us [B, T, nu] (the models' own nu) and,
+    when the history is kept, cost_history, eta_history, predicted_history [B, n_steps], accepted_history [B, n_steps]
+    (int32: 1 accepted, 0 rejected, -1 not evaluable), stiffness_history (None for VSA) and motor_inertia_history
+    [B, n_steps, nj]: the candidate evaluated in every step."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class Engine(object):
     """ShootingProblem shard resident in HBM.  Region layouts: include/aslr_to_amd.h."""
 
@@ -658,6 +669,70 @@ class Engine(object):
         return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
                          status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t(),
                          reference_row=self.reference_row, closed_cost=cc, failed_knot=fk, hold=h)
+
+    def design_descent(self, sp, n_steps, first_maxiter, iters_per_step, stiffness_bounds=None, motor_inertia_bounds=None,
+                       eta0=0.05, grow=2.0, shrink=0.5, c1=1e-4, max_rel=0.25, keep_history=False):
+        """A descent in every trajectory's own spring stiffness and motor inertia on the device (aslr_design_descent,
+        include/aslr_to_amd_design.h): per step a solve from the candidate in XS / US (first_maxiter iterations in step 0,
+        iters_per_step later), the gradient of cost_sensitivity, an Armijo test against the accepted design and the next
+        candidate, a bounded step in log theta.  One ABI call, no host round trip per step.  stiffness_bounds,
+        motor_inertia_bounds: (lo, hi), each [B, nj], [nj] or a scalar; a field whose bounds are None is not optimised.
+        The initial design is the parameter table if one is set, the models' constants otherwise.  -> DesignResult; XS /
+        US and the parameter table are left on the accepted design."""
+        torch = _torch()
+        B, T, nx, nu, nj = self.B, self.T, self.nx, self.nu, self.nx // 4
+        n = int(n_steps)
+        m = max(n, 0)
+
+        def rows(bounds, name):
+            """(lo, hi) -> two [nj, B] tensors (ones where the field is not optimised: never read)"""
+            if bounds is None:
+                return [torch.ones((nj, B), dtype=torch.float64, device=self.device)] * 2
+            if len(bounds) != 2:
+                raise ValueError("%s must be a pair (lo, hi)" % name)
+            out = []
+            for v in bounds:
+                t = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
+                                    device=self.device)
+                if t.dim() == 0:
+                    t = t.expand(nj)
+                if t.dim() == 1:
+                    t = t.unsqueeze(0).expand(B, -1)
+                if tuple(t.shape) != (B, nj):
+                    raise ValueError("%s entries must have shape [B=%d, nj=%d], [nj] or be scalars, not %s"
+                                     % (name, B, nj, list(t.shape)))
+                out.append(t.t())
+            return out
+
+        with torch.cuda.device(self.device):
+            (klo, khi), (blo, bhi) = rows(stiffness_bounds, "stiffness_bounds"), rows(motor_inertia_bounds, "motor_inertia_bounds")
+            lo, hi = torch.cat([klo, blo]).contiguous(), torch.cat([khi, bhi]).contiguous()
+            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
+            f64 = torch.float64
+            theta, cost, xb, ub = new(f64, 2 * nj, B), new(f64, B), new(f64, T + 1, B, nx), new(f64, T, B, nu)
+            gacc, eta, grad = new(f64, 2 * nj, B), new(f64, B), new(f64, 2 * nj, B)
+            hf = new(f64, m, 3, B) if keep_history else None
+            hi_ = new(torch.int32, m, B) if keep_history else None
+            th = new(f64, m, 2 * nj, B) if keep_history else None
+        ptr = lambda t: None if t is None else t.data_ptr()
+        d = _abi.Design()
+        d.n_steps, d.first_maxiter, d.iters_per_step = n, int(first_maxiter), int(iters_per_step)
+        d.opt_stiffness, d.opt_motor_inertia = int(stiffness_bounds is not None), int(motor_inertia_bounds is not None)
+        d.eta0, d.grow, d.shrink, d.c1, d.max_rel = float(eta0), float(grow), float(shrink), float(c1), float(max_rel)
+        d.lo, d.hi = ptr(lo), ptr(hi)
+        d.theta_best, d.cost_best, d.xs_best, d.us_best = ptr(theta), ptr(cost), ptr(xb), ptr(ub)
+        d.hist_f, d.hist_i, d.theta_hist = ptr(hf), ptr(hi_), ptr(th)
+        d.g_acc, d.eta, d.grad = ptr(gacc), ptr(eta), ptr(grad)
+        self._call("aslr_design_descent", C.byref(sp), C.byref(d), self._stream())
+        torch.cuda.synchronize(self.device)  # (the scratch tensors die on return)
+        vsa = self.low.dam == _abi.DAM_VSA
+        hist = {}
+        if keep_history:
+            hist = dict(cost_history=hf[:, 0].t(), eta_history=hf[:, 1].t(), predicted_history=hf[:, 2].t(),
+                        accepted_history=hi_.t(), stiffness_history=None if vsa else th[:, :nj].permute(2, 0, 1),
+                        motor_inertia_history=th[:, nj:].permute(2, 0, 1))
+        return DesignResult(stiffness=None if vsa else theta[:nj].t(), motor_inertia=theta[nj:].t(), cost=cost,
+                            xs=xb.permute(1, 0, 2), us=self.cut_u(ub.permute(1, 0, 2)), **hist)
 
     def traj_f(self, row):
         return self.region(_abi.R_TRAJ_F)[row]
