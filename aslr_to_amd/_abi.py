@@ -204,6 +204,9 @@ PLANT_SENS_SYMBOLS = ["aslr_policy_plant_sensitivity"]
 # what include/aslr_to_amd_design.h declares: a seventh extension header, in a list of its own for the same reason
 DESIGN_SYMBOLS = ["aslr_design_descent"]
 
+# what include/aslr_to_amd_policy_all.h declares: an eighth extension header, in a list of its own for the same reason
+POLICY_ALL_SYMBOLS = ["aslr_policy_rollout_all"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -283,6 +286,8 @@ def load_library():
     lib.aslr_cost_sensitivity.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.aslr_policy_rollout.restype = C.c_int
     lib.aslr_policy_rollout.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.aslr_policy_rollout_all.restype = C.c_int
+    lib.aslr_policy_rollout_all.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.aslr_mpc_run_plant.restype = C.c_int
     lib.aslr_mpc_run_plant.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
     lib.aslr_solve_pool_params.restype = C.c_int

@@ -13,6 +13,7 @@
 #include "../../include/aslr_to_amd_pool_params.h"
 #include "../../include/aslr_to_amd_cov.h"
 #include "../../include/aslr_to_amd_plant_sens.h"
+#include "../../include/aslr_to_amd_policy_all.h"
 #include "../../include/aslr_to_amd_design.h"
 
 using namespace aslr;
@@ -1144,7 +1145,7 @@ int aslr_policy_rollout(aslr_problem_t *p, int n_samples, const double *plant_st
   if (!cost && !failed_knot && !x_final && !xs_closed && !us_closed)
     return fail(ASLR_E_INVALID, "aslr_policy_rollout: all five outputs are NULL: nothing to compute");
   if (p->nj != 2)
-    return fail(ASLR_E_INVALID, "aslr_policy_rollout: the roll-out kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint team form is not built)", p->nj);
+    return fail(ASLR_E_INVALID, "aslr_policy_rollout: the roll-out kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint team form is not built); aslr_policy_rollout_all serves every size", p->nj);
   if (plant_stiffness && p->dam != ASLR_DAM_SEA)
     return fail(ASLR_E_INVALID, "aslr_policy_rollout: plant_stiffness on a VSA model, which takes its stiffness from u");
   const bool table = p->ks->traj_params;
@@ -1159,6 +1160,34 @@ int aslr_policy_rollout(aslr_problem_t *p, int n_samples, const double *plant_st
   a.S = n_samples; a.clamp = clamp != 0;
   a.table = table; a.diagonal = table || plant_stiffness || plant_motor_inertia;
   return launch_policy_rollout(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+}
+
+int aslr_policy_rollout_all(aslr_problem_t *p, int n_samples, const double *plant_stiffness, const double *plant_motor_inertia,
+                            const double *dx0, const double *disturbance, int clamp, double *cost, int32_t *failed_knot,
+                            double *x_final, double *xs_closed, double *us_closed, void *stream) {
+  if (!p) return no_handle("aslr_policy_rollout_all");
+  if (n_samples <= 0) return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: n_samples is %d, must be positive", n_samples);
+  // (16 samples per block along grid y for both kernels)
+  if (n_samples > 16 * 65535) return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: n_samples is %d, above the %d of one launch", n_samples, 16 * 65535);
+  if (!cost && !failed_knot && !x_final && !xs_closed && !us_closed)
+    return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: all five outputs are NULL: nothing to compute");
+  if (p->nj != 2 && p->nj != 7)
+    return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: no roll-out kernel for this %d-joint handle", p->nj);
+  if (plant_stiffness && p->dam != ASLR_DAM_SEA)
+    return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: plant_stiffness on a VSA model, which takes its stiffness from u");
+  const bool table = p->ks->traj_params;
+  if (plant_stiffness || plant_motor_inertia)
+    for (int i = 0; i < p->desc.nmodels; ++i)
+      if (!is_diagonal(p->nj, p->desc.models[i].K) || !is_diagonal(p->nj, p->desc.models[i].B))
+        return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: a plant argument needs diagonal K and B, and those of model %d are not", i);
+  PolicyArgs a;
+  memset(&a, 0, sizeof a);
+  a.plant_stiffness = plant_stiffness; a.plant_motor_inertia = plant_motor_inertia; a.dx0 = dx0; a.disturbance = disturbance;
+  a.cost = cost; a.failed_knot = failed_knot; a.x_final = x_final; a.xs_closed = xs_closed; a.us_closed = us_closed;
+  a.S = n_samples; a.clamp = clamp != 0;
+  a.table = table; a.diagonal = table || plant_stiffness || plant_motor_inertia;
+  if (p->nj == 2) return launch_policy_rollout(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+  return launch_policy_rollout_team(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
 }
 
 int aslr_backward_pass(aslr_problem_t *p, const aslr_solver_params_t *sp, void *stream) {

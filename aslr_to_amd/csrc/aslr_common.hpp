@@ -244,6 +244,8 @@ struct PolicyArgs {
   int32_t diagonal; // a plant array or a table is in use (every model's K and B is diagonal then): diagonals through ModelRegs::set_traj
 };
 int launch_policy_rollout(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st);
+// the nx = 28 sizes of the same roll-out (aslr_policy_rollout_all, aslr_policy_team.inc.hpp): 8-lane teams, the same arguments
+int launch_policy_rollout_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st);
 
 // The plant phase of one control step of aslr_mpc_run_plant (aslr_mpc_plant.inc.hpp): the caller's arrays, by value, beside
 // the KArgs and ModelLimits of the handle; `table` and `diagonal` as in PolicyArgs.  Like the policy kernel it has no row in

@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
   }
 }
 
-// the nx = 8 sizes; the 7-joint team form is not built
+// the nx = 8 sizes; the 7-joint team form is policy_rollout_team_kernel (aslr_policy_team.inc.hpp, aslr_policy_rollout_all)
 int launch_policy_rollout(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st) {
   const dim3 grid((k.B + 3) / 4, (pa.S + 15) / 16), block(64);
   const auto go = [&](auto NJc, auto DAMc) {

@@ -1,0 +1,269 @@
+// aslr_policy_team.inc.hpp -- closed-loop roll-outs of the stored policy on a perturbed plant for the larger chain
+// (7-DoF SEA / VSA): aslr_policy_rollout_all, include/aslr_to_amd_policy_all.h, DESIGN.md 4.17.
+//
+//   policy_rollout_team_kernel   A TEAM OF 8 LANES PER (trajectory, SAMPLE), with the lane roles of rollout_team_kernel
+//                                (aslr_forward_team.inc.hpp): lane c < NJ owns row c of the control law (rows c and NJ + c
+//                                for VSA), joint c's rotation, column c of M and of M^-1 and entry c of the Euler step; lane
+//                                NJ owns the nonlinear effects.  What differs:
+//     - the team index is the sample: one block = 2 waves = 16 samples of ONE trajectory, so what the samples share --
+//       [K_t | xs_t | us_t | reference placement of the knot] -- is staged once per wave and prefetched one knot ahead;
+//     - every team has its own plant: lane c holds K_cc and 1 / B_cc of its sample (the caller's arrays, else the row of
+//       the parameter table, else the model's row -- the full row, so a non-diagonal model without a plant argument still
+//       rolls out), its entries of the initial-state offset and of the disturbance;
+//     - the node cost is evaluated inside the kernel (knot_eval<..., kEvalCost> on the team's state and applied control)
+//       and summed per sample in knot order: S x B costs leave the device unless trajectories are asked for.  Every lane
+//       of the team evaluates the cost of its team's knot: one instruction stream, no divergence inside the wave, and
+//       the time of one evaluation -- what a single lane per team would take, the other seven masked off;
+//     - it writes nothing but the caller's buffers.
+#pragma once
+#include "aslr_forward_team.inc.hpp"
+
+namespace aslr {
+
+template <int NJ, int DAM>
+__global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, ModelLimits lim, PolicyArgs pa) {
+  using C = FwdTeam<NJ, DAM>;
+  constexpr int NX = C::NX, NU = C::NU;
+  constexpr bool VSA = C::VSA;
+  constexpr int TPB = 16; // teams (samples) per block
+  // per-wave stage (doubles): K, xs, us of the current knot and its reference placement
+  constexpr int oK = 0, oXr = oK + NU * NX, oU = oXr + NX, oFr = (oU + NU + 1) / 2 * 2, STG = oFr + 12, NSLOT = (STG + 63) / 64;
+  __shared__ double sm[2 * STG + TPB * C::TEAM_LDS];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, team = tid >> 3, c = tid & 7;
+  const int B = a.B, T = a.T, S = pa.S, b = blockIdx.x;
+  // teams past S run on clamped indices (the arithmetic of a sample is the same instruction stream wherever it sits);
+  // only their stores are guarded
+  const int sq = blockIdx.y * TPB + team, s = sq < S ? sq : S - 1;
+  const bool on = sq < S;
+  double *stg = sm + wv * STG, *tm_ = sm + 2 * STG + team * C::TEAM_LDS;
+  double *xT = tm_ + C::tX, *uT = tm_ + C::tU, *tcL = tm_ + C::tTc, *tmL = tm_ + C::tTm, *RL = tm_ + C::tR,
+         *ML = tm_ + C::tM, *MiL = tm_ + C::tMi;
+  const bool jl = c < NJ; // this lane owns joint / row cj
+  const int cj = jl ? c : NJ - 1;
+  const DevDesc &D = *a.desc;
+  const aslr_chain_t &ch = D.chain;
+  const chain_cp chc = chain_const(&D.chain);
+  const unsigned long long team_bits = 0xffull << ((lane >> 3) * 8);
+
+  // ---- stage slots: element idx = lane + 64 q of [K | xs | us | placement] at knot t ----
+  const double *sp0[NSLOT];
+  size_t sstr[NSLOT];
+  bool son[NSLOT], sctl[NSLOT];
+  ASLR_UNROLL for (int q = 0; q < NSLOT; ++q) {
+    const int idx = lane + 64 * q;
+    sp0[q] = a.xs; sstr[q] = 0; son[q] = false; sctl[q] = false;
+    if (idx < oXr) { sp0[q] = a.kgain + (size_t)b * NU * NX + idx; sstr[q] = (size_t)B * NU * NX; son[q] = true; sctl[q] = true; }
+    else if (idx < oU) { sp0[q] = a.xs + (size_t)b * NX + (idx - oXr); sstr[q] = (size_t)B * NX; son[q] = true; sctl[q] = true; }
+    else if (idx < oU + NU) { sp0[q] = a.us + (size_t)b * NU + (idx - oU); sstr[q] = (size_t)B * NU; son[q] = true; sctl[q] = true; }
+    else if (idx >= oFr && idx < STG && a.frame_ref) { sp0[q] = a.frame_ref + (size_t)b * 12 + (idx - oFr); sstr[q] = (size_t)B * 12; son[q] = true; }
+  }
+  double pf[NSLOT];
+  auto prefetch = [&](int t) {
+    const size_t row = (size_t)min(a.ref_row0 + t, a.ref_last); // (the knot's row of the reference path)
+    ASLR_UNROLL for (int q = 0; q < NSLOT; ++q) {
+      pf[q] = 0.0;
+      if (son[q] && (!sctl[q] || t < T)) pf[q] = sp0[q][(sctl[q] ? (size_t)t : row) * sstr[q]];
+    }
+  };
+
+  // ---- the plant of this team, entry cj: the caller's arrays [nj][S][B] where given, else the trajectory's row of the
+  // parameter table where one is set, else (use_k / use_b false) the row of the knot's model ----
+  const bool table = pa.table != 0, use_k = pa.plant_stiffness || table, use_b = pa.plant_motor_inertia || table;
+  double k_cj = 0.0, b_cj = 0.0, lb_c = 0.0, ub_c = 0.0, lb_s = 0.0, ub_s = 0.0; // (lb_s / ub_s: the stiffness row, VSA)
+  if (table) {
+    const double *tp = traj_params_at(D, b);
+    k_cj = tp[(size_t)cj * B];
+    b_cj = tp[(size_t)(NJ + cj) * B];
+    lb_c = tp[(size_t)(2 * NJ + cj) * B];
+    ub_c = tp[(size_t)(2 * NJ + NU + cj) * B];
+    if (VSA) { lb_s = tp[(size_t)(3 * NJ + cj) * B]; ub_s = tp[(size_t)(3 * NJ + NU + cj) * B]; }
+  }
+  if (pa.plant_stiffness) k_cj = pa.plant_stiffness[((size_t)cj * S + s) * B + b];
+  if (pa.plant_motor_inertia) b_cj = 1.0 / pa.plant_motor_inertia[((size_t)cj * S + s) * B + b];
+  double Krow[NJ], Srow[NJ], Brow[NJ], dt = 0.0;
+  ASLR_UNROLL for (int j = 0; j < NJ; ++j) { Krow[j] = 0.0; Srow[j] = 0.0; Brow[j] = 0.0; }
+  bool has_lim = false;
+  int m_loaded = -1;
+
+  // joint placements and axes: constants of the chain, staged once in LDS (rollout_team_kernel says why)
+  __shared__ double jtab[8][12];
+  if (threadIdx.x < NJ) {
+    ASLR_UNROLL for (int k = 0; k < 9; ++k) jtab[threadIdx.x][k] = ch.joint_R[threadIdx.x][k];
+    ASLR_UNROLL for (int k = 0; k < 3; ++k) jtab[threadIdx.x][9 + k] = ch.axis[threadIdx.x][k];
+  }
+  __syncthreads();
+
+  // x0 (+ the sample's offset) into the team's state
+  ASLR_UNROLL for (int k = 0; k < 4; ++k) {
+    const int e = c + 8 * k;
+    if (e < NX) {
+      double v = a.x0[(size_t)b * NX + e];
+      if (pa.dx0) v += pa.dx0[((size_t)s * B + b) * NX + e]; // (no `+ 0.0` without it: the sign of a zero is a bit too)
+      xT[e] = v;
+    }
+  }
+  // the disturbance of the knot ahead, this lane's entries cj, NJ + cj, 2 NJ + cj, 3 NJ + cj of the state
+  const double *wsrc = pa.disturbance ? pa.disturbance + ((size_t)s * T * B + b) * NX + cj : nullptr; // knot t at + t B NX
+  double wn[4] = {0.0, 0.0, 0.0, 0.0};
+  auto load_w = [&](int t) {
+    ASLR_UNROLL for (int k = 0; k < 4; ++k) wn[k] = wsrc[(size_t)t * B * NX + k * NJ];
+  };
+  if (wsrc && T > 0) load_w(0);
+  double *xs_o = pa.xs_closed ? pa.xs_closed + ((size_t)s * (T + 1) * B + b) * NX : nullptr; // knot t at + t B NX
+  double *us_o = pa.us_closed ? pa.us_closed + ((size_t)s * T * B + b) * NU : nullptr;
+  auto store_x = [&](int t) { // the team's state as row t of xs_closed, 4 contiguous entries per lane
+    if (on && jl && xs_o) {
+      double *o = xs_o + (size_t)t * B * NX + 4 * c;
+      *reinterpret_cast<double2 *>(o) = make_double2(xT[4 * c], xT[4 * c + 1]);
+      *reinterpret_cast<double2 *>(o + 2) = make_double2(xT[4 * c + 2], xT[4 * c + 3]);
+    }
+  };
+  const typename Chain3D<NJ>::Consts cc(D, true);
+  ModelRegs<NJ, NU> mr; // (the cost stack reads none of it)
+
+  double J = 0.0;
+  int failed = -1;
+  prefetch(0);
+  for (int t = 0; t <= T; ++t) {
+    wave_sync(); // the previous knot's readers of the stage are done, its state is written
+    ASLR_UNROLL for (int q = 0; q < NSLOT; ++q) { if (lane + 64 * q < STG) stg[lane + 64 * q] = pf[q]; }
+    const int mi = node_model_at(a, t);
+    wave_sync();
+    const DevModel &dm = D.models[mi];
+    if (t < T && mi != m_loaded) { // wave-uniform: model constants and control limits, re-read only when the model changes
+      dt = dm.m.dt;
+      ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
+        if (!VSA) {
+          // (pa.diagonal is the host's fact: a plant array or a table, both of which need diagonal models)
+          Krow[j] = pa.diagonal ? ((j == cj) ? (use_k ? k_cj : dm.m.K[cj * NJ + cj]) : 0.0) : dm.m.K[cj * NJ + j];
+          Srow[j] = dm.m.S[cj * NU + j];
+        }
+        Brow[j] = pa.diagonal ? ((j == cj) ? (use_b ? b_cj : dm.Binv[cj * NJ + cj]) : 0.0) : dm.Binv[cj * NJ + j];
+      }
+      has_lim = lim.has[mi] != 0;
+      if (!table) {
+        lb_c = lim.lb[mi][cj];
+        ub_c = lim.ub[mi][cj];
+        if (VSA) { lb_s = lim.lb[mi][NJ + cj]; ub_s = lim.ub[mi][NJ + cj]; }
+      }
+      m_loaded = mi;
+    }
+    // ---- control law, row cj: u = us - K (x - xs), box clamp when asked for ----
+    double u_c = 0.0, u_s = 0.0; // this lane's entries of the applied control (u_s: the stiffness command, VSA)
+    if (t < T) {
+      u_c = stg[oU + cj];
+      ASLR_UNROLL for (int jx = 0; jx < NX; ++jx) u_c -= stg[oK + cj * NX + jx] * (xT[jx] - stg[oXr + jx]);
+      if (pa.clamp && has_lim) u_c = fmin(fmax(u_c, lb_c), ub_c);
+      if (jl) uT[c] = u_c;
+      if constexpr (VSA) { // row NJ + cj: the stiffness command of joint cj
+        u_s = stg[oU + NJ + cj];
+        ASLR_UNROLL for (int jx = 0; jx < NX; ++jx) u_s -= stg[oK + (NJ + cj) * NX + jx] * (xT[jx] - stg[oXr + jx]);
+        if (pa.clamp && has_lim) u_s = fmin(fmax(u_s, lb_s), ub_s);
+        if (jl) uT[NJ + c] = u_s;
+      }
+    }
+    wave_sync();
+    // ---- node cost of the team's knot: its state and the applied control; the terminal node with the model's "u is None"
+    // default.  One call site for both, BEFORE the loads of the next knot are issued: the cost stack reads its terms from
+    // global memory, and behind those loads its waits would be waits for the prefetch ----
+    {
+      double x[NX], u[NU], xnext[NX], cst = 0.0;
+      ASLR_UNROLL for (int i = 0; i < NX; ++i) x[i] = xT[i];
+      ASLR_UNROLL for (int i = 0; i < NU; ++i) u[i] = uT[i];
+      knot_eval<NJ, DAM, kEvalCost, Chain3D<NJ>>(cc, mr, dm, a.frame_ref ? stg + oFr : nullptr, x, t < T ? u : nullptr, xnext, cst, nullptr);
+      J += cst; // (knot order)
+    }
+    if (t == T) { store_x(t); break; }
+    double w[4];
+    ASLR_UNROLL for (int k = 0; k < 4; ++k) w[k] = wn[k];
+    prefetch(t + 1); // in flight while the dynamics of knot t compute
+    if (wsrc && t + 1 < T) load_w(t + 1);
+    // (the optional stores of a knot go out after the loads of the next one)
+    store_x(t);
+    if (on && jl && us_o) {
+      us_o[(size_t)t * B * NU + c] = u_c;
+      if constexpr (VSA) us_o[(size_t)t * B * NU + NJ + c] = u_s;
+    }
+    // ---- rotation of joint cj ----
+    if (jl) {
+      const M3 R = mul(m3(jtab[cj]), axis_angle(v3(jtab[cj] + 9), xT[cj]));
+      ASLR_UNROLL for (int k = 0; k < 9; ++k) RL[9 * c + k] = R.a[k];
+    }
+    wave_sync();
+    // ---- coupling and motor torques, entry cj ----
+    if (jl) {
+      double sc_ = 0.0, s2 = 0.0;
+      if constexpr (VSA) { // K = diag(stiffness commands), tau_m = the torque commands
+        ASLR_UNROLL for (int j = 0; j < NJ; ++j) sc_ += (j == c ? uT[NJ + c] : 0.0) * (xT[j] - xT[NJ + j]);
+        s2 = uT[c];
+      } else {
+        ASLR_UNROLL for (int j = 0; j < NJ; ++j) { sc_ += Krow[j] * (xT[j] - xT[NJ + j]); s2 += Srow[j] * uT[j]; }
+      }
+      tcL[c] = sc_;
+      tmL[c] = s2;
+    }
+    // ---- one RNEA per lane: column c of M (lanes c < NJ), nonlinear effects (lane NJ) ----
+    if (c <= NJ) {
+      double vv[NJ], aa[NJ], tau[NJ];
+      const bool nl = c == NJ;
+      ASLR_UNROLL for (int i = 0; i < NJ; ++i) { vv[i] = nl ? xT[2 * NJ + i] : 0.0; aa[i] = (!nl && i == c) ? 1.0 : 0.0; }
+      const V3 g = v3(chc->gravity);
+      const V3 grav = nl ? g : V3{0.0, 0.0, 0.0};
+      rnea_lds<NJ>(chc, RL, vv, aa, grav, tau);
+      ASLR_UNROLL for (int i = 0; i < NJ; ++i) ML[8 * c + i] = tau[i];
+    }
+    wave_sync();
+    // ---- column cj of M^-1 (M symmetrised like Chain3D::mass) ----
+    {
+      double Ms[NJ][NJ], e[NJ];
+      ASLR_UNROLL for (int i = 0; i < NJ; ++i)
+        ASLR_UNROLL for (int j = 0; j <= i; ++j) {
+          Ms[i][j] = (i == j) ? ML[8 * j + i] : 0.5 * (ML[8 * j + i] + ML[8 * i + j]);
+          Ms[j][i] = Ms[i][j];
+        }
+      spd_inverse_col<NJ>(Ms, cj, e);
+      if (jl) { ASLR_UNROLL for (int i = 0; i < NJ; ++i) MiL[8 * c + i] = e[i]; }
+    }
+    wave_sync();
+    // ---- accelerations and semi-implicit Euler, entries cj of q_l, q_m, v_l, v_m ----
+    double al = 0.0, am = 0.0;
+    ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
+      al += MiL[8 * j + cj] * (-ML[8 * NJ + j] - tcL[j]);
+      am += Brow[j] * (tmL[j] + tcL[j]);
+    }
+    const double ql = xT[cj], qm = xT[NJ + cj], vl = xT[2 * NJ + cj], vm = xT[3 * NJ + cj];
+    const double nql = ql + (vl * dt + al * dt * dt), nvl = vl + al * dt;
+    const double nqm = qm + (vm * dt + am * dt * dt), nvm = vm + am * dt;
+    const double nxt[4] = {nql, nvl, nqm, nvm}; // this lane's entries of xnext: |xnext|_inf test, entry by entry
+    const bool bad = jl && inf_norm_bad<4>(fabs(nql) + fabs(nvl) + fabs(nqm) + fabs(nvm), nxt);
+    if ((__ballot(bad) & team_bits) && failed < 0) failed = t; // NaN / Inf / |xnext|_inf >= 1e30, as the solver's rollout
+    wave_sync(); // every lane of the team has read the old state
+    if (jl) {
+      if (wsrc) { xT[c] = nql + w[0]; xT[NJ + c] = nqm + w[1]; xT[2 * NJ + c] = nvl + w[2]; xT[3 * NJ + c] = nvm + w[3]; }
+      else { xT[c] = nql; xT[NJ + c] = nqm; xT[2 * NJ + c] = nvl; xT[3 * NJ + c] = nvm; }
+    }
+  }
+  if (!on) return;
+  const size_t sb = (size_t)s * B + b;
+  if (c == 0) {
+    if (pa.cost) pa.cost[sb] = failed >= 0 ? NAN : J;
+    if (pa.failed_knot) pa.failed_knot[sb] = failed;
+  }
+  if (jl && pa.x_final) { // (the state of knot T: nothing has written it since the loop's last fence)
+    double *o = pa.x_final + sb * NX + 4 * c;
+    *reinterpret_cast<double2 *>(o) = make_double2(xT[4 * c], xT[4 * c + 1]);
+    *reinterpret_cast<double2 *>(o + 2) = make_double2(xT[4 * c + 2], xT[4 * c + 3]);
+  }
+}
+
+// the nx = 28 sizes: grid (trajectories, groups of 16 samples), one block = 2 waves of 8 teams
+int launch_policy_rollout_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st) {
+  const dim3 grid(k.B, (pa.S + 15) / 16), block(128);
+  if (nj == 7 && dam == ASLR_DAM_SEA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_SEA>), grid, block, 0, st, k, lim, pa);
+  else if (nj == 7 && dam == ASLR_DAM_VSA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_VSA>), grid, block, 0, st, k, lim, pa);
+  else return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: no team roll-out kernel for nj = %d", nj);
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
+
+} // namespace aslr

@@ -346,7 +346,8 @@ class Engine(object):
     def policy_rollout(self, n_samples, plant_stiffness=None, plant_motor_inertia=None, dx0=None, disturbance=None,
                        clamp=False, keep_trajectories=False):
         """Closed-loop roll-outs of the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), on n_samples = S perturbed
-        plants per trajectory (aslr_policy_rollout, include/aslr_to_amd_policy.h).  Batch-major arrays or tensors, each
+        plants per trajectory (aslr_policy_rollout, include/aslr_to_amd_policy.h; on the 7-joint arms aslr_policy_rollout_all,
+        include/aslr_to_amd_policy_all.h).  Batch-major arrays or tensors, each
         optional: plant_stiffness, plant_motor_inertia [B, S, nj] (diagonals of the plant's K and B; None: the
         trajectory's own), dx0 [B, S, nx] (added to x0), disturbance [B, S, T, nx] (added to the next state of every
         knot).  clamp: clamp the control to the knot's box.  -> PolicyRolloutResult.  Writes nothing into the workspace.
@@ -378,7 +379,8 @@ class Engine(object):
             xs = new(torch.float64, n, T + 1, B, nx) if keep_trajectories else None
             us = new(torch.float64, n, T, B, nu) if keep_trajectories else None
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._call("aslr_policy_rollout", S, ptr(pk), ptr(pb), ptr(d0), ptr(w), 1 if clamp else 0, ptr(cost), ptr(failed),
+        # (2 joints: the entry point that has always served them; every other size: the one that serves all sizes)
+        self._call("aslr_policy_rollout" if nj == 2 else "aslr_policy_rollout_all", S, ptr(pk), ptr(pb), ptr(d0), ptr(w), 1 if clamp else 0, ptr(cost), ptr(failed),
                    ptr(xf), ptr(xs), ptr(us), self._stream())
         return PolicyRolloutResult(cost=cost.t(), failed_knot=failed.t(), x_final=xf.permute(1, 0, 2),
                                    xs=None if xs is None else xs.permute(2, 0, 1, 3),
