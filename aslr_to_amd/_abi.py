@@ -207,6 +207,9 @@ DESIGN_SYMBOLS = ["aslr_design_descent"]
 # what include/aslr_to_amd_policy_all.h declares: an eighth extension header, in a list of its own for the same reason
 POLICY_ALL_SYMBOLS = ["aslr_policy_rollout_all"]
 
+# what include/aslr_to_amd_mpc_plant_all.h declares: a ninth extension header, in a list of its own for the same reason
+MPC_PLANT_ALL_SYMBOLS = ["aslr_mpc_run_plant_all"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -290,6 +293,8 @@ def load_library():
     lib.aslr_policy_rollout_all.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.aslr_mpc_run_plant.restype = C.c_int
     lib.aslr_mpc_run_plant.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
+    lib.aslr_mpc_run_plant_all.restype = C.c_int
+    lib.aslr_mpc_run_plant_all.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
     lib.aslr_solve_pool_params.restype = C.c_int
     lib.aslr_solve_pool_params.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Pool), C.POINTER(PoolParams), i32, i32, vp,
                                            C.POINTER(i32)]

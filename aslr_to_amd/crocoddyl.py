@@ -495,7 +495,8 @@ class SolverDDP(object):
         reference_row + s + t; afterwards problem.reference_row has grown by n_steps (MpcResult.reference_row).
         -> engine.MpcResult; solver.xs / us are the last shifted plan.
 
-        On a plant that differs from the model (aslr_mpc_run_plant; any of the following away from its default): hold = h
+        On a plant that differs from the model (aslr_mpc_run_plant; aslr_mpc_run_plant_all on the 7-joint arms, so every
+        model size is served; any of the following away from its default): hold = h
         re-plans only every h knots and tracks with the Riccati gains of the last solve in between, u = us_j - K_j (x -
         xs_j); plant_stiffness / plant_motor_inertia [B, nj] are the diagonals of the plant's K and B (no plant_stiffness
         for a VSA model); clamp: clamp the applied controls to the box, None = iff this solver is SolverBoxDDP;

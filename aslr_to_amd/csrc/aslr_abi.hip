@@ -14,6 +14,7 @@
 #include "../../include/aslr_to_amd_cov.h"
 #include "../../include/aslr_to_amd_plant_sens.h"
 #include "../../include/aslr_to_amd_policy_all.h"
+#include "../../include/aslr_to_amd_mpc_plant_all.h"
 #include "../../include/aslr_to_amd_design.h"
 
 using namespace aslr;
@@ -1332,15 +1333,19 @@ int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_m
   return ASLR_OK;
 }
 
-int aslr_mpc_run_plant(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, int hold,
-                       const double *plant_stiffness, const double *plant_motor_inertia, int clamp, double *closed_cost,
-                       int32_t *failed_knot, void *stream) {
-  const char *fn = "aslr_mpc_run_plant";
+// aslr_mpc_run_plant and aslr_mpc_run_plant_all (include/aslr_to_amd_mpc_plant_all.h): one body.  fn: the entry point a
+// refusal names; arms: 7-joint handles are admitted (their plant phase is mpc_plant_team_kernel's)
+namespace {
+int mpc_run_plant(const char *fn, bool arms, aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, int hold,
+                  const double *plant_stiffness, const double *plant_motor_inertia, int clamp, double *closed_cost,
+                  int32_t *failed_knot, void *stream) {
   if (int rc = mpc_refusals(fn, p, sp, mpc)) return rc;
   const int T = p->desc.T;
   if (hold < 1 || hold > T) return fail(ASLR_E_INVALID, "%s: hold = %d must lie in [1, T = %d]", fn, hold, T);
-  if (p->nj != 2)
-    return fail(ASLR_E_INVALID, "%s: the plant kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint form is not built; aslr_mpc_run serves it)", fn, p->nj);
+  if (p->nj != 2 && !arms)
+    return fail(ASLR_E_INVALID, "%s: the plant kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle; aslr_mpc_run_plant_all serves every size", fn, p->nj);
+  if (p->nj != 2 && p->nj != 7)
+    return fail(ASLR_E_INVALID, "%s: no plant kernel for this %d-joint handle", fn, p->nj);
   if (plant_stiffness && p->dam != ASLR_DAM_SEA)
     return fail(ASLR_E_INVALID, "%s: plant_stiffness on a VSA model, which takes its stiffness from u", fn);
   if (plant_stiffness || plant_motor_inertia)
@@ -1373,7 +1378,7 @@ int aslr_mpc_run_plant(aslr_problem_t *p, const aslr_solver_params_t *sp, const 
     pa.closed_cost = closed_cost; pa.failed_knot = failed_knot;
     pa.hold = hold; pa.k0 = (int32_t)k0; pa.first = s == 0; pa.clamp = clamp != 0;
     pa.table = table; pa.diagonal = table || plant_stiffness || plant_motor_inertia;
-    if (int rc = launch_mpc_plant(p->nj, p->dam, ks, p->limits, pa, st)) return rc;
+    if (int rc = (p->nj == 2 ? launch_mpc_plant : launch_mpc_plant_team)(p->nj, p->dam, ks, p->limits, pa, st)) return rc;
     MpcHoldDev m;
     m.nx = p->nx; m.nu = p->nu; m.h = hold;
     m.xplus = mpc->x_closed + (k0 + hold) * B * nx; // (the plant kernel left x+ in the row behind its last record)
@@ -1384,6 +1389,19 @@ int aslr_mpc_run_plant(aslr_problem_t *p, const aslr_solver_params_t *sp, const 
   }
   if (p->ref_path_set) p->k.ref_row0 = row0 + (int32_t)N;
   return ASLR_OK;
+}
+} // namespace
+
+int aslr_mpc_run_plant(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, int hold,
+                       const double *plant_stiffness, const double *plant_motor_inertia, int clamp, double *closed_cost,
+                       int32_t *failed_knot, void *stream) {
+  return mpc_run_plant("aslr_mpc_run_plant", false, p, sp, mpc, hold, plant_stiffness, plant_motor_inertia, clamp, closed_cost, failed_knot, stream);
+}
+
+int aslr_mpc_run_plant_all(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, int hold,
+                           const double *plant_stiffness, const double *plant_motor_inertia, int clamp, double *closed_cost,
+                           int32_t *failed_knot, void *stream) {
+  return mpc_run_plant("aslr_mpc_run_plant_all", true, p, sp, mpc, hold, plant_stiffness, plant_motor_inertia, clamp, closed_cost, failed_knot, stream);
 }
 
 // aslr_design_descent (include/aslr_to_amd_design.h): per outer step the launches of a solve that

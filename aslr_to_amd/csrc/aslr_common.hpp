@@ -261,6 +261,8 @@ struct MpcPlantArgs {
   int32_t table, diagonal;
 };
 int launch_mpc_plant(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
+// the nx = 28 sizes of the same plant phase (aslr_mpc_run_plant_all, aslr_mpc_plant_team.inc.hpp): 8-lane teams, the same arguments
+int launch_mpc_plant_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
 
 // One outer step of aslr_design_descent (aslr_design.hip): what design_step_kernel reads and writes, by value.  The workspace
 // pointers are the handle's; everything else is the caller's (include/aslr_to_amd_design.h).  Like the adjoint kernel it

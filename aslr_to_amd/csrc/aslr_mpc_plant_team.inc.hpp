@@ -1,0 +1,284 @@
+// aslr_mpc_plant_team.inc.hpp -- the plant phase of a receding-horizon run on a mismatched plant for the larger chain
+// (7-DoF SEA / VSA): aslr_mpc_run_plant_all, include/aslr_to_amd_mpc_plant_all.h, DESIGN.md 4.18.
+//
+//   mpc_plant_team_kernel   A TEAM OF 8 LANES PER TRAJECTORY, with the lane roles of policy_rollout_team_kernel
+//                           (aslr_policy_team.inc.hpp): lane c < NJ owns row c of the control law (rows c and NJ + c for
+//                           VSA), joint c's rotation, column c of M and of M^-1 and entry c of the Euler step; lane NJ owns
+//                           the nonlinear effects.  The definition is mpc_plant_kernel's (aslr_mpc_plant.inc.hpp): `hold`
+//                           knots of the plan in XS / US / KGAIN applied to the trajectory's own plant.  What differs from
+//                           the policy kernel:
+//     - there is ONE plant per trajectory, so the eight teams of a wave are eight trajectories and share nothing: no
+//       per-wave stage.  A block is one wave; the grid is over ceil(B / 8) waves;
+//     - every team reads [K_j | xs_j | us_j] of ITS trajectory straight from KGAIN / XS / US, one knot ahead: lane c its
+//       row(s) of K_j as 16-byte pieces into registers, entries 4c .. 4c + 3 of xs_j (to the team's LDS at the top of the
+//       next knot), its own entries of us_j (they stay in registers: the lane that reads them is the lane that owns the
+//       row), of the reference placement and of the disturbance;
+//     - every applied knot is node 0's action model (the running knots share one model: aslr_mpc_run's refusals), so the
+//       model rows, dt and the box are read once, before the loop;
+//     - knot 0 forms no feedback term: x IS XS[0], and KGAIN[0] never enters the arithmetic (it may hold Inf or NaN);
+//     - the sums of a run continue over its control steps in place (pa.first), there is no terminal cost;
+//     - it writes nothing but the caller's buffers.
+#pragma once
+#include "aslr_forward_team.inc.hpp"
+
+namespace aslr {
+
+template <int NJ, int DAM>
+__global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits lim, MpcPlantArgs pa) {
+  using C = FwdTeam<NJ, DAM>;
+  constexpr int NX = C::NX, NU = C::NU;
+  constexpr bool VSA = C::VSA;
+  constexpr int TPB = 8; // teams (trajectories) per block = per wave
+  // per team (doubles): FwdTeam's arrays, then xs_j and the reference placement of the knot
+  constexpr int tXr = C::TEAM_LDS, tFr = tXr + NX, TEAM = tFr + 12;
+  static_assert(NX % 4 == 0 && NX / 4 == NJ, "lane c < NJ moves entries 4c .. 4c + 3 of a state row");
+  __shared__ double sm[TPB * TEAM];
+  const int lane = threadIdx.x, team = lane >> 3, c = lane & 7;
+  const int B = a.B, hold = pa.hold;
+  // teams past B run on a clamped index (the arithmetic of a trajectory is the same instruction stream wherever it sits);
+  // only their stores are guarded
+  const int bq = blockIdx.x * TPB + team, b = bq < B ? bq : B - 1;
+  const bool on = bq < B;
+  double *tm_ = sm + team * TEAM;
+  double *xT = tm_ + C::tX, *uT = tm_ + C::tU, *tcL = tm_ + C::tTc, *tmL = tm_ + C::tTm, *RL = tm_ + C::tR,
+         *ML = tm_ + C::tM, *MiL = tm_ + C::tMi, *xrT = tm_ + tXr, *frT = tm_ + tFr;
+  const bool jl = c < NJ; // this lane owns joint / row cj
+  const int cj = jl ? c : NJ - 1;
+  const DevDesc &D = *a.desc;
+  const aslr_chain_t &ch = D.chain;
+  const chain_cp chc = chain_const(&D.chain);
+  const unsigned long long team_bits = 0xffull << (team * 8);
+
+  // joint placements and axes: constants of the chain, staged once in LDS (rollout_team_kernel says why)
+  __shared__ double jtab[8][12];
+  if (lane < NJ) {
+    ASLR_UNROLL for (int k = 0; k < 9; ++k) jtab[lane][k] = ch.joint_R[lane][k];
+    ASLR_UNROLL for (int k = 0; k < 3; ++k) jtab[lane][9 + k] = ch.axis[lane][k];
+  }
+
+  // ---- the model of every applied knot, and the plant of this team, entry cj: the caller's arrays [nj][B] where given,
+  // else the trajectory's row of the parameter table where one is set, else the row of the model ----
+  const int mi = node_model_at(a, 0);
+  const DevModel &dm = D.models[mi];
+  const bool table = pa.table != 0, use_k = pa.plant_stiffness || table, use_b = pa.plant_motor_inertia || table;
+  double k_cj = 0.0, b_cj = 0.0, lb_c = 0.0, ub_c = 0.0, lb_s = 0.0, ub_s = 0.0; // (lb_s / ub_s: the stiffness row, VSA)
+  if (table) {
+    const double *tp = traj_params_at(D, b);
+    k_cj = tp[(size_t)cj * B];
+    b_cj = tp[(size_t)(NJ + cj) * B];
+    lb_c = tp[(size_t)(2 * NJ + cj) * B];
+    ub_c = tp[(size_t)(2 * NJ + NU + cj) * B];
+    if (VSA) { lb_s = tp[(size_t)(3 * NJ + cj) * B]; ub_s = tp[(size_t)(3 * NJ + NU + cj) * B]; }
+  } else {
+    lb_c = lim.lb[mi][cj];
+    ub_c = lim.ub[mi][cj];
+    if (VSA) { lb_s = lim.lb[mi][NJ + cj]; ub_s = lim.ub[mi][NJ + cj]; }
+  }
+  if (pa.plant_stiffness) k_cj = pa.plant_stiffness[(size_t)cj * B + b];
+  if (pa.plant_motor_inertia) b_cj = 1.0 / pa.plant_motor_inertia[(size_t)cj * B + b];
+  double Krow[NJ], Srow[NJ], Brow[NJ];
+  ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
+    Krow[j] = 0.0; Srow[j] = 0.0;
+    if (!VSA) {
+      // (pa.diagonal is the host's fact: a plant array or a table, both of which need diagonal models)
+      Krow[j] = pa.diagonal ? ((j == cj) ? (use_k ? k_cj : dm.m.K[cj * NJ + cj]) : 0.0) : dm.m.K[cj * NJ + j];
+      Srow[j] = dm.m.S[cj * NU + j];
+    }
+    Brow[j] = pa.diagonal ? ((j == cj) ? (use_b ? b_cj : dm.Binv[cj * NJ + cj]) : 0.0) : dm.Binv[cj * NJ + j];
+  }
+  const double dt = dm.m.dt;
+  const bool clamp = pa.clamp && lim.has[mi];
+
+  // XS[0] into the team's state: where the solve started, and the plant is now
+  if (jl) {
+    const double *x0 = a.xs + (size_t)b * NX + 4 * c;
+    const double2 v0 = *reinterpret_cast<const double2 *>(x0), v1 = *reinterpret_cast<const double2 *>(x0 + 2);
+    xT[4 * c] = v0.x; xT[4 * c + 1] = v0.y; xT[4 * c + 2] = v1.x; xT[4 * c + 3] = v1.y;
+  }
+
+  // ---- what is read one knot ahead: this lane's row(s) of K_j, entries 4c .. 4c + 3 of xs_j, entries cj (and NJ + cj) of
+  // us_j, entries c and 8 + c of the reference placement of row min(row0 + j, last), and entries cj, NJ + cj, 2 NJ + cj,
+  // 3 NJ + cj of the disturbance ----
+  double Kn[NX], Ksn[VSA ? NX : 2], xn[4] = {0.0, 0.0, 0.0, 0.0}, un = 0.0, usn = 0.0, fn[2] = {0.0, 0.0}, wn[4] = {0.0, 0.0, 0.0, 0.0};
+  ASLR_UNROLL for (int i = 0; i < NX; ++i) Kn[i] = 0.0;
+  ASLR_UNROLL for (int i = 0; i < (VSA ? NX : 2); ++i) Ksn[i] = 0.0;
+  const double *wsrc = pa.disturbance ? pa.disturbance + (size_t)b * NX + cj : nullptr; // knot j at + j B NX
+  auto prefetch = [&](int j) {
+    const double *us = a.us + ((size_t)j * B + b) * NU;
+    un = us[cj];
+    if constexpr (VSA) usn = us[NJ + cj];
+    if (a.frame_ref) {
+      const double *fr = a.frame_ref + 12 * ((size_t)min(a.ref_row0 + j, a.ref_last) * B + b); // (the applied knot's row of the path)
+      fn[0] = fr[c];
+      fn[1] = fr[8 + (c & 3)];
+    }
+    if (wsrc) { ASLR_UNROLL for (int k = 0; k < 4; ++k) wn[k] = wsrc[(size_t)j * B * NX + k * NJ]; }
+  };
+  // (not for knot 0: x IS xs[0], no feedback term is formed -- x - xs would be +0, but K may hold Inf or NaN)
+  auto prefetch_gains = [&](int j) {
+    {
+      const double *K = a.kgain + ((size_t)j * B + b) * NU * NX, *xr = a.xs + ((size_t)j * B + b) * NX + 4 * cj;
+      ASLR_UNROLL for (int p = 0; p < NX / 2; ++p) {
+        const double2 v = *reinterpret_cast<const double2 *>(K + cj * NX + 2 * p);
+        Kn[2 * p] = v.x; Kn[2 * p + 1] = v.y;
+      }
+      if constexpr (VSA) {
+        ASLR_UNROLL for (int p = 0; p < NX / 2; ++p) {
+          const double2 v = *reinterpret_cast<const double2 *>(K + (NJ + cj) * NX + 2 * p);
+          Ksn[2 * p] = v.x; Ksn[2 * p + 1] = v.y;
+        }
+      }
+      const double2 v0 = *reinterpret_cast<const double2 *>(xr), v1 = *reinterpret_cast<const double2 *>(xr + 2);
+      xn[0] = v0.x; xn[1] = v0.y; xn[2] = v1.x; xn[3] = v1.y;
+    }
+  };
+  double *x_o = pa.x_rec + (size_t)b * NX + 4 * cj, *u_o = pa.u_rec + (size_t)b * NU; // knot j at + j B NX / + j B NU
+  auto store_x = [&](int j) { // the team's state as row j of this step's records, 4 contiguous entries per lane
+    if (on && jl) {
+      double *o = x_o + (size_t)j * B * NX;
+      *reinterpret_cast<double2 *>(o) = make_double2(xT[4 * c], xT[4 * c + 1]);
+      *reinterpret_cast<double2 *>(o + 2) = make_double2(xT[4 * c + 2], xT[4 * c + 3]);
+    }
+  };
+  const typename Chain3D<NJ>::Consts cc(D, true);
+  ModelRegs<NJ, NU> mr; // (the cost stack reads none of it)
+
+  // the sums of a run continue over its control steps: step 0 starts them, a later step picks up what the one before left
+  double J = 0.0;
+  int failed = -1;
+  if (!pa.first) {
+    if (pa.closed_cost) J = pa.closed_cost[b];
+    if (pa.failed_knot) failed = pa.failed_knot[b];
+  }
+  bool failed_here = false;
+  prefetch(0);
+  for (int j = 0; j < hold; ++j) {
+    wave_sync(); // the previous knot's readers of xs_j and the placement are done, its state is written (knot 0: the joint table, XS[0])
+    if (jl && j > 0) { ASLR_UNROLL for (int k = 0; k < 4; ++k) xrT[4 * c + k] = xn[k]; }
+    frT[c] = fn[0];
+    if (c < 4) frT[8 + c] = fn[1];
+    wave_sync();
+    // ---- control law, row cj: u = us_j - K_j (x - xs_j) from knot 1 on, box clamp when asked for ----
+    double u_c = un, u_s = usn; // this lane's entries of the applied control (u_s: the stiffness command, VSA)
+    if (j > 0) {
+      ASLR_UNROLL for (int jx = 0; jx < NX; ++jx) u_c -= Kn[jx] * (xT[jx] - xrT[jx]);
+      if constexpr (VSA) { ASLR_UNROLL for (int jx = 0; jx < NX; ++jx) u_s -= Ksn[jx] * (xT[jx] - xrT[jx]); }
+    }
+    if (clamp) {
+      u_c = fmin(fmax(u_c, lb_c), ub_c);
+      if constexpr (VSA) u_s = fmin(fmax(u_s, lb_s), ub_s);
+    }
+    if (jl) {
+      uT[c] = u_c;
+      if constexpr (VSA) uT[NJ + c] = u_s;
+    }
+    wave_sync();
+    // ---- running cost of the applied knot: the team's state and the applied control, BEFORE the loads of the next knot
+    // are issued (the cost stack reads its terms from global memory, and behind those loads its waits would be waits for
+    // the prefetch) ----
+    {
+      double x[NX], u[NU], xnext[NX], cst = 0.0;
+      ASLR_UNROLL for (int i = 0; i < NX; ++i) x[i] = xT[i];
+      ASLR_UNROLL for (int i = 0; i < NU; ++i) u[i] = uT[i];
+      knot_eval<NJ, DAM, kEvalCost, Chain3D<NJ>>(cc, mr, dm, a.frame_ref ? frT : nullptr, x, u, xnext, cst, nullptr);
+      J += cst; // (applied control, knot order)
+    }
+    double w[4];
+    ASLR_UNROLL for (int k = 0; k < 4; ++k) w[k] = wn[k];
+    // in flight while the dynamics of knot j compute.  Unconditional, so that these registers are dead from the top of the
+    // knot to here, across the cost: the last knot reads its own row again, which nothing uses
+    const int jn = min(j + 1, hold - 1);
+    prefetch(jn);
+    // (the records of a knot go out after the loads of the next one)
+    store_x(j);
+    if (on && jl) {
+      u_o[(size_t)j * B * NU + c] = u_c;
+      if constexpr (VSA) u_o[(size_t)j * B * NU + NJ + c] = u_s;
+    }
+    // ---- rotation of joint cj ----
+    if (jl) {
+      const M3 R = mul(m3(jtab[cj]), axis_angle(v3(jtab[cj] + 9), xT[cj]));
+      ASLR_UNROLL for (int k = 0; k < 9; ++k) RL[9 * c + k] = R.a[k];
+    }
+    wave_sync();
+    // ---- coupling and motor torques, entry cj ----
+    if (jl) {
+      double sc_ = 0.0, s2 = 0.0;
+      if constexpr (VSA) { // K = diag(stiffness commands), tau_m = the torque commands
+        ASLR_UNROLL for (int i = 0; i < NJ; ++i) sc_ += (i == c ? uT[NJ + c] : 0.0) * (xT[i] - xT[NJ + i]);
+        s2 = uT[c];
+      } else {
+        ASLR_UNROLL for (int i = 0; i < NJ; ++i) { sc_ += Krow[i] * (xT[i] - xT[NJ + i]); s2 += Srow[i] * uT[i]; }
+      }
+      tcL[c] = sc_;
+      tmL[c] = s2;
+    }
+    // ---- one RNEA per lane: column c of M (lanes c < NJ), nonlinear effects (lane NJ) ----
+    if (c <= NJ) {
+      double vv[NJ], aa[NJ], tau[NJ];
+      const bool nl = c == NJ;
+      ASLR_UNROLL for (int i = 0; i < NJ; ++i) { vv[i] = nl ? xT[2 * NJ + i] : 0.0; aa[i] = (!nl && i == c) ? 1.0 : 0.0; }
+      const V3 g = v3(chc->gravity);
+      const V3 grav = nl ? g : V3{0.0, 0.0, 0.0};
+      rnea_lds<NJ>(chc, RL, vv, aa, grav, tau);
+      ASLR_UNROLL for (int i = 0; i < NJ; ++i) ML[8 * c + i] = tau[i];
+    }
+    wave_sync();
+    // the row(s) of K and the entries of xs of the knot ahead: 28 / 56 doubles per lane, issued behind the RNEA -- the
+    // register peak of the knot, where they would be spilled to the private segment -- and in flight over the inverse, the
+    // accelerations and the Euler step
+    prefetch_gains(jn);
+    // ---- column cj of M^-1 (M symmetrised like Chain3D::mass) ----
+    {
+      double Ms[NJ][NJ], e[NJ];
+      ASLR_UNROLL for (int i = 0; i < NJ; ++i)
+        ASLR_UNROLL for (int k = 0; k <= i; ++k) {
+          Ms[i][k] = (i == k) ? ML[8 * k + i] : 0.5 * (ML[8 * k + i] + ML[8 * i + k]);
+          Ms[k][i] = Ms[i][k];
+        }
+      spd_inverse_col<NJ>(Ms, cj, e);
+      if (jl) { ASLR_UNROLL for (int i = 0; i < NJ; ++i) MiL[8 * c + i] = e[i]; }
+    }
+    wave_sync();
+    // ---- accelerations and semi-implicit Euler, entries cj of q_l, q_m, v_l, v_m ----
+    double al = 0.0, am = 0.0;
+    ASLR_UNROLL for (int i = 0; i < NJ; ++i) {
+      al += MiL[8 * i + cj] * (-ML[8 * NJ + i] - tcL[i]);
+      am += Brow[i] * (tmL[i] + tcL[i]);
+    }
+    const double ql = xT[cj], qm = xT[NJ + cj], vl = xT[2 * NJ + cj], vm = xT[3 * NJ + cj];
+    const double nql = ql + (vl * dt + al * dt * dt), nvl = vl + al * dt;
+    const double nqm = qm + (vm * dt + am * dt * dt), nvm = vm + am * dt;
+    const double nxt[4] = {nql, nvl, nqm, nvm}; // this lane's entries of xnext: |xnext|_inf test, entry by entry
+    const bool bad = jl && inf_norm_bad<4>(fabs(nql) + fabs(nvl) + fabs(nqm) + fabs(nvm), nxt);
+    if (__ballot(bad) & team_bits) { // NaN / Inf / |xnext|_inf >= 1e30, as the solver's rollout
+      failed_here = true;
+      if (failed < 0) failed = pa.k0 + j;
+    }
+    wave_sync(); // every lane of the team has read the old state
+    if (jl) {
+      if (wsrc) { xT[c] = nql + w[0]; xT[NJ + c] = nqm + w[1]; xT[2 * NJ + c] = nvl + w[2]; xT[3 * NJ + c] = nvm + w[3]; }
+      else { xT[c] = nql; xT[NJ + c] = nqm; xT[2 * NJ + c] = nvl; xT[3 * NJ + c] = nvm; }
+    }
+  }
+  wave_sync(); // the state behind the last applied knot is written
+  if (!on) return;
+  // x+: the row behind the last record (the next step's first record, or x_closed[N]); mpc_advance_hold_kernel reads it there
+  store_x(hold);
+  if (c == 0) {
+    if (pa.closed_cost) pa.closed_cost[b] = failed_here ? NAN : J; // (NaN stays NaN through the sums of the later steps)
+    if (pa.failed_knot) pa.failed_knot[b] = failed;
+  }
+}
+
+// the nx = 28 sizes: one block = one wave = 8 teams = 8 trajectories
+int launch_mpc_plant_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st) {
+  const dim3 grid((k.B + 7) / 8), block(64);
+  if (nj == 7 && dam == ASLR_DAM_SEA) hipLaunchKernelGGL((mpc_plant_team_kernel<7, ASLR_DAM_SEA>), grid, block, 0, st, k, lim, pa);
+  else if (nj == 7 && dam == ASLR_DAM_VSA) hipLaunchKernelGGL((mpc_plant_team_kernel<7, ASLR_DAM_VSA>), grid, block, 0, st, k, lim, pa);
+  else return fail(ASLR_E_INVALID, "aslr_mpc_run_plant_all: no team plant kernel for nj = %d", nj);
+  HIP_TRY(hipGetLastError());
+  return ASLR_OK;
+}
+
+} // namespace aslr

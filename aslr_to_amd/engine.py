@@ -627,7 +627,8 @@ class Engine(object):
 
     def mpc_run_plant(self, sp, n_steps, first_maxiter, iters_per_step, hold=1, plant_stiffness=None, plant_motor_inertia=None,
                       disturbance=None, clamp=False, closed_cost=True):
-        """mpc_run on a plant of its own (aslr_mpc_run_plant, include/aslr_to_amd_mpc_plant.h): every control step solves
+        """mpc_run on a plant of its own (aslr_mpc_run_plant, include/aslr_to_amd_mpc_plant.h; on the 7-joint arms
+        aslr_mpc_run_plant_all, include/aslr_to_amd_mpc_plant_all.h): every control step solves
         as mpc_run does, then applies `hold` knots of the plan to the plant -- the first control as it is, the later ones
         with the Riccati feedback u = us_j - K_j (x - xs_j) -- and shifts the plan by hold.  Batch-major arrays or tensors,
         each optional: plant_stiffness, plant_motor_inertia [B, nj] (diagonals of the plant's K and B; None: the
@@ -665,8 +666,9 @@ class Engine(object):
         mpc.disturbance = dist.data_ptr() if dist is not None else None
         mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = xc.data_ptr(), uc.data_ptr(), sf.data_ptr(), si.data_ptr()
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._call("aslr_mpc_run_plant", C.byref(sp), C.byref(mpc), h, ptr(pk), ptr(pb), 1 if clamp else 0, ptr(cc), ptr(fk),
-                   self._stream())
+        # (2 joints: the entry point that has always served them; every other size: the one that serves all sizes)
+        self._call("aslr_mpc_run_plant" if nj == 2 else "aslr_mpc_run_plant_all", C.byref(sp), C.byref(mpc), h, ptr(pk), ptr(pb),
+                   1 if clamp else 0, ptr(cc), ptr(fk), self._stream())
         torch.cuda.synchronize(self.device)  # (the time-major copies of the inputs die on return)
         return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
                          status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t(),

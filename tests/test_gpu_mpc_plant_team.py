@@ -1,0 +1,476 @@
+"""aslr_mpc_run_plant_all on the GPU (include/aslr_to_amd_mpc_plant_all.h; mpc_plant_team_kernel,
+csrc/aslr_mpc_plant_team.inc.hpp) against tests/_mpc_plant.py, on the 7-joint arms.
+
+As tests/test_gpu_mpc_plant.py: the oracle's solve returns no gains, so the call is held to its definition by induction --
+ONE control step against the definition (a twin handle's plain solve gives the plan and the gains; the plant phase is a numpy
+loop over the oracle's knot), then the loop against itself, bit for bit; at hold = 1, where no gain is read, the whole loop
+against the oracle's.  Kernel outputs are held to 1e-9 relative, max |a - b| / (1 + |b|); tests/test_mpc_plant_team_host.py
+shows that the inputs are conditioned for it.  Shapes: tests/_mpc_plant_team.py.  x_closed and u_closed sit in buffers of the
+test's own, followed by guard words that must survive."""
+import copy
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import _gpu_case as gc
+import _mpc_plant as mp
+import _mpc_plant_team as mt
+import _parity
+import _policy as pol
+import _policy_team as pt
+import _traj_oracle
+import test_mpc_host as H
+from aslr_to_amd import _abi, crocoddyl, scenarios
+
+pytestmark = pytest.mark.gpu
+
+REGIONS = (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_F, _abi.R_TRAJ_I, _abi.R_X0)
+GUARD, SENTINEL = 64, -7.25
+KEYS = ("x", "u", "stat_f", "stat_i", "cost", "failed")
+NAME = mt.NAME
+
+
+def _raw(e, sp, n, first, per, hold=1, pk=None, pb=None, dist=None, clamp=False, cost=True, failed=True, expect=_abi.OK,
+         name=NAME):
+    """the entry point `name`.  pk, pb: batch-major [B, nj] or None (NULL); dist: time-major [N, B, nx] or None; cost /
+    failed: whether closed_cost / failed_knot are given.  -> dict of time-major numpy arrays: x [N+1, B, nx], u [N, B, nu],
+    stat_f [n, 4, B], stat_i [n, 2, B], cost [B], failed [B] (None where not given); the guards behind x and u must be
+    untouched.  expect != OK: -> the message of the refusal, and nothing was written."""
+    import torch
+    N = max(n, 0) * max(hold, 0)
+    dev = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=e.device)
+    tk, tb, td = dev(None if pk is None else np.transpose(pk)), dev(None if pb is None else np.transpose(pb)), dev(dist)
+    nxw, nuw = (N + 1) * e.B * e.nx, N * e.B * e.nu
+    x = torch.full((nxw + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
+    u = torch.full((nuw + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
+    sf = torch.full((max(n, 1), 4, e.B), SENTINEL, dtype=torch.float64, device=e.device)
+    si = torch.full((max(n, 1), 2, e.B), -7, dtype=torch.int32, device=e.device)
+    cc = torch.full((e.B,), SENTINEL, dtype=torch.float64, device=e.device) if cost else None
+    fk = torch.full((e.B,), -7, dtype=torch.int32, device=e.device) if failed else None
+    mpc = _abi.Mpc()
+    mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, first, per
+    mpc.disturbance = td.data_ptr() if td is not None else None
+    mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = x.data_ptr(), u.data_ptr(), sf.data_ptr(), si.data_ptr()
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+    with torch.cuda.device(e.device):
+        rc = getattr(e.lib, name)(e.handle, C.byref(sp), C.byref(mpc), hold, ptr(tk), ptr(tb), 1 if clamp else 0, ptr(cc), ptr(fk),
+                                  e._stream())
+    gc.sync()
+    if expect != _abi.OK:
+        assert rc == expect, rc
+        for t, s in ((x, SENTINEL), (u, SENTINEL), (sf, SENTINEL), (si, -7), (cc, SENTINEL), (fk, -7)):
+            assert t is None or (t == s).all(), "a refused call wrote to an output"
+        return e.lib.aslr_last_error().decode()
+    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
+    xa, ua = gc.to_np(x), gc.to_np(u)
+    assert (xa[nxw:] == SENTINEL).all() and (ua[nuw:] == SENTINEL).all(), "a guard was overwritten"
+    return dict(x=xa[:nxw].reshape(N + 1, e.B, e.nx), u=ua[:nuw].reshape(N, e.B, e.nu), stat_f=gc.to_np(sf), stat_i=gc.to_np(si),
+                cost=None if cc is None else gc.to_np(cc), failed=None if fk is None else gc.to_np(fk))
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+def _same(a, b, what):
+    np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=what)
+
+
+def _same_runs(a, b, what, keys=KEYS):
+    for k in keys:
+        if a[k] is not None or b[k] is not None:
+            _same(a[k], b[k], "%s: %s" % (what, k))
+
+
+def _fresh(low, nsub=1):
+    e = gc.engine(low)
+    if nsub > 1:
+        e.set_subshards(nsub)
+    e.set_candidate(None, None)
+    return e
+
+
+def _arm(name, B, T):
+    sc = scenarios.SCENARIOS[name](B=B, T=T, seed=mt.SCENARIO_SEED)
+    low = scenarios.lower(sc)
+    sp = scenarios.solver_params(sc, solver="SolverBoxDDP" if low.dam == _abi.DAM_VSA else "SolverFDDP", maxiter=3)
+    return sc, low, sp
+
+
+def _plants_and_noise(low, N):
+    pk, pb = mp.plants(low, seed=mt.PLANT_SEED, rng_range=mt.PLANT_RANGE)
+    return pk, pb, np.random.default_rng(mt.DIST_SEED).uniform(-mt.DIST, mt.DIST, (N, low.B, low.nx))
+
+
+# ---- 1. one control step is the definition ----
+@pytest.mark.parametrize("key", sorted(mt.ONE_STEP))
+def test_one_control_step_is_the_definition(oracle, key):
+    """n_steps = 1, three SolverFDDP / SolverBoxDDP iterations from the empty candidate, plants within +-30 %, disturbance
+    U(-1e-3, 1e-3): the records, the cost and failed_knot against mp.plant_phase on the twin's XS / US / KGAIN within 1e-9;
+    the shifted plan, X0 and the statistics exactly; KFF, GAPS, VXXF zero.  B = 3 leaves five idle teams, B = 9 crosses a
+    wave (= a block); hold = 4 = T is the shift whose every source is the clamped last row; vsa_box runs T = 6, hold = 6
+    (tests/_mpc_plant_team.py says why)."""
+    c = mt.one_step(key)
+    low, sp, hold, clamp, pk, pb, dist = (c[k] for k in ("low", "sp", "hold", "clamp", "pk", "pb", "dist"))
+    e, twin = _fresh(low), _fresh(low)
+    row_before = e.reference_row
+    got = _raw(e, sp, 1, 3, 3, hold, pk, pb, dist, clamp)
+    twin.solve(sp, poll_every=0)
+    gc.sync()
+    X, U, K = (gc.to_np(twin.region(r)) for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN))
+    assert (gc.to_np(twin.traj_i(_abi.TI_ITER)) >= 1).any() and (hold == 1 or np.abs(K[1:hold]).max() > 1e-3)
+    want = mt.reference(oracle, c, X, U[..., :low.nu], K[..., :low.nu, :])
+    assert (want["failed"] == -1).all()
+    errs = dict(x=pol.relerr(got["x"], want["x"]), u=pol.relerr(got["u"][..., :low.nu], want["u"]), cost=pol.relerr(got["cost"], want["cost"]))
+    print("%s: relerr %s" % (key, {k: "%.2e" % v for k, v in errs.items()}))
+    assert max(errs.values()) < 1e-9, errs
+    np.testing.assert_array_equal(got["failed"], want["failed"])
+    if hold > 1:   # the plant and the disturbance moved the loop off the plan, so the feedback term was at work
+        assert np.abs(got["x"][1:hold] - X[1:hold]).max() > 1e-6
+    if clamp:
+        assert want["bound"].any() and not want["bound"].all(), "the narrowed box must move some control of the reference, not on every trajectory"
+        free = mt.reference(oracle, c, X, U[..., :low.nu], K[..., :low.nu, :], clamp=False)
+        assert pol.relerr(free["u"], want["u"]) > 1e-3   # ... and the clamp is what the kernel applied
+    if c["table"] and c["arrays"]:   # the plants given on top of the table are what the kernel used, not the table's rows
+        table = mt.reference(oracle, c, X, U[..., :low.nu], K[..., :low.nu, :], plants=False)
+        assert pol.relerr(table["x"], want["x"]) > 1e-6
+    _same(got["x"][0], X[0], "x_closed[0] is XS[0]")
+    if not clamp:
+        _same(got["u"][0], U[0], "u_closed[0] is US[0]")
+    # the shift, exactly: rows of the twin's plan, the last one repeated; x+ in xs[0], X0 and x_closed[N]
+    xs_want, us_want = mp.shifted(X, U, hold, got["x"][hold])
+    XS, US = gc.to_np(e.region(_abi.R_XS)), gc.to_np(e.region(_abi.R_US))
+    _same(XS[1:], xs_want[1:], "XS after the shift, away from row 0")
+    _same(US, us_want, "US after the shift")
+    _same(XS[0], got["x"][hold], "xs[0] = x_closed[N]")
+    _same(gc.to_np(e.region(_abi.R_X0)), got["x"][hold], "X0 = x_closed[N]")
+    for rid in (_abi.R_KFF, _abi.R_GAPS, _abi.R_VXXF):
+        assert not gc.to_np(e.region(rid)).view(np.int64).any(), "region %d is not all zero" % rid
+    tf, ti = gc.to_np(twin.region(_abi.R_TRAJ_F)), gc.to_np(twin.region(_abi.R_TRAJ_I))
+    for i, row in enumerate((_abi.TF_COST, _abi.TF_STOP, _abi.TF_XREG, _abi.TF_STEP)):
+        _same(got["stat_f"][0, i], tf[row], "stat_f[%d]" % i)
+    _same(got["stat_i"][0, 0], ti[_abi.TI_ITER], "iterations")
+    _same(got["stat_i"][0, 1], ti[_abi.TI_STATUS], "status")
+    if getattr(low, "ref_path", None) is not None:
+        assert e.reference_row == row_before + hold
+
+
+# ---- 2. the loop is its own step, bit for bit ----
+@pytest.mark.parametrize("name", ["talos_arm_sea", "talos_arm_vsa"])
+def test_the_loop_is_its_own_step_bit_for_bit(name):
+    """one call of three control steps against three calls of one, hold = 2, B = 9, T = 6"""
+    n, hold, first, per = 3, 2, 3, 2
+    sc, low, sp = _arm(name, 9, 6)
+    pk, pb, dist = _plants_and_noise(low, n * hold)
+    dev, twin = _fresh(low), _fresh(low)
+    one = _raw(dev, sp, n, first, per, hold, pk, pb, dist)
+    parts = [_raw(twin, sp, 1, first if s == 0 else per, per, hold, pk, pb, dist[s * hold:(s + 1) * hold]) for s in range(n)]
+    for s, p in enumerate(parts):
+        _same(one["x"][s * hold:(s + 1) * hold + 1], p["x"], "x_closed of step %d" % s)
+        _same(one["u"][s * hold:(s + 1) * hold], p["u"], "u_closed of step %d" % s)
+        _same(one["stat_f"][s], p["stat_f"][0], "stat_f of step %d" % s)
+        _same(one["stat_i"][s], p["stat_i"][0], "stat_i of step %d" % s)
+        assert (p["failed"] == -1).all()
+    assert (one["failed"] == -1).all()
+    for rid in REGIONS:
+        gc.same_bits(dev.region(rid), twin.region(rid), "region %d" % rid)
+    total = np.zeros(low.B)
+    for p in parts:
+        total = total + p["cost"]
+    err = np.abs(one["cost"] - total).max() / np.abs(total).max()
+    print("%s: closed cost against the in-order sum of the three steps: %.2e relative" % (name, err))
+    assert (np.abs(one["cost"] - total) <= 1e-12 * np.abs(total)).all()
+    assert np.abs(one["x"][1:] - one["x"][:-1]).max() > 0.0           # the states move
+    assert (one["stat_i"][:, 0].max(axis=1) >= 1).all()                # every step iterates on some trajectory
+
+
+# ---- 3. the oracle loop at hold = 1 on a mismatched plant ----
+@pytest.mark.parametrize("row", mt.ROWS, ids=mt.ROW_IDS)
+def test_hold_one_matches_the_oracle_loop_on_a_mismatched_plant(oracle, row):
+    """the rows tests/test_mpc_plant_team_host.py holds to the stability criterion; the bounds of
+    test_gpu_mpc_plant's test of the same name: iteration counts and status words exactly, states, controls and the final
+    plan within 1e-6 of the trajectory's scale, step costs and the closed cost within 1e-4 of max(1, |cost|)"""
+    ref, pk, pb = mp.loop_reference(oracle, row, H)
+    sc, sp, dist = H.parity_case(*row)
+    e = _fresh(scenarios.lower(sc))
+    r = e.mpc_run_plant(sp, H.N_STEPS, H.FIRST_MAXITER, H.ITERS_PER_STEP, 1, pk, pb, np.ascontiguousarray(dist.transpose(1, 0, 2)))
+    xc, uc = gc.to_np(r.xs_closed).transpose(1, 0, 2), gc.to_np(e.pad_u(r.us_closed)).transpose(1, 0, 2)
+    for s in range(H.N_STEPS):
+        np.testing.assert_array_equal(gc.to_np(r.iters)[:, s], ref["iters"][s], err_msg="iterations of step %d" % s)
+        _parity.assert_status_words_match(gc.to_np(r.status)[:, s], ref["status"][s])
+    scale = np.maximum(1.0, np.maximum(np.abs(ref["x_closed"]).max(axis=(0, 2)), np.abs(ref["u_closed"]).max(axis=(0, 2))))
+    dx = (np.abs(xc - ref["x_closed"]).max(axis=(0, 2)) / scale).max()
+    du = (np.abs(uc - ref["u_closed"]).max(axis=(0, 2)) / scale).max()
+    dc = (np.abs(gc.to_np(r.cost).T - ref["cost"]) / np.maximum(1.0, np.abs(ref["cost"]))).max()
+    dp = (np.abs(gc.to_np(e.region(_abi.R_XS)) - ref["xs"]).max(axis=(0, 2)) / scale).max()
+    dj = (np.abs(gc.to_np(r.closed_cost) - ref["closed_cost"]) / np.maximum(1.0, np.abs(ref["closed_cost"]))).max()
+    print("%s %s: max rel |dx| %.2e |du| %.2e |dcost| %.2e, final plan %.2e, closed cost %.2e" % (row[0], row[1], dx, du, dc, dp, dj))
+    assert dx < 1e-6 and du < 1e-6 and dp < 1e-6, (dx, du, dp)
+    assert dc < 1e-4 and dj < 1e-4, (dc, dj)
+    assert (gc.to_np(r.failed_knot) == -1).all()
+
+
+# ---- 4. delegation and neutrality ----
+def test_defaults_are_aslr_mpc_run_bit_for_bit():
+    """hold = 1 and nothing asked of the plant on a 7-joint handle: records, statistics and the regions of aslr_mpc_run"""
+    sc, low, sp = _arm("talos_arm_sea", 9, 6)
+    n, first, per = 3, 3, 2
+    dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n, low.B, low.nx))
+    a, b = _fresh(low), _fresh(low)
+    got = _raw(a, sp, n, first, per, 1, None, None, dist, False, cost=False, failed=False)
+    r = b.mpc_run(sp, n, first, per, np.ascontiguousarray(dist.transpose(1, 0, 2)))
+    gc.sync()
+    _same(got["x"], gc.to_np(r.xs_closed).transpose(1, 0, 2), "x_closed")
+    _same(got["u"], gc.to_np(b.pad_u(r.us_closed)).transpose(1, 0, 2), "u_closed")
+    for i, k in enumerate(("cost", "stop", "x_reg", "step")):
+        _same(got["stat_f"][:, i], gc.to_np(getattr(r, k)).T, k)
+    _same(got["stat_i"][:, 0], gc.to_np(r.iters).T, "iters")
+    _same(got["stat_i"][:, 1], gc.to_np(r.status).T, "status")
+    for rid in REGIONS:
+        gc.same_bits(a.region(rid), b.region(rid), "region %d" % rid)
+    assert int(r.iters[:, 0].min()) >= 1
+
+
+@pytest.mark.parametrize("name", ["talos_arm_sea", "talos_arm_vsa"])
+def test_the_nominal_plant_is_neutral_and_a_plant_off_is_not(name):
+    """ONE step with the trajectories' own K and B passed as plant arrays and the cost requested: x_closed[1] within 1e-11 of
+    the trajectory's scale of aslr_mpc_run's (the calc and the plant kernels need not share bits); with the plant 20 % off
+    it moves by more than 1e-6."""
+    sc, low, sp = _arm(name, 9, 6)
+    dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (1, low.B, low.nx))
+    nom = lambda f: np.array([pol.nominal_diag(low, b, f) for b in range(low.B)])
+    kn, bn = (nom("K") if low.dam == _abi.DAM_SEA else None), nom("B")
+    base = _fresh(low).mpc_run(sp, 1, 3, 2, np.ascontiguousarray(dist.transpose(1, 0, 2)))
+    want = gc.to_np(base.xs_closed).transpose(1, 0, 2)
+    got = _raw(_fresh(low), sp, 1, 3, 2, 1, kn, bn, dist)
+    scale = np.maximum(1.0, np.abs(want).max(axis=(0, 2)))
+    err = (np.abs(got["x"][1] - want[1]).max(axis=1) / scale).max()
+    print("%s: x_closed[1] with the nominal plant given against aslr_mpc_run: %.2e of scale" % (name, err))
+    assert err < 1e-11
+    _same(got["x"][0], want[0], "x_closed[0]")
+    assert np.isfinite(got["cost"]).all() and (got["failed"] == -1).all()
+    off = _raw(_fresh(low), sp, 1, 3, 2, 1, None if kn is None else 1.2 * kn, 1.2 * bn, dist)
+    assert np.abs(off["x"][1] - want[1]).max() > 1e-6
+
+
+# ---- 5. schedule and position independence ----
+def test_results_do_not_depend_on_subshards_or_batch():
+    """one and two sub-shards give the same bits (B = 65: the sub-shard boundary lies on a multiple of 64 trajectories);
+    trajectories 0..2 of a batch of 9 equal a batch of 3"""
+    n, hold, first, per = 2, 2, 3, 2
+    sc, low, sp = _arm("talos_arm_sea", 65, 4)
+    pk, pb, dist = _plants_and_noise(low, n * hold)
+    e1, e2 = _fresh(low), _fresh(low, 2)
+    r1, r2 = (_raw(e, sp, n, first, per, hold, pk, pb, dist) for e in (e1, e2))
+    _same_runs(r1, r2, "two sub-shards")
+    for rid in REGIONS:
+        gc.same_bits(e1.region(rid), e2.region(rid), "region %d with two sub-shards" % rid)
+    sc9, low9, _ = _arm("talos_arm_sea", 9, 4)
+    pk9, pb9, dist9 = _plants_and_noise(low9, n * hold)
+    e9 = _fresh(low9)
+    r9 = _raw(e9, sp, n, first, per, hold, pk9, pb9, dist9)
+    three = dict(sc9, x0=sc9["x0"][:3], frame_refs=sc9["frame_refs"][:3])
+    e3 = _fresh(scenarios.lower(three))
+    r3 = _raw(e3, sp, n, first, per, hold, pk9[:3], pb9[:3], dist9[:, :3])
+    cut = {k: (v[:3] if k in ("cost", "failed") else v[:, :3] if k in ("x", "u") else v[:, :, :3]) for k, v in r9.items()}
+    _same_runs(cut, r3, "trajectories 0..2 of 9 in a batch of 3")
+    for rid in (_abi.R_XS, _abi.R_US):
+        gc.same_bits(e9.region(rid)[:, :3], e3.region(rid), "region %d of the first three trajectories" % rid)
+    assert (r9["stat_i"][:, 0].max(axis=1) >= 1).all()
+
+
+# ---- 6. a trajectory fails alone ----
+@pytest.mark.parametrize("name", ["talos_arm_sea", "talos_arm_vsa"])
+def test_a_failing_trajectory_fails_alone_and_is_counted_in_applied_knots(name):
+    """n_steps = 2, hold = 2, B = 9 (trajectories 0..7 are the eight teams of one wave, trajectory 8 sits in the next).
+    Trajectory 4 has a plant motor inertia of 0: it fails at applied knot 0.  Trajectory 2 is pushed by 1e31 behind applied
+    knot 2, the first of the SECOND step: the next knot's plant state fails the solver's test, so failed_knot is 3 (the index
+    counts applied knots over the steps).  Both costs are NaN.  Every other trajectory -- the six wave mates of the failing
+    ones among them -- has, bit for bit, the outputs of the run without the failures."""
+    n, hold = 2, 2
+    sc, low, sp = _arm(name, 9, 4)
+    pk, pb, dist = _plants_and_noise(low, n * hold)
+    base = _raw(_fresh(low), sp, n, 3, 2, hold, pk, pb, dist)
+    assert (base["failed"] == -1).all() and np.isfinite(base["cost"]).all()
+    pushed, pb0 = np.array(dist), np.array(pb)
+    pushed[2, 2], pb0[4] = 1e31, 0.0
+    got = _raw(_fresh(low), sp, n, 3, 2, hold, pk, pb0, pushed)
+    np.testing.assert_array_equal(got["failed"], [-1, -1, 3, -1, 0, -1, -1, -1, -1])
+    assert np.isnan(got["cost"][[2, 4]]).all()
+    ok = [0, 1, 3, 5, 6, 7, 8]
+    for k in ("x", "u"):
+        _same(got[k][:, ok], base[k][:, ok], "%s of the other trajectories" % k)
+    for k in ("stat_f", "stat_i"):
+        _same(got[k][:, :, ok], base[k][:, :, ok], "%s of the other trajectories" % k)
+    _same(got["cost"][ok], base["cost"][ok], "closed cost of the other trajectories")
+    _same(got["x"][:3, 2], base["x"][:3, 2], "trajectory 2 before its push")   # (and up to its failure a trajectory is what it was)
+
+
+# ---- 7. against the other kernel ----
+@pytest.mark.parametrize("name", ["talos_arm_sea", "talos_arm_vsa"])
+def test_one_step_over_the_whole_horizon_is_the_policy_rollout(oracle, name):
+    """n_steps = 1, hold = T, a plant and no disturbance, against aslr_policy_rollout_all on a twin handle after the same
+    solve, with S = 1, the same plant and the trajectories kept: policy_rollout_team_kernel and mpc_plant_team_kernel are
+    independently written.  x_closed[0..T] against xs_closed and u_closed against us_closed within 1e-9; closed_cost is the
+    roll-out's cost minus the terminal node's (the oracle's knot on the roll-out's last state)."""
+    sc, low, sp = _arm(name, 9, 4)
+    B, T = low.B, low.T
+    pk, pb, _ = _plants_and_noise(low, T)
+    e, twin = _fresh(low), _fresh(low)
+    got = _raw(e, sp, 1, 3, 3, T, pk, pb, None)
+    twin.solve(sp, poll_every=0)
+    roll = twin.policy_rollout(1, None if pk is None else pk[:, None], pb[:, None], keep_trajectories=True)
+    gc.sync()
+    assert np.abs(gc.to_np(twin.region(_abi.R_KGAIN))[1:]).max() > 1e-3
+    xs = gc.to_np(roll.xs)[:, 0].transpose(1, 0, 2)
+    us = gc.to_np(twin.pad_u(roll.us[:, 0])).transpose(1, 0, 2)
+    ex, eu = pol.relerr(got["x"], xs), pol.relerr(got["u"], us)
+    term = np.array([oracle.knot(_traj_oracle.single(low, i), int(low.node_model[T]), xs[T, i], None,
+                                 frame_ref=None if low.frame_ref is None else low.frame_ref[i], diff=False)["cost"] for i in range(B)])
+    ec = pol.relerr(got["cost"], gc.to_np(roll.cost)[:, 0] - term)
+    print("%s: against the policy roll-out: x %.2e, u %.2e, cost %.2e" % (name, ex, eu, ec))
+    assert (got["failed"] == -1).all() and (gc.to_np(roll.failed_knot) == -1).all()
+    assert max(ex, eu, ec) < 1e-9, (ex, eu, ec)
+    assert np.abs(got["x"][1:] - gc.to_np(twin.region(_abi.R_XS))[1:]).max() > 1e-6   # (the plant moved the loop off the plan)
+
+
+# ---- 8. 2-joint handles ----
+@pytest.mark.parametrize("case", ["sea", "vsa_table"])
+def test_two_joint_handles_get_the_bits_of_aslr_mpc_run_plant(case):
+    n, hold, first, per = 2, 2, 3, 2
+    sc = scenarios.two_dof_sea(B=5, T=4, seed=4) if case == "sea" else pol.scenario("two_dof_vsa_boxddp", 5, 4, True, False)
+    low = scenarios.lower(sc)
+    sp = scenarios.solver_params(sc, solver="SolverFDDP" if case == "sea" else "SolverBoxDDP", maxiter=3)
+    pk, pb, dist = _plants_and_noise(low, n * hold)
+    a, b = _fresh(low), _fresh(low)
+    new = _raw(a, sp, n, first, per, hold, pk, pb, dist, case != "sea")
+    old = _raw(b, sp, n, first, per, hold, pk, pb, dist, case != "sea", name="aslr_mpc_run_plant")
+    _same_runs(new, old, "aslr_mpc_run_plant_all against aslr_mpc_run_plant")
+    for rid in REGIONS:
+        gc.same_bits(a.region(rid), b.region(rid), "region %d" % rid)
+    assert (new["failed"] == -1).all() and (new["stat_i"][:, 0].max(axis=1) >= 1).all()
+
+
+# ---- 9. refusals ----
+def _solve_matches_a_fresh_handle(e, low, sp):
+    fresh = gc.engine(low)
+    for h in (e, fresh):
+        h.set_candidate(None, None)
+        h.solve(sp, poll_every=4)
+    gc.sync()
+    for rid in REGIONS[:4]:
+        gc.same_bits(e.region(rid), fresh.region(rid), "region %d after a refused %s" % (rid, NAME))
+
+
+def _refused(e, sp, word, *args, **kw):
+    name = kw.get("name", NAME)
+    msg = _raw(e, sp, *args, expect=_abi.E_INVALID, **kw)
+    assert msg.startswith(name + ":") and word in msg, msg
+    return msg
+
+
+def test_refusals_enqueue_nothing_and_leave_the_handle_usable():
+    sc, low, sp = _arm("talos_arm_sea", 3, 4)
+    e = _fresh(low)
+    ones = np.ones((3, 7))
+    # what aslr_mpc_run refuses
+    for args in ((0, 3, 2), (2, 0, 2), (2, 3, 0)):
+        _refused(e, sp, "n_steps, first_maxiter and iters_per_step must be >= 1", *args, hold=2)
+    e.enable_iteration_log(20)
+    _refused(e, sp, "an iteration log is set", 2, 3, 2, hold=2)
+    e.enable_iteration_log(0)
+    # the hold
+    for hold in (0, -1, 5):
+        _refused(e, sp, "hold", 2, 3, 2, hold=hold)
+    # n_steps * hold beyond INT32_MAX: refused before anything is sized by it (the small buffers here are never touched)
+    import torch
+    buf = torch.full((64,), SENTINEL, dtype=torch.float64, device=e.device)
+    ibuf = torch.full((64,), -7, dtype=torch.int32, device=e.device)
+    mpc = _abi.Mpc()
+    mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = 2 ** 29, 3, 2
+    mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = buf.data_ptr(), buf.data_ptr(), buf.data_ptr(), ibuf.data_ptr()
+    with torch.cuda.device(e.device):
+        assert e.lib.aslr_mpc_run_plant_all(e.handle, C.byref(sp), C.byref(mpc), 4, None, None, 0, None, None, e._stream()) == _abi.E_INVALID
+    msg = e.lib.aslr_last_error().decode()
+    assert msg.startswith(NAME + ":") and "overflow" in msg, msg
+    gc.sync()
+    assert (buf == SENTINEL).all() and (ibuf == -7).all()
+    _solve_matches_a_fresh_handle(e, low, sp)
+    assert _raw(e, sp, 2, 3, 2, 4, ones * pol.nominal_diag(low, 0, "K"), ones * pol.nominal_diag(low, 0, "B"))["x"].shape == (9, 3, 28)   # (hold = T runs, on the same handle)
+    # two distinct running models
+    mixed = dict(sc)
+    mixed["running"] = [sc["running"][0]] * 2 + [copy.copy(sc["running"][0])] * 2
+    lowm = scenarios.lower(mixed)
+    em = _fresh(lowm)
+    _refused(em, sp, "more than one action model", 2, 3, 2, hold=2)
+    _solve_matches_a_fresh_handle(em, lowm, sp)
+    # plant_stiffness on a VSA model; (7, VSA) with SolverDDP: aslr_mpc_run's refusal
+    scv, lowv, spv = _arm("talos_arm_vsa", 3, 4)
+    ev = _fresh(lowv)
+    _refused(ev, spv, "VSA", 2, 3, 2, hold=2, pk=ones)
+    _refused(ev, scenarios.solver_params(scv, solver="SolverDDP", maxiter=3), "built for SolverBoxDDP only", 2, 3, 2, hold=2)
+    _solve_matches_a_fresh_handle(ev, lowv, spv)
+    # K that is not diagonal: refused with a plant argument, run on the model's full rows without one
+    lown = scenarios.lower(scenarios.talos_arm_sea(B=3, T=4, seed=mt.SCENARIO_SEED))
+    for i in range(lown.desc.nmodels):   # (the lowered description is what aslr_problem_create reads)
+        lown.desc.models[i].K[1] = lown.desc.models[i].K[7] = 0.03
+    en = _fresh(lown)
+    _refused(en, sp, "diagonal", 2, 3, 2, hold=2, pb=np.full((3, 7), 1e-2))
+    _solve_matches_a_fresh_handle(en, lown, sp)
+    # the old entry point still refuses the 7-joint handle, in its own name, also when nothing is asked of the plant
+    e7 = _fresh(low)   # (the run above moved X0 of `e`)
+    msg = _refused(e7, sp, "7-joint", 2, 3, 2, hold=2, name="aslr_mpc_run_plant")
+    assert "nx = 8" in msg
+    _refused(e7, sp, "nx = 8", 2, 3, 2, hold=1, cost=False, failed=False, name="aslr_mpc_run_plant")
+    _solve_matches_a_fresh_handle(e7, low, sp)
+
+
+def test_a_model_that_is_not_diagonal_runs_on_its_full_rows(oracle):
+    """no plant argument and no table: K with off-diagonal entries is the plant, as in policy_rollout_team_kernel -- one
+    control step against mp.plant_phase within 1e-9, and the off-diagonal entries are seen (the diagonal model differs)"""
+    hold = 2
+    sc, low, sp = _arm("talos_arm_sea", 3, 4)
+    lown = scenarios.lower(sc)
+    for i in range(lown.desc.nmodels):
+        lown.desc.models[i].K[1] = lown.desc.models[i].K[7] = 0.03
+    dist = np.random.default_rng(mt.DIST_SEED).uniform(-mt.DIST, mt.DIST, (hold, 3, low.nx))
+    e, twin = _fresh(lown), _fresh(lown)
+    got = _raw(e, sp, 1, 3, 3, hold, None, None, dist)
+    twin.solve(sp, poll_every=0)
+    gc.sync()
+    X, U, K = (gc.to_np(twin.region(r)) for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN))
+    ref = [mp.plant_phase(oracle, lown, b, X[:, b], U[:, b], K[:, b], hold, None, None, dist[:, b]) for b in range(3)]
+    errs = dict(x=pol.relerr(got["x"], np.stack([r["x"] for r in ref], axis=1)), u=pol.relerr(got["u"], np.stack([r["u"] for r in ref], axis=1)),
+                cost=pol.relerr(got["cost"], np.array([r["cost"] for r in ref])))
+    print("not diagonal: relerr %s" % {k: "%.2e" % v for k, v in errs.items()})
+    assert max(errs.values()) < 1e-9, errs
+    diag = _raw(_fresh(low), sp, 1, 3, 3, hold, None, None, dist)
+    assert np.abs(diag["x"][1] - got["x"][1]).max() > 1e-6
+
+
+# ---- 10. Python ----
+def test_python_facade():
+    import torch
+    B, T = 3, 8
+    sc = scenarios.talos_arm_sea(B=B, T=T, seed=4)
+    make = lambda cls, s: cls(crocoddyl.ShootingProblem(s["x0"], s["running"], s["terminal"], frame_refs=s["frame_refs"]))
+    solver = make(crocoddyl.SolverFDDP, sc)
+    pb = 1.2 * np.array([pol.nominal_diag(solver.problem.engine.low, b, "B") for b in range(B)])
+    r = solver.solve_mpc(3, 2, maxiter=6, hold=2, plant_motor_inertia=pb, closed_cost=True)
+    assert tuple(r.xs_closed.shape) == (B, 7, 28) and tuple(r.us_closed.shape) == (B, 6, 7)
+    assert tuple(r.closed_cost.shape) == (B,) and tuple(r.failed_knot.shape) == (B,) and r.failed_knot.dtype == torch.int32
+    assert r.hold == 2 and tuple(r.iters.shape) == (B, 3) and tuple(r.cost.shape) == (B, 3)
+    assert torch.isfinite(r.closed_cost).all() and (r.failed_knot == -1).all()
+    # clamp=None follows the solver class: SolverBoxDDP clamps the feedback control to the (narrowed) box
+    scv = mt.scenario("talos_arm_vsa", B, T, table=True, box=True)
+    tp = scv["traj_params"]
+    makev = lambda: crocoddyl.SolverBoxDDP(crocoddyl.ShootingProblem(scv["x0"], scv["running"], scv["terminal"],
+                                                                     frame_refs=scv["frame_refs"], **tp))
+    pbv = 1.3 * np.asarray(tp["motor_inertia"])
+    runs = {c: makev().solve_mpc(2, 3, maxiter=3, hold=3, plant_motor_inertia=pbv, clamp=c) for c in (None, True)}
+    gc.same_bits(runs[None].us_closed, runs[True].us_closed, "clamp=None under SolverBoxDDP is clamp=True")
+    box = lambda v: torch.as_tensor(v, dtype=torch.float64, device=runs[True].us_closed.device)
+    lb, ub = (box(v) for v in pt.box(7))
+    assert ((runs[True].us_closed >= lb) & (runs[True].us_closed <= ub)).all()
