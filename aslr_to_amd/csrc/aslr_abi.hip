@@ -1,6 +1,7 @@
 // aslr_abi.hip -- the C ABI of include/aslr_to_amd.h: handle, workspace carving, solver driver.
 // The kernels live in aslr_calc_*.hip / aslr_backward_*.hip / aslr_forward_*.hip.
 #include <cstdarg>
+#include <functional>
 #include <memory>
 #include <new>
 #include <vector>
@@ -18,6 +19,9 @@
 #include "../../include/aslr_to_amd_design.h"
 
 using namespace aslr;
+
+// HIP_TRY inside a body that several entry points share: the message names the entry point that was called, fn
+#define HIP_TRY_AS(fn, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return aslr::fail(ASLR_E_HIP, "%s: %s -> %s (%s:%d)", fn, #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 
 namespace {
 thread_local char g_err[kErrLen] = {0};
@@ -765,19 +769,103 @@ int iterate_n(const char *fn, aslr_problem *p, const aslr_solver_params_t *sp, i
   return iterate(p, sp, first != 0, n, static_cast<hipStream_t>(stream), IterOpts{p->k, 0, first != 0, nullptr});
 }
 
-// aslr_solve_pool: flush the stopped slots and hand them their next problems ...
+// aslr_solve_pool: flush the stopped slots and hand them their next problems
 int pool_refill(const KArgs &k, const PoolDev &pl, const aslr_solver_params_t *sp, hipStream_t st) {
   hipLaunchKernelGGL(pool_refill_kernel, dim3(k.B), dim3(64), 0, st, k, pl, reg_start(sp), sp->is_feasible);
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }
-// ... and read how many problems have been written out so far
-int pool_flush_and_count(const aslr_problem *p, const KArgs &k, const PoolDev &pl, const aslr_solver_params_t *sp, hipStream_t st, int32_t *fin) {
-  if (int rc = pool_refill(k, pl, sp, st)) return rc;
-  HIP_TRY(hipMemcpyAsync(p->h_done, pl.counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  *fin = p->h_done[0];
-  return ASLR_OK;
+
+// what aslr_solve_pool refuses, under the name of the entry point that was called (aslr_solve_pool_params refuses the same).
+// table_set: why that call declines a handle with a parameter table, and what to do about it
+int pool_refusals(const char *fn, const aslr_problem *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool, const char *table_set) {
+  if (!p) return no_handle(fn);
+  if (!sp || !pool) return fail(ASLR_E_INVALID, "%s: %s is NULL", fn, !sp ? "sp" : "pool");
+  if (pool->P <= 0) return fail(ASLR_E_INVALID, "%s: pool->P = %d must be >= 1", fn, pool->P);
+  if (!pool->x0 || !pool->xs_out || !pool->us_out || !pool->stat_f || !pool->stat_i || !pool->slot_problem || !pool->counters)
+    return fail(ASLR_E_INVALID, "%s: x0, xs_out, us_out, stat_f, stat_i, slot_problem and counters of the pool must be given", fn);
+  if (sp->maxiter <= 0 || sp->fixed_iterations)
+    return fail(ASLR_E_INVALID, "%s: sp->maxiter = %d must be >= 1 and sp->fixed_iterations = %d must be 0 (slots stop by themselves)", fn, sp->maxiter, sp->fixed_iterations);
+  if (pool->frame_ref && !p->k.frame_ref)
+    return fail(ASLR_E_INVALID, "%s: per-problem frame references need a problem created with a frame_ref table", fn);
+  if (p->ks->traj_params)
+    return fail(ASLR_E_INVALID, "%s: the handle has a per-trajectory parameter table set %s", fn, table_set);
+  if (p->ref_path_set)
+    return fail(ASLR_E_INVALID, "%s: the handle has a reference path set (a pool problem would inherit its slot's path); clear it with aslr_set_reference_path(p, NULL, 0, 0, stream)", fn);
+  return solver_unsupported(fn, p, sp->solver);
+}
+
+// The body of aslr_solve_pool and aslr_solve_pool_params, after their refusals.  fn: the entry point a message names;
+// refill(k): the launch that flushes the stopped slots and hands them their next problems, with argument block k;
+// run_set: the kernel set that iterates while the call runs (other than the handle's: switched to, and back on every return
+// behind the switch); fresh_first: IterOpts::fresh_first of every round
+int pool_run(const char *fn, aslr_problem *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool, int32_t refill_every,
+             int32_t poll_every, hipStream_t st, int32_t *iters_done, const KernelSet *run_set, bool fresh_first,
+             const std::function<int(const KArgs &)> &refill) {
+  const int B = p->desc.B;
+  if (refill_every <= 0) refill_every = 4;
+  if (poll_every <= 0) poll_every = 4 * refill_every;
+  if (poll_every > sp->maxiter + refill_every) poll_every = sp->maxiter + refill_every; // (a short maxiter must still be polled)
+  // every slot starts idle; the first refill hands out the first B problems
+  HIP_TRY_AS(fn, hipMemsetAsync(pool->slot_problem, 0xFF, sizeof(int32_t) * B, st));
+  HIP_TRY_AS(fn, hipMemsetAsync(pool->counters, 0, sizeof(int32_t) * 2, st));
+  HIP_TRY_AS(fn, hipMemsetAsync(p->k.traj_i + (size_t)ASLR_TI_DONE * B, 0, sizeof(int32_t) * B, st));
+  // the refill overwrites the slots' x0 / frame_ref columns with the pool's: keep the handle's own and put them back
+  // on exit, so that a later solve / rollout on this handle sees the problems it was created with
+  double *save = reinterpret_cast<double *>(region(p, ASLR_R_POOL_SAVE));
+  HIP_TRY_AS(fn, hipMemcpyAsync(save, p->k.x0, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st));
+  if (p->k.frame_ref) HIP_TRY_AS(fn, hipMemcpyAsync(save + (size_t)B * p->nx, p->k.frame_ref, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st));
+  // While the call runs the handle iterates with run_set.  Where that is the set that reads TRAJ_PARAMS, the model-only
+  // record chunks in place belong to the models' constants: the mark is cleared, so the first sweep that covers every slot
+  // sets it again
+  const KernelSet *own_set = p->ks;
+  if (run_set != own_set) { p->ks = run_set; p->const_written = false; }
+  // the pool's argument block; trajectories stop by themselves after maxiter iterations; the first sweep covers every
+  // slot when the pool fills them all
+  IterOpts o{p->k, sp->maxiter, pool->P >= B, nullptr};
+  o.k.iter_log = nullptr; o.k.log_cap = 0; // (a slot's iteration index restarts with every problem)
+  // the closed-form reach residual was validated for the references given at create time only (fill_planar_reach):
+  // pool targets take the general log map
+  if (pool->frame_ref) o.k.planar_reach = 0;
+  o.fresh_first = fresh_first;
+  // flush (the refill before it ran ahead of the iterations since), then read how many problems have been written out so far
+  const auto flush_and_count = [&](int32_t *fin) -> int {
+    if (int rc = refill(o.k)) return rc;
+    HIP_TRY_AS(fn, hipMemcpyAsync(p->h_done, pool->counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY_AS(fn, hipStreamSynchronize(st));
+    *fin = p->h_done[0];
+    return ASLR_OK;
+  };
+  int it = 0, rc = ASLR_OK;
+  // the slowest possible schedule: every problem takes maxiter iterations, one wave of B problems after the other
+  const long long cap = ((long long)(pool->P + B - 1) / B + 1) * (long long)(sp->maxiter + refill_every);
+  while (it < cap) {
+    rc = refill(o.k);
+    if (!rc) rc = iterate(p, sp, false, refill_every, st, o);
+    if (rc) break;
+    o.full_first = false; // (later rounds evaluate the refilled slots only)
+    it += refill_every;
+    if (it % poll_every < refill_every) {
+      int32_t fin = 0;
+      rc = flush_and_count(&fin);
+      if (rc || fin >= pool->P) break;
+    }
+  }
+  int32_t fin_total = -1;
+  // one more flush, then every problem must have been written out
+  if (!rc) rc = flush_and_count(&fin_total);
+  { // (after an error in the loop this restore is enqueued without a synchronisation first: ADVICE.md proposes one)
+    hipError_t e = hipMemcpyAsync(const_cast<double *>(p->k.x0), save, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && p->k.frame_ref) e = hipMemcpyAsync(const_cast<double *>(p->k.frame_ref), save + (size_t)B * p->nx, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess && !rc) rc = fail(ASLR_E_HIP, "%s: putting the handle's x0 / frame_ref back failed: %s", fn, hipGetErrorString(e));
+  }
+  // back on the handle's own set; the record chunks in place belong to the last designs of the slots: the next sweep of
+  // the handle rewrites them (as after aslr_set_trajectory_params)
+  if (run_set != own_set) { p->ks = own_set; p->const_written = false; }
+  if (iters_done) *iters_done = it;
+  if (rc) return rc;
+  if (fin_total < pool->P) return fail(ASLR_E_INVALID, "%s: %d of %d problems finished within the iteration bound", fn, fin_total, pool->P);
+  return launch_reset_accepted(p->k, st);
 }
 
 // what aslr_mpc_run refuses, under the name of the entry point that was called (aslr_mpc_run_plant refuses the same)
@@ -873,6 +961,47 @@ std::vector<double> motor_inertia_rows(const aslr_problem *p, const aslr_traj_pa
     for (int j = 0; j < nj; ++j)
       bd[(size_t)j * n + b] = tp->motor_inertia ? tp->motor_inertia[(size_t)b * nj + j] : p->desc.models[0].B[j * nj + j];
   return bd;
+}
+
+// K and B of every model diagonal and, with `zeros`, no zero the sweep divides by: model by model the diagonal test, then
+// joint by joint K (when the stiffness term is computed, `stiff`, from the models' constants) and B; then the stiffness rows
+// of the parameter table (when `stiff` and a table is set).  The first failure is the refusal.
+int model_refusals(const char *fn, const aslr_problem *p, bool zeros, bool stiff) {
+  const int B = p->desc.B, nj = p->nj;
+  const bool table = p->ks->traj_params;
+  const aslr_model_t *M = p->desc.models;
+  for (int i = 0; i < p->desc.nmodels; ++i) {
+    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "%s: K and B of model %d must be diagonal", fn, i);
+    for (int j = 0; zeros && j < nj; ++j) {
+      if (stiff && !table && M[i].K[j * nj + j] == 0.0) return fail(ASLR_E_INVALID, "%s: stiffness entry K[%d] of model %d is 0 (the stiffness term divides by it)", fn, j, i);
+      if (M[i].B[j * nj + j] == 0.0) return fail(ASLR_E_INVALID, "%s: motor inertia entry B[%d] of model %d is 0", fn, j, i);
+    }
+  }
+  if (zeros && stiff && table)
+    for (int j = 0; j < nj; ++j)
+      for (int b = 0; b < B; ++b)
+        if (p->tp_host[(size_t)j * B + b] == 0.0) return fail(ASLR_E_INVALID, "%s: stiffness entry [%d][%d] of the parameter table is 0 (the stiffness term divides by it)", fn, b, j);
+  return ASLR_OK;
+}
+
+// what a roll-out and an MPC run refuse of their plant arguments (diagonals of the plant's K and B, each nullable)
+int plant_arg_refusals(const char *fn, const aslr_problem *p, const double *plant_stiffness, const double *plant_motor_inertia) {
+  if (plant_stiffness && p->dam != ASLR_DAM_SEA)
+    return fail(ASLR_E_INVALID, "%s: plant_stiffness on a VSA model, which takes its stiffness from u", fn);
+  if (plant_stiffness || plant_motor_inertia)
+    for (int i = 0; i < p->desc.nmodels; ++i)
+      if (!is_diagonal(p->nj, p->desc.models[i].K) || !is_diagonal(p->nj, p->desc.models[i].B))
+        return fail(ASLR_E_INVALID, "%s: a plant argument needs diagonal K and B, and those of model %d are not", fn, i);
+  return ASLR_OK;
+}
+
+// a solve as aslr_solve enqueues it when the host never polls: n iterations from a fresh solver state with argument block
+// k, then the commit of aslr_finalize.  fresh_first: IterOpts::fresh_first
+int solve_unpolled(aslr_problem *p, const aslr_solver_params_t *sp, int n, const KArgs &k, bool fresh_first, hipStream_t st) {
+  IterOpts o{k, 0, true, nullptr};
+  o.fresh_first = fresh_first;
+  if (int rc = iterate(p, sp, true, n, st, o)) return rc;
+  return aslr_finalize(p, st);
 }
 
 } // namespace
@@ -1049,22 +1178,9 @@ int aslr_cost_sensitivity(aslr_problem_t *p, double *dcost_dstiffness, double *d
   if (!p) return no_handle("aslr_cost_sensitivity");
   if (!dcost_dstiffness && !dcost_dmotor_inertia && !dcost_dx0 && !costate)
     return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: all four outputs are NULL: nothing to compute");
-  const bool sea = p->dam == ASLR_DAM_SEA, table = p->ks->traj_params;
+  const bool sea = p->dam == ASLR_DAM_SEA;
   if (dcost_dstiffness && !sea) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: dcost_dstiffness on a VSA model, which takes its stiffness from u");
-  const int B = p->desc.B, nj = p->nj, nm = p->desc.nmodels;
-  const aslr_model_t *M = p->desc.models;
-  for (int i = 0; i < nm; ++i) {
-    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: K and B of model %d must be diagonal", i);
-    for (int j = 0; j < nj; ++j) {
-      const double k = M[i].K[j * nj + j], bj = M[i].B[j * nj + j];
-      if (sea && !table && k == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: stiffness entry K[%d] of model %d is 0 (the stiffness term divides by it)", j, i);
-      if (bj == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: motor inertia entry B[%d] of model %d is 0", j, i);
-    }
-  }
-  if (sea && table)
-    for (int j = 0; j < nj; ++j)
-      for (int b = 0; b < B; ++b)
-        if (p->tp_host[(size_t)j * B + b] == 0.0) return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: stiffness entry [%d][%d] of the parameter table is 0 (the stiffness term divides by it)", b, j);
+  if (int rc = model_refusals("aslr_cost_sensitivity", p, true, sea)) return rc;
   return adjoint_sweeps(p, dcost_dstiffness, dcost_dmotor_inertia, dcost_dx0, costate, static_cast<hipStream_t>(stream));
 }
 
@@ -1106,25 +1222,18 @@ int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var
     return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: no kernel for records of (nx = %d, nu = %d)", p->nx, p->nu);
   // the stiffness columns are computed when an output of theirs, or their variance in x_var / u_var, is asked for
   const bool stiff = dx_dstiffness || dxT_dstiffness || dcost_dstiffness || (stiffness_var && (x_var || u_var));
-  const int B = p->desc.B, nj = p->nj, nm = p->desc.nmodels;
+  if (int rc = model_refusals("aslr_policy_plant_sensitivity", p, true, stiff)) return rc;
+  const int nj = p->nj;
   const aslr_model_t *M = p->desc.models;
   PlantSensArgs a;
   memset(&a, 0, sizeof a);
-  for (int i = 0; i < nm; ++i) {
-    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B)) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: K and B of model %d must be diagonal", i);
+  for (int i = 0; i < p->desc.nmodels; ++i) {
     a.dt[i] = M[i].dt;
     for (int j = 0; j < nj; ++j) {
-      const double k = M[i].K[j * nj + j], bj = M[i].B[j * nj + j];
-      if (stiff && !table && k == 0.0) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: stiffness entry K[%d] of model %d is 0 (the stiffness term divides by it)", j, i);
-      if (bj == 0.0) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: motor inertia entry B[%d] of model %d is 0", j, i);
-      a.K[i][j] = sea ? k : 0.0;
-      a.Binv[i][j] = 1.0 / bj;
+      a.K[i][j] = sea ? M[i].K[j * nj + j] : 0.0;
+      a.Binv[i][j] = 1.0 / M[i].B[j * nj + j];
     }
   }
-  if (stiff && table)
-    for (int j = 0; j < nj; ++j)
-      for (int b = 0; b < B; ++b)
-        if (p->tp_host[(size_t)j * B + b] == 0.0) return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: stiffness entry [%d][%d] of the parameter table is 0 (the stiffness term divides by it)", b, j);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
   const KArgs &k = p->k;
@@ -1137,58 +1246,44 @@ int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var
   return launch_plant_sens(p->nx, p->nu, a, st);
 }
 
-int aslr_policy_rollout(aslr_problem_t *p, int n_samples, const double *plant_stiffness, const double *plant_motor_inertia,
-                        const double *dx0, const double *disturbance, int clamp, double *cost, int32_t *failed_knot,
-                        double *x_final, double *xs_closed, double *us_closed, void *stream) {
-  if (!p) return no_handle("aslr_policy_rollout");
-  if (n_samples <= 0) return fail(ASLR_E_INVALID, "aslr_policy_rollout: n_samples is %d, must be positive", n_samples);
-  if (n_samples > 16 * 65535) return fail(ASLR_E_INVALID, "aslr_policy_rollout: n_samples is %d, above the %d of one launch", n_samples, 16 * 65535);
+// aslr_policy_rollout and aslr_policy_rollout_all (include/aslr_to_amd_policy_all.h): one body.  fn: the entry point a
+// refusal names; arms: 7-joint handles are admitted (their roll-out is policy_rollout_team_kernel's)
+namespace {
+int policy_rollout(const char *fn, bool arms, aslr_problem_t *p, int n_samples, const double *plant_stiffness,
+                   const double *plant_motor_inertia, const double *dx0, const double *disturbance, int clamp, double *cost,
+                   int32_t *failed_knot, double *x_final, double *xs_closed, double *us_closed, void *stream) {
+  if (!p) return no_handle(fn);
+  if (n_samples <= 0) return fail(ASLR_E_INVALID, "%s: n_samples is %d, must be positive", fn, n_samples);
+  // (16 samples per block along grid y for both kernels)
+  if (n_samples > 16 * 65535) return fail(ASLR_E_INVALID, "%s: n_samples is %d, above the %d of one launch", fn, n_samples, 16 * 65535);
   if (!cost && !failed_knot && !x_final && !xs_closed && !us_closed)
-    return fail(ASLR_E_INVALID, "aslr_policy_rollout: all five outputs are NULL: nothing to compute");
-  if (p->nj != 2)
-    return fail(ASLR_E_INVALID, "aslr_policy_rollout: the roll-out kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint team form is not built); aslr_policy_rollout_all serves every size", p->nj);
-  if (plant_stiffness && p->dam != ASLR_DAM_SEA)
-    return fail(ASLR_E_INVALID, "aslr_policy_rollout: plant_stiffness on a VSA model, which takes its stiffness from u");
+    return fail(ASLR_E_INVALID, "%s: all five outputs are NULL: nothing to compute", fn);
+  if (p->nj != 2 && !arms)
+    return fail(ASLR_E_INVALID, "%s: the roll-out kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint team form is not built); aslr_policy_rollout_all serves every size", fn, p->nj);
+  if (p->nj != 2 && p->nj != 7)
+    return fail(ASLR_E_INVALID, "%s: no roll-out kernel for this %d-joint handle", fn, p->nj);
+  if (int rc = plant_arg_refusals(fn, p, plant_stiffness, plant_motor_inertia)) return rc;
   const bool table = p->ks->traj_params;
-  if (plant_stiffness || plant_motor_inertia)
-    for (int i = 0; i < p->desc.nmodels; ++i)
-      if (!is_diagonal(p->nj, p->desc.models[i].K) || !is_diagonal(p->nj, p->desc.models[i].B))
-        return fail(ASLR_E_INVALID, "aslr_policy_rollout: a plant argument needs diagonal K and B, and those of model %d are not", i);
   PolicyArgs a;
   memset(&a, 0, sizeof a);
   a.plant_stiffness = plant_stiffness; a.plant_motor_inertia = plant_motor_inertia; a.dx0 = dx0; a.disturbance = disturbance;
   a.cost = cost; a.failed_knot = failed_knot; a.x_final = x_final; a.xs_closed = xs_closed; a.us_closed = us_closed;
   a.S = n_samples; a.clamp = clamp != 0;
   a.table = table; a.diagonal = table || plant_stiffness || plant_motor_inertia;
-  return launch_policy_rollout(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+  return (p->nj == 2 ? launch_policy_rollout : launch_policy_rollout_team)(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+}
+} // namespace
+
+int aslr_policy_rollout(aslr_problem_t *p, int n_samples, const double *plant_stiffness, const double *plant_motor_inertia,
+                        const double *dx0, const double *disturbance, int clamp, double *cost, int32_t *failed_knot,
+                        double *x_final, double *xs_closed, double *us_closed, void *stream) {
+  return policy_rollout("aslr_policy_rollout", false, p, n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance, clamp, cost, failed_knot, x_final, xs_closed, us_closed, stream);
 }
 
 int aslr_policy_rollout_all(aslr_problem_t *p, int n_samples, const double *plant_stiffness, const double *plant_motor_inertia,
                             const double *dx0, const double *disturbance, int clamp, double *cost, int32_t *failed_knot,
                             double *x_final, double *xs_closed, double *us_closed, void *stream) {
-  if (!p) return no_handle("aslr_policy_rollout_all");
-  if (n_samples <= 0) return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: n_samples is %d, must be positive", n_samples);
-  // (16 samples per block along grid y for both kernels)
-  if (n_samples > 16 * 65535) return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: n_samples is %d, above the %d of one launch", n_samples, 16 * 65535);
-  if (!cost && !failed_knot && !x_final && !xs_closed && !us_closed)
-    return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: all five outputs are NULL: nothing to compute");
-  if (p->nj != 2 && p->nj != 7)
-    return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: no roll-out kernel for this %d-joint handle", p->nj);
-  if (plant_stiffness && p->dam != ASLR_DAM_SEA)
-    return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: plant_stiffness on a VSA model, which takes its stiffness from u");
-  const bool table = p->ks->traj_params;
-  if (plant_stiffness || plant_motor_inertia)
-    for (int i = 0; i < p->desc.nmodels; ++i)
-      if (!is_diagonal(p->nj, p->desc.models[i].K) || !is_diagonal(p->nj, p->desc.models[i].B))
-        return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: a plant argument needs diagonal K and B, and those of model %d are not", i);
-  PolicyArgs a;
-  memset(&a, 0, sizeof a);
-  a.plant_stiffness = plant_stiffness; a.plant_motor_inertia = plant_motor_inertia; a.dx0 = dx0; a.disturbance = disturbance;
-  a.cost = cost; a.failed_knot = failed_knot; a.x_final = x_final; a.xs_closed = xs_closed; a.us_closed = us_closed;
-  a.S = n_samples; a.clamp = clamp != 0;
-  a.table = table; a.diagonal = table || plant_stiffness || plant_motor_inertia;
-  if (p->nj == 2) return launch_policy_rollout(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
-  return launch_policy_rollout_team(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+  return policy_rollout("aslr_policy_rollout_all", true, p, n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance, clamp, cost, failed_knot, x_final, xs_closed, us_closed, stream);
 }
 
 int aslr_backward_pass(aslr_problem_t *p, const aslr_solver_params_t *sp, void *stream) {
@@ -1314,9 +1409,7 @@ int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_m
     if (p->ref_path_set) ks.ref_row0 = row0 + s;
     KArgs plant = ks; // the plant: node 0's action model on knot 0 of every trajectory, through the handle's calc launcher
     plant.seg_t1 = 0;
-    // a solve as aslr_solve enqueues it when the host never polls
-    if (int rc = iterate(p, sp, true, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, st, IterOpts{ks, 0, true, nullptr})) return rc;
-    if (int rc = aslr_finalize(p, stream)) return rc;
+    if (int rc = solve_unpolled(p, sp, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, ks, false, st)) return rc;
     if (int rc = p->ks->calc(plant, false, 0, -1.0, st)) return rc;
     MpcDev m;
     m.nx = p->nx; m.nu = p->nu;
@@ -1346,12 +1439,7 @@ int mpc_run_plant(const char *fn, bool arms, aslr_problem_t *p, const aslr_solve
     return fail(ASLR_E_INVALID, "%s: the plant kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle; aslr_mpc_run_plant_all serves every size", fn, p->nj);
   if (p->nj != 2 && p->nj != 7)
     return fail(ASLR_E_INVALID, "%s: no plant kernel for this %d-joint handle", fn, p->nj);
-  if (plant_stiffness && p->dam != ASLR_DAM_SEA)
-    return fail(ASLR_E_INVALID, "%s: plant_stiffness on a VSA model, which takes its stiffness from u", fn);
-  if (plant_stiffness || plant_motor_inertia)
-    for (int i = 0; i < p->desc.nmodels; ++i)
-      if (!is_diagonal(p->nj, p->desc.models[i].K) || !is_diagonal(p->nj, p->desc.models[i].B))
-        return fail(ASLR_E_INVALID, "%s: a plant argument needs diagonal K and B, and those of model %d are not", fn, i);
+  if (int rc = plant_arg_refusals(fn, p, plant_stiffness, plant_motor_inertia)) return rc;
   const long long N = (long long)mpc->n_steps * hold;
   const int32_t row0 = p->k.ref_row0;
   if (N > INT32_MAX || (p->ref_path_set && row0 > (long long)INT32_MAX - N - T))
@@ -1367,8 +1455,7 @@ int mpc_run_plant(const char *fn, bool arms, aslr_problem_t *p, const aslr_solve
     // row0 + k0 + t, its plant phase applies knot j against row row0 + k0 + j (by value in the argument block, as aslr_mpc_run)
     KArgs ks = p->k;
     if (p->ref_path_set) ks.ref_row0 = row0 + (int32_t)k0;
-    if (int rc = iterate(p, sp, true, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, st, IterOpts{ks, 0, true, nullptr})) return rc;
-    if (int rc = aslr_finalize(p, stream)) return rc;
+    if (int rc = solve_unpolled(p, sp, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, ks, false, st)) return rc;
     MpcPlantArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.plant_stiffness = plant_stiffness; pa.plant_motor_inertia = plant_motor_inertia;
@@ -1454,10 +1541,9 @@ int aslr_design_descent(aslr_problem_t *p, const aslr_solver_params_t *sp, const
   if (!(d->max_rel > 0.0 && d->max_rel < 1.0)) return fail(ASLR_E_INVALID, "%s: max_rel = %g must lie in (0, 1)", fn, d->max_rel);
   if (p->k.iter_log) return fail(ASLR_E_INVALID, "%s: an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)", fn);
   if (int rc = solver_unsupported(fn, p, sp->solver)) return rc;
-  const int B = p->desc.B, nj = p->nj, nm = p->desc.nmodels;
+  const int B = p->desc.B, nj = p->nj;
   const bool sea = p->dam == ASLR_DAM_SEA, had_table = p->ks->traj_params;
-  for (int i = 0; i < nm; ++i)
-    if (!is_diagonal(nj, p->desc.models[i].K) || !is_diagonal(nj, p->desc.models[i].B)) return fail(ASLR_E_INVALID, "%s: K and B of model %d must be diagonal", fn, i);
+  if (int rc = model_refusals(fn, p, false, false)) return rc;
   const KernelSet *tp_set = find_kernel_set(nj, p->dam, true);
   if (!tp_set) return fail(ASLR_E_INVALID, "%s: no per-trajectory-parameter kernels for (nj=%d, dam=%d)", fn, nj, p->dam);
   // ---- the initial design: the handle's table, or the models' constants lowered as aslr_set_trajectory_params lowers them ----
@@ -1506,12 +1592,9 @@ int aslr_design_descent(aslr_problem_t *p, const aslr_solver_params_t *sp, const
     aslr_solver_params_t sps = *sp;
     for (int s = 0; s < d->n_steps; ++s) {
       if (s > 0) sps.is_feasible = 0; // the plan was made under other parameters
-      // a solve as aslr_solve enqueues it when the host never polls; its first sweep rewrites the model-only record chunks,
-      // which depend on the candidate the step kernel has just put into the table
-      IterOpts o{p->k, 0, true, nullptr};
-      o.fresh_first = true;
-      if (int rc = iterate(p, &sps, true, s == 0 ? d->first_maxiter : d->iters_per_step, st, o)) return rc;
-      if (int rc = aslr_finalize(p, stream)) return rc;
+      // the first sweep of the solve rewrites the model-only record chunks, which depend on the candidate the step kernel
+      // has just put into the table
+      if (int rc = solve_unpolled(p, &sps, s == 0 ? d->first_maxiter : d->iters_per_step, p->k, true, st)) return rc;
       if (int rc = design_gradient(p, d, st)) return rc;
       if (int rc = launch_design_step(design_step_args(p, d, s, s == d->n_steps - 1), st)) return rc;
     }
@@ -1539,114 +1622,35 @@ int aslr_debug_design_step(aslr_problem_t *p, const aslr_design_t *d, int32_t s,
 
 int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool, int32_t refill_every,
                     int32_t poll_every, void *stream, int32_t *iters_done) {
-  if (!p) return no_handle("aslr_solve_pool");
-  if (!sp || !pool) return fail(ASLR_E_INVALID, "aslr_solve_pool: %s is NULL", !sp ? "sp" : "pool");
-  if (pool->P <= 0) return fail(ASLR_E_INVALID, "aslr_solve_pool: pool->P = %d must be >= 1", pool->P);
-  if (!pool->x0 || !pool->xs_out || !pool->us_out || !pool->stat_f || !pool->stat_i || !pool->slot_problem || !pool->counters)
-    return fail(ASLR_E_INVALID, "aslr_solve_pool: x0, xs_out, us_out, stat_f, stat_i, slot_problem and counters of the pool must be given");
-  if (sp->maxiter <= 0 || sp->fixed_iterations)
-    return fail(ASLR_E_INVALID, "aslr_solve_pool: sp->maxiter = %d must be >= 1 and sp->fixed_iterations = %d must be 0 (slots stop by themselves)", sp->maxiter, sp->fixed_iterations);
-  if (pool->frame_ref && !p->k.frame_ref)
-    return fail(ASLR_E_INVALID, "aslr_solve_pool: per-problem frame references need a problem created with a frame_ref table");
-  if (p->ks->traj_params)
-    return fail(ASLR_E_INVALID, "aslr_solve_pool: the handle has a per-trajectory parameter table set (a pool problem would inherit its slot's parameters); clear it with aslr_set_trajectory_params(p, NULL, stream)");
-  if (p->ref_path_set)
-    return fail(ASLR_E_INVALID, "aslr_solve_pool: the handle has a reference path set (a pool problem would inherit its slot's path); clear it with aslr_set_reference_path(p, NULL, 0, 0, stream)");
-  if (int rc = solver_unsupported("aslr_solve_pool", p, sp->solver)) return rc;
+  const char *fn = "aslr_solve_pool";
+  if (int rc = pool_refusals(fn, p, sp, pool, "(a pool problem would inherit its slot's parameters); clear it with aslr_set_trajectory_params(p, NULL, stream)")) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int B = p->desc.B;
-  if (refill_every <= 0) refill_every = 4;
-  if (poll_every <= 0) poll_every = 4 * refill_every;
-  if (poll_every > sp->maxiter + refill_every) poll_every = sp->maxiter + refill_every; // (a short maxiter must still be polled)
   PoolDev pl;
   pl.P = pool->P; pl.nx = p->nx; pl.nu = p->nu;
   pl.x0 = pool->x0; pl.frame_ref = pool->frame_ref; pl.xs_out = pool->xs_out; pl.us_out = pool->us_out;
   pl.xs_init = pool->xs_init; pl.us_init = pool->us_init;
   pl.stat_f = pool->stat_f; pl.stat_i = pool->stat_i; pl.slot_problem = pool->slot_problem; pl.counters = pool->counters;
-  // every slot starts idle; the first refill hands out the first B problems
-  HIP_TRY(hipMemsetAsync(pool->slot_problem, 0xFF, sizeof(int32_t) * B, st));
-  HIP_TRY(hipMemsetAsync(pool->counters, 0, sizeof(int32_t) * 2, st));
-  HIP_TRY(hipMemsetAsync(p->k.traj_i + (size_t)ASLR_TI_DONE * B, 0, sizeof(int32_t) * B, st));
-  // the refill overwrites the slots' x0 / frame_ref columns with the pool's: keep the handle's own and put them back
-  // on exit, so that a later solve / rollout on this handle sees the problems it was created with
-  double *save = reinterpret_cast<double *>(region(p, ASLR_R_POOL_SAVE));
-  HIP_TRY(hipMemcpyAsync(save, p->k.x0, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st));
-  if (p->k.frame_ref) HIP_TRY(hipMemcpyAsync(save + (size_t)B * p->nx, p->k.frame_ref, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st));
-  // the pool's argument block; trajectories stop by themselves after maxiter iterations; the first sweep covers every
-  // slot when the pool fills them all
-  IterOpts o{p->k, sp->maxiter, pool->P >= B, nullptr};
-  o.k.iter_log = nullptr; o.k.log_cap = 0; // (a slot's iteration index restarts with every problem)
-  // the closed-form reach residual was validated for the references given at create time only (fill_planar_reach):
-  // pool targets take the general log map
-  if (pool->frame_ref) o.k.planar_reach = 0;
-  int it = 0, rc = ASLR_OK;
-  // the slowest possible schedule: every problem takes maxiter iterations, one wave of B problems after the other
-  const long long cap = ((long long)(pool->P + B - 1) / B + 1) * (long long)(sp->maxiter + refill_every);
-  while (it < cap) {
-    rc = pool_refill(o.k, pl, sp, st);
-    if (!rc) rc = iterate(p, sp, false, refill_every, st, o);
-    if (rc) break;
-    o.full_first = false; // (later rounds evaluate the refilled slots only)
-    it += refill_every;
-    if (it % poll_every < refill_every) {
-      int32_t fin = 0;
-      // (flush before counting: the kernel above ran before these iterations)
-      rc = pool_flush_and_count(p, o.k, pl, sp, st, &fin);
-      if (rc || fin >= pool->P) break;
-    }
-  }
-  int32_t fin_total = -1;
-  // one more flush, then every problem must have been written out
-  if (!rc) rc = pool_flush_and_count(p, o.k, pl, sp, st, &fin_total);
-  { // (after an error in the loop this restore is enqueued without a synchronisation first: ADVICE.md proposes one)
-    hipError_t e = hipMemcpyAsync(const_cast<double *>(p->k.x0), save, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && p->k.frame_ref) e = hipMemcpyAsync(const_cast<double *>(p->k.frame_ref), save + (size_t)B * p->nx, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess && !rc) rc = fail(ASLR_E_HIP, "aslr_solve_pool: putting the handle's x0 / frame_ref back failed: %s", hipGetErrorString(e));
-  }
-  if (iters_done) *iters_done = it;
-  if (rc) return rc;
-  if (fin_total < pool->P) return fail(ASLR_E_INVALID, "aslr_solve_pool: %d of %d problems finished within the iteration bound", fin_total, pool->P);
-  return launch_reset_accepted(p->k, st);
+  return pool_run(fn, p, sp, pool, refill_every, poll_every, st, iters_done, p->ks, false,
+                  [&](const KArgs &k) { return pool_refill(k, pl, sp, st); });
 }
 
 // aslr_solve_pool with per-problem K, 1 / B and control box (include/aslr_to_amd_pool_params.h).
-// The loop is aslr_solve_pool's, restated rather than shared so that the older call stays the code its tests pin.  What
-// differs: the refill kernel also hands a slot its problem's column of the parameter table, the TP kernel set iterates while
-// the call runs, and the first calcDiff sweep after EVERY refill launches without kModeSkipConst (IterOpts::fresh_first).
+// What differs: the refill kernel also hands a slot its problem's column of the parameter table, the TP kernel set iterates
+// while the call runs, and the first calcDiff sweep after EVERY refill launches without kModeSkipConst (IterOpts::fresh_first).
 int aslr_solve_pool_params(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool,
                            const aslr_pool_params_t *pp, int32_t refill_every, int32_t poll_every, void *stream,
                            int32_t *iters_done) {
   if (!pp || (!pp->stiffness && !pp->motor_inertia && !pp->u_lb && !pp->u_ub))
     return aslr_solve_pool(p, sp, pool, refill_every, poll_every, stream, iters_done);
   const char *fn = "aslr_solve_pool_params";
-  // ---- what aslr_solve_pool refuses, under this call's name ----
-  if (!p) return no_handle(fn);
-  if (!sp || !pool) return fail(ASLR_E_INVALID, "%s: %s is NULL", fn, !sp ? "sp" : "pool");
-  if (pool->P <= 0) return fail(ASLR_E_INVALID, "%s: pool->P = %d must be >= 1", fn, pool->P);
-  if (!pool->x0 || !pool->xs_out || !pool->us_out || !pool->stat_f || !pool->stat_i || !pool->slot_problem || !pool->counters)
-    return fail(ASLR_E_INVALID, "%s: x0, xs_out, us_out, stat_f, stat_i, slot_problem and counters of the pool must be given", fn);
-  if (sp->maxiter <= 0 || sp->fixed_iterations)
-    return fail(ASLR_E_INVALID, "%s: sp->maxiter = %d must be >= 1 and sp->fixed_iterations = %d must be 0 (slots stop by themselves)", fn, sp->maxiter, sp->fixed_iterations);
-  if (pool->frame_ref && !p->k.frame_ref)
-    return fail(ASLR_E_INVALID, "%s: per-problem frame references need a problem created with a frame_ref table", fn);
-  // ---- its own ----
-  if (p->ks->traj_params)
-    return fail(ASLR_E_INVALID, "%s: the handle has a per-trajectory parameter table set (the refill overwrites region TRAJ_PARAMS: the table would be lost); clear it with aslr_set_trajectory_params(p, NULL, stream), or give its rows in pp", fn);
-  if (p->ref_path_set)
-    return fail(ASLR_E_INVALID, "%s: the handle has a reference path set (a pool problem would inherit its slot's path); clear it with aslr_set_reference_path(p, NULL, 0, 0, stream)", fn);
-  if (int rc = solver_unsupported(fn, p, sp->solver)) return rc;
+  if (int rc = pool_refusals(fn, p, sp, pool, "(the refill overwrites region TRAJ_PARAMS: the table would be lost); clear it with aslr_set_trajectory_params(p, NULL, stream), or give its rows in pp")) return rc;
   if (!pp->params_dev) return fail(ASLR_E_INVALID, "%s: params_dev is NULL while a parameter field is given (DEVICE scratch of [2 nj + 2 nu][P] doubles)", fn);
-  const KernelSet *tp_set = find_kernel_set(p->nj, p->dam, true), *plain_set = p->ks;
+  const KernelSet *tp_set = find_kernel_set(p->nj, p->dam, true);
   if (!tp_set) return fail(ASLR_E_INVALID, "%s: no per-trajectory-parameter kernels for (nj=%d, dam=%d)", fn, p->nj, p->dam);
   const aslr_traj_params_t tp{pp->stiffness, pp->motor_inertia, pp->u_lb, pp->u_ub};
   std::vector<double> h; // [rows][P]
   if (int rc = build_param_rows(fn, p, &tp, pool->P, &h)) return rc;
-
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int B = p->desc.B;
-  if (refill_every <= 0) refill_every = 4;
-  if (poll_every <= 0) poll_every = 4 * refill_every;
-  if (poll_every > sp->maxiter + refill_every) poll_every = sp->maxiter + refill_every; // (a short maxiter must still be polled)
   HIP_TRY(hipMemcpyAsync(pp->params_dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipStreamSynchronize(st)); // (h is pageable: the copy is staged, and the vector may die at any return below)
   PoolParamsDev pl;
@@ -1656,61 +1660,11 @@ int aslr_solve_pool_params(aslr_problem_t *p, const aslr_solver_params_t *sp, co
   pl.stat_f = pool->stat_f; pl.stat_i = pool->stat_i; pl.slot_problem = pool->slot_problem; pl.counters = pool->counters;
   pl.params = pp->params_dev;
   pl.traj_params = reinterpret_cast<double *>(region(p, ASLR_R_TRAJ_PARAMS));
-  // every slot starts idle; the first refill hands out the first B problems
-  HIP_TRY(hipMemsetAsync(pool->slot_problem, 0xFF, sizeof(int32_t) * B, st));
-  HIP_TRY(hipMemsetAsync(pool->counters, 0, sizeof(int32_t) * 2, st));
-  HIP_TRY(hipMemsetAsync(p->k.traj_i + (size_t)ASLR_TI_DONE * B, 0, sizeof(int32_t) * B, st));
-  double *save = reinterpret_cast<double *>(region(p, ASLR_R_POOL_SAVE)); // (the handle's own x0 / frame_ref, as aslr_solve_pool)
-  HIP_TRY(hipMemcpyAsync(save, p->k.x0, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st));
-  if (p->k.frame_ref) HIP_TRY(hipMemcpyAsync(save + (size_t)B * p->nx, p->k.frame_ref, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st));
-  // While the call runs the handle iterates with the kernels that read TRAJ_PARAMS.  The model-only record chunks in place
-  // belong to the models' constants: the mark is cleared, so the first sweep that covers every slot sets it again.
-  p->ks = tp_set;
-  p->const_written = false;
-  IterOpts o{p->k, sp->maxiter, pool->P >= B, nullptr};
-  o.k.iter_log = nullptr; o.k.log_cap = 0; // (a slot's iteration index restarts with every problem)
-  if (pool->frame_ref) o.k.planar_reach = 0; // (pool targets take the general log map)
   // Every round starts with a refill, and a refilled slot may hold another design than before: the round's first sweep
   // writes every record chunk of the trajectories it evaluates (a refilled slot has RECALC set and DONE clear, so
   // calc_kernel passes each of its knots through the store path without SKIPC; the sweeps in between keep the skip)
-  o.fresh_first = true;
-  const auto refill = [&]() { return launch_pool_refill_params(o.k, pl, reg_start(sp), sp->is_feasible, st); };
-  const auto flush_and_count = [&](int32_t *fin) -> int {
-    if (int rc = refill()) return rc;
-    HIP_TRY(hipMemcpyAsync(p->h_done, pl.counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *fin = p->h_done[0];
-    return ASLR_OK;
-  };
-  int it = 0, rc = ASLR_OK;
-  const long long cap = ((long long)(pool->P + B - 1) / B + 1) * (long long)(sp->maxiter + refill_every);
-  while (it < cap) {
-    rc = refill();
-    if (!rc) rc = iterate(p, sp, false, refill_every, st, o);
-    if (rc) break;
-    o.full_first = false; // (later rounds evaluate the refilled slots only)
-    it += refill_every;
-    if (it % poll_every < refill_every) {
-      int32_t fin = 0;
-      rc = flush_and_count(&fin);
-      if (rc || fin >= pool->P) break;
-    }
-  }
-  int32_t fin_total = -1;
-  if (!rc) rc = flush_and_count(&fin_total);
-  {
-    hipError_t e = hipMemcpyAsync(const_cast<double *>(p->k.x0), save, sizeof(double) * B * p->nx, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && p->k.frame_ref) e = hipMemcpyAsync(const_cast<double *>(p->k.frame_ref), save + (size_t)B * p->nx, sizeof(double) * B * 12, hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess && !rc) rc = fail(ASLR_E_HIP, "%s: putting the handle's x0 / frame_ref back failed: %s", fn, hipGetErrorString(e));
-  }
-  // back on the models' constants; the record chunks in place belong to the last designs of the slots: the next sweep of
-  // the handle rewrites them (as after aslr_set_trajectory_params)
-  p->ks = plain_set;
-  p->const_written = false;
-  if (iters_done) *iters_done = it;
-  if (rc) return rc;
-  if (fin_total < pool->P) return fail(ASLR_E_INVALID, "%s: %d of %d problems finished within the iteration bound", fn, fin_total, pool->P);
-  return launch_reset_accepted(p->k, st);
+  return pool_run(fn, p, sp, pool, refill_every, poll_every, st, iters_done, tp_set, true,
+                  [&](const KArgs &k) { return launch_pool_refill_params(k, pl, reg_start(sp), sp->is_feasible, st); });
 }
 
 int aslr_dam_eval(aslr_problem_t *p, int32_t model_index, int32_t n, const double *x, const double *u, double *xout,

@@ -18,6 +18,11 @@ def _torch():
     return torch
 
 
+def _ptr(t):
+    """A device tensor as the C ABI takes it: its address, NULL for None."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 class MpcResult(object):
     """What Engine.mpc_run returns: batch-major device tensors, views of the time-major arrays the kernels wrote --
     xs_closed [B, n+1, nx], us_closed [B, n, nu_user], and per step's solve iters, status (int32), cost, stop, x_reg,
@@ -154,6 +159,24 @@ class Engine(object):
     def _stream(self):
         torch = _torch()
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _f64(self, v):
+        """v (array, tensor or None) as a float64 tensor on this engine's device; None stays None."""
+        if v is None:
+            return None
+        torch = _torch()
+        return torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
+                               device=self.device)
+
+    def _dev(self, v, shape, perm, name, message=None):
+        """_f64(v), checked against the batch-major `shape`, permuted to the library's layout and made contiguous.
+        message: the ValueError text, where a caller has its own."""
+        if v is None:
+            return None
+        t = self._f64(v)
+        if tuple(t.shape) != shape:
+            raise ValueError(message or "%s must have shape %s, not %s" % (name, list(shape), list(t.shape)))
+        return t.permute(*perm).contiguous()
 
     def _call(self, name, *args):
         """One C-ABI call with this engine's device current (the ABI launches on the thread's current device, on a
@@ -338,8 +361,7 @@ class Engine(object):
         with torch.cuda.device(self.device):
             new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
             dk, db, dx0, lam = (None if vsa else new(nj, self.B)), new(nj, self.B), new(self.nx, self.B), new(self.T + 1, self.B, self.nx)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._call("aslr_cost_sensitivity", ptr(dk), ptr(db), ptr(dx0), ptr(lam), self._stream())
+        self._call("aslr_cost_sensitivity", _ptr(dk), _ptr(db), _ptr(dx0), _ptr(lam), self._stream())
         return SensitivityResult(stiffness=None if dk is None else dk.t(), motor_inertia=db.t(), x0=dx0.t(),
                                  costate=lam.permute(1, 0, 2))
 
@@ -355,21 +377,11 @@ class Engine(object):
         lives on the device) and shows up in failed_knot."""
         torch = _torch()
         S, B, T, nx, nu, nj = int(n_samples), self.B, self.T, self.nx, self.nu, self.nx // 4
-
-        def dev(v, shape, perm, name):
-            if v is None:
-                return None
-            t = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
-                                device=self.device)
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, not %s" % (name, list(shape), list(t.shape)))
-            return t.permute(*perm).contiguous()
-
         if S > 0:  # (S <= 0: the library refuses by name)
-            pk = dev(plant_stiffness, (B, S, nj), (2, 1, 0), "plant_stiffness")
-            pb = dev(plant_motor_inertia, (B, S, nj), (2, 1, 0), "plant_motor_inertia")
-            d0 = dev(dx0, (B, S, nx), (1, 0, 2), "dx0")
-            w = dev(disturbance, (B, S, T, nx), (1, 2, 0, 3), "disturbance")
+            pk = self._dev(plant_stiffness, (B, S, nj), (2, 1, 0), "plant_stiffness")
+            pb = self._dev(plant_motor_inertia, (B, S, nj), (2, 1, 0), "plant_motor_inertia")
+            d0 = self._dev(dx0, (B, S, nx), (1, 0, 2), "dx0")
+            w = self._dev(disturbance, (B, S, T, nx), (1, 2, 0, 3), "disturbance")
         else:
             pk = pb = d0 = w = None
         n = max(S, 0)
@@ -378,10 +390,9 @@ class Engine(object):
             cost, failed, xf = new(torch.float64, n, B), new(torch.int32, n, B), new(torch.float64, n, B, nx)
             xs = new(torch.float64, n, T + 1, B, nx) if keep_trajectories else None
             us = new(torch.float64, n, T, B, nu) if keep_trajectories else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         # (2 joints: the entry point that has always served them; every other size: the one that serves all sizes)
-        self._call("aslr_policy_rollout" if nj == 2 else "aslr_policy_rollout_all", S, ptr(pk), ptr(pb), ptr(d0), ptr(w), 1 if clamp else 0, ptr(cost), ptr(failed),
-                   ptr(xf), ptr(xs), ptr(us), self._stream())
+        self._call("aslr_policy_rollout" if nj == 2 else "aslr_policy_rollout_all", S, _ptr(pk), _ptr(pb), _ptr(d0), _ptr(w), 1 if clamp else 0, _ptr(cost), _ptr(failed),
+                   _ptr(xf), _ptr(xs), _ptr(us), self._stream())
         return PolicyRolloutResult(cost=cost.t(), failed_knot=failed.t(), x_final=xf.permute(1, 0, 2),
                                    xs=None if xs is None else xs.permute(2, 0, 1, 3),
                                    us=None if us is None else self.cut_u(us.permute(2, 0, 1, 3)))
@@ -395,15 +406,8 @@ class Engine(object):
         any backward sweep K = 0 and the result is the open-loop covariance; the control box is not applied."""
         torch = _torch()
         B, T, nx, nu = self.B, self.T, self.nx, self.nu
-
-        def dev(v, name):
-            if v is None:
-                return None
-            return torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
-                                   device=self.device)
-
         with torch.cuda.device(self.device):
-            s0, w = dev(sigma0, "sigma0"), dev(noise_var, "noise_var")
+            s0, w = self._f64(sigma0), self._f64(noise_var)
             if s0 is not None:
                 if s0.dim() == 2:
                     s0 = s0.unsqueeze(0).expand(B, -1, -1)
@@ -428,8 +432,7 @@ class Engine(object):
             new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
             xv, uv, cf, ci = new(T + 1, B, nx), new(T, B, nu), new(B, nx, nx), new(B)
             cov = new(T + 1, B, nx, nx) if keep_cov else None
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._call("aslr_policy_covariance", ptr(s0), ptr(w), ptr(xv), ptr(uv), ptr(cf), ptr(cov), ptr(ci), self._stream())
+        self._call("aslr_policy_covariance", _ptr(s0), _ptr(w), _ptr(xv), _ptr(uv), _ptr(cf), _ptr(cov), _ptr(ci), self._stream())
         torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
         return PolicyCovarianceResult(x_var=xv.permute(1, 0, 2), u_var=self.cut_u(uv.permute(1, 0, 2)), cov_final=cf,
                                       cost_increase=ci, cov=None if cov is None else cov.permute(1, 0, 2, 3))
@@ -451,8 +454,7 @@ class Engine(object):
         def var(v, name):
             if v is None:
                 return None
-            v = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
-                                device=self.device)
+            v = self._f64(v)
             if v.dim() == 1:
                 v = v.unsqueeze(0).expand(B, -1)
             if tuple(v.shape) != (B, nj):
@@ -468,9 +470,8 @@ class Engine(object):
             (fk, fb), (ck, cb) = both(B, nx, nj), both(nj, B)
             tk, tb = both(T + 1, B, nx, nj) if keep_trajectories else (None, None)
             xv, uv = (new(T + 1, B, nx), new(T, B, nu)) if (vk is not None or vb is not None) else (None, None)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        self._call("aslr_policy_plant_sensitivity", ptr(vk), ptr(vb), ptr(tk), ptr(tb), ptr(fk), ptr(fb), ptr(ck), ptr(cb),
-                   ptr(xv), ptr(uv), self._stream())
+        self._call("aslr_policy_plant_sensitivity", _ptr(vk), _ptr(vb), _ptr(tk), _ptr(tb), _ptr(fk), _ptr(fb), _ptr(ck), _ptr(cb),
+                   _ptr(xv), _ptr(uv), self._stream())
         torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
         bm = lambda t, *perm: None if t is None else t.permute(*perm)
         return PlantSensitivityResult(dx_final_dstiffness=fk, dx_final_dmotor_inertia=fb, dcost_dstiffness=bm(ck, 1, 0),
@@ -575,6 +576,7 @@ class Engine(object):
         it = C.c_int32(0)
         low = self.low
         tp = lower_traj_params(low.desc, low.nj, low.nu, self.nu_user, low.dam, stiffness, motor_inertia, u_lb, u_ub, rows=P)
+        more = {}
         if tp is not None:
             with torch.cuda.device(self.device):
                 params = torch.empty((2 * low.nj + 2 * low.nu, P), dtype=torch.float64, device=self.device)
@@ -584,14 +586,13 @@ class Engine(object):
             pp.params_dev = params.data_ptr()
             self._call("aslr_solve_pool_params", C.byref(sp), C.byref(pool), C.byref(pp), int(refill_every), int(poll_every),
                        self._stream(), C.byref(it))
-            torch.cuda.synchronize(self.device)
-            return dict(xs=xs, us=self.cut_u(us), cost=sf[:, 0], stop=sf[:, 1], x_reg=sf[:, 2], step=sf[:, 3], iters=si[:, 0],
-                        status=si[:, 1], batch_iters=it.value, params=params)
-        self._call("aslr_solve_pool", C.byref(sp), C.byref(pool), int(refill_every), int(poll_every), self._stream(),
-                   C.byref(it))
+            more = dict(params=params)
+        else:
+            self._call("aslr_solve_pool", C.byref(sp), C.byref(pool), int(refill_every), int(poll_every), self._stream(),
+                       C.byref(it))
         torch.cuda.synchronize(self.device)
         return dict(xs=xs, us=self.cut_u(us), cost=sf[:, 0], stop=sf[:, 1], x_reg=sf[:, 2], step=sf[:, 3], iters=si[:, 0],
-                    status=si[:, 1], batch_iters=it.value)
+                    status=si[:, 1], batch_iters=it.value, **more)
 
     def mpc_run(self, sp, n_steps, first_maxiter, iters_per_step, disturbance=None):
         """A receding-horizon run on the device (aslr_mpc_run): step 0 solves first_maxiter iterations from the candidate
@@ -604,26 +605,35 @@ class Engine(object):
         torch = _torch()
         n = int(n_steps)
         with torch.cuda.device(self.device):
-            dist = None
-            if disturbance is not None:
-                d = torch.as_tensor(disturbance, dtype=torch.float64, device=self.device)
-                if tuple(d.shape) != (self.B, n, self.nx):
-                    raise ValueError("disturbance must have shape [B=%d, n_steps=%d, nx=%d]" % (self.B, n, self.nx))
-                dist = d.permute(1, 0, 2).contiguous()
-            m = max(n, 0)
-            xc = torch.zeros((m + 1, self.B, self.nx), dtype=torch.float64, device=self.device)
-            uc = torch.zeros((m, self.B, self.nu), dtype=torch.float64, device=self.device)
+            dist = self._dev(disturbance, (self.B, n, self.nx), (1, 0, 2), "disturbance",
+                             "disturbance must have shape [B=%d, n_steps=%d, nx=%d]" % (self.B, n, self.nx))
+        mpc, bufs = self._mpc_block(n, max(n, 0), first_maxiter, iters_per_step, dist)
+        self._call("aslr_mpc_run", C.byref(sp), C.byref(mpc), self._stream())
+        torch.cuda.synchronize(self.device)  # (the time-major disturbance copy dies on return)
+        return self._mpc_result(bufs)
+
+    def _mpc_block(self, n, N, first_maxiter, iters_per_step, dist):
+        """The aslr_mpc_t of a run of n control steps that apply N knots in all, and the four zeroed time-major buffers it
+        points to (x_closed, u_closed, stat_f, stat_i); dist: the time-major disturbance, or None."""
+        torch = _torch()
+        m = max(n, 0)
+        with torch.cuda.device(self.device):
+            xc = torch.zeros((N + 1, self.B, self.nx), dtype=torch.float64, device=self.device)
+            uc = torch.zeros((N, self.B, self.nu), dtype=torch.float64, device=self.device)
             sf = torch.zeros((m, 4, self.B), dtype=torch.float64, device=self.device)
             si = torch.zeros((m, 2, self.B), dtype=torch.int32, device=self.device)
         mpc = _abi.Mpc()
         mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, int(first_maxiter), int(iters_per_step)
         mpc.disturbance = dist.data_ptr() if dist is not None else None
         mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = xc.data_ptr(), uc.data_ptr(), sf.data_ptr(), si.data_ptr()
-        self._call("aslr_mpc_run", C.byref(sp), C.byref(mpc), self._stream())
-        torch.cuda.synchronize(self.device)  # (the time-major disturbance copy dies on return)
+        return mpc, (xc, uc, sf, si)
+
+    def _mpc_result(self, bufs, **more):
+        """The MpcResult of the buffers _mpc_block made, once the run is complete; more: the fields of mpc_run_plant."""
+        xc, uc, sf, si = bufs
         return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
                          status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t(),
-                         reference_row=self.reference_row)
+                         reference_row=self.reference_row, **more)
 
     def mpc_run_plant(self, sp, n_steps, first_maxiter, iters_per_step, hold=1, plant_stiffness=None, plant_motor_inertia=None,
                       disturbance=None, clamp=False, closed_cost=True):
@@ -640,39 +650,18 @@ class Engine(object):
         torch = _torch()
         n, h, nj = int(n_steps), int(hold), self.nx // 4
         N = max(n, 0) * max(h, 0)
-
-        def dev(v, shape, perm, name):
-            if v is None:
-                return None
-            t = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
-                                device=self.device)
-            if tuple(t.shape) != shape:
-                raise ValueError("%s must have shape %s, not %s" % (name, list(shape), list(t.shape)))
-            return t.permute(*perm).contiguous()
-
         with torch.cuda.device(self.device):
-            pk = dev(plant_stiffness, (self.B, nj), (1, 0), "plant_stiffness")
-            pb = dev(plant_motor_inertia, (self.B, nj), (1, 0), "plant_motor_inertia")
-            dist = dev(disturbance, (self.B, N, self.nx), (1, 0, 2), "disturbance")
-            m = max(n, 0)
-            xc = torch.zeros((N + 1, self.B, self.nx), dtype=torch.float64, device=self.device)
-            uc = torch.zeros((N, self.B, self.nu), dtype=torch.float64, device=self.device)
-            sf = torch.zeros((m, 4, self.B), dtype=torch.float64, device=self.device)
-            si = torch.zeros((m, 2, self.B), dtype=torch.int32, device=self.device)
+            pk = self._dev(plant_stiffness, (self.B, nj), (1, 0), "plant_stiffness")
+            pb = self._dev(plant_motor_inertia, (self.B, nj), (1, 0), "plant_motor_inertia")
+            dist = self._dev(disturbance, (self.B, N, self.nx), (1, 0, 2), "disturbance")
             cc = torch.zeros((self.B,), dtype=torch.float64, device=self.device) if closed_cost else None
             fk = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
-        mpc = _abi.Mpc()
-        mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, int(first_maxiter), int(iters_per_step)
-        mpc.disturbance = dist.data_ptr() if dist is not None else None
-        mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = xc.data_ptr(), uc.data_ptr(), sf.data_ptr(), si.data_ptr()
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        mpc, bufs = self._mpc_block(n, N, first_maxiter, iters_per_step, dist)
         # (2 joints: the entry point that has always served them; every other size: the one that serves all sizes)
-        self._call("aslr_mpc_run_plant" if nj == 2 else "aslr_mpc_run_plant_all", C.byref(sp), C.byref(mpc), h, ptr(pk), ptr(pb),
-                   1 if clamp else 0, ptr(cc), ptr(fk), self._stream())
+        self._call("aslr_mpc_run_plant" if nj == 2 else "aslr_mpc_run_plant_all", C.byref(sp), C.byref(mpc), h, _ptr(pk), _ptr(pb),
+                   1 if clamp else 0, _ptr(cc), _ptr(fk), self._stream())
         torch.cuda.synchronize(self.device)  # (the time-major copies of the inputs die on return)
-        return MpcResult(xs_closed=xc.permute(1, 0, 2), us_closed=self.cut_u(uc.permute(1, 0, 2)), iters=si[:, 0].t(),
-                         status=si[:, 1].t(), cost=sf[:, 0].t(), stop=sf[:, 1].t(), x_reg=sf[:, 2].t(), step=sf[:, 3].t(),
-                         reference_row=self.reference_row, closed_cost=cc, failed_knot=fk, hold=h)
+        return self._mpc_result(bufs, closed_cost=cc, failed_knot=fk, hold=h)
 
     def design_descent(self, sp, n_steps, first_maxiter, iters_per_step, stiffness_bounds=None, motor_inertia_bounds=None,
                        eta0=0.05, grow=2.0, shrink=0.5, c1=1e-4, max_rel=0.25, keep_history=False):
@@ -718,15 +707,14 @@ class Engine(object):
             hf = new(f64, m, 3, B) if keep_history else None
             hi_ = new(torch.int32, m, B) if keep_history else None
             th = new(f64, m, 2 * nj, B) if keep_history else None
-        ptr = lambda t: None if t is None else t.data_ptr()
         d = _abi.Design()
         d.n_steps, d.first_maxiter, d.iters_per_step = n, int(first_maxiter), int(iters_per_step)
         d.opt_stiffness, d.opt_motor_inertia = int(stiffness_bounds is not None), int(motor_inertia_bounds is not None)
         d.eta0, d.grow, d.shrink, d.c1, d.max_rel = float(eta0), float(grow), float(shrink), float(c1), float(max_rel)
-        d.lo, d.hi = ptr(lo), ptr(hi)
-        d.theta_best, d.cost_best, d.xs_best, d.us_best = ptr(theta), ptr(cost), ptr(xb), ptr(ub)
-        d.hist_f, d.hist_i, d.theta_hist = ptr(hf), ptr(hi_), ptr(th)
-        d.g_acc, d.eta, d.grad = ptr(gacc), ptr(eta), ptr(grad)
+        d.lo, d.hi = _ptr(lo), _ptr(hi)
+        d.theta_best, d.cost_best, d.xs_best, d.us_best = _ptr(theta), _ptr(cost), _ptr(xb), _ptr(ub)
+        d.hist_f, d.hist_i, d.theta_hist = _ptr(hf), _ptr(hi_), _ptr(th)
+        d.g_acc, d.eta, d.grad = _ptr(gacc), _ptr(eta), _ptr(grad)
         self._call("aslr_design_descent", C.byref(sp), C.byref(d), self._stream())
         torch.cuda.synchronize(self.device)  # (the scratch tensors die on return)
         vsa = self.low.dam == _abi.DAM_VSA
