@@ -10,12 +10,13 @@
 //                   column c of dtau/dq, then column c of dtau/dv (tangent sweeps with a runtime direction);
 //   lane  NJ      : the nonlinear effects.
 //
+// Phase 0's M columns, M^-1 column and accelerations are TeamStep's (aslr_team_step.hpp), the step the team rollouts take.
 // Intermediates shared by the team (joint rotations, M, M^-1, the kept sweep) live in LDS.  The results --
 // [xout (2 nj) | M^-1 | the link rows of da_dx = M^-1 [-dtau/dq - K | K | -dtau/dv]] per knot, region DYN (layout:
 // dyn_len_c) -- are consumed by calc_kernel<..., PRE>, which then only does the cost stack and the record assembly and
 // reads each da_dx entry where a record line needs it (nothing of the 3 nj^2 block is held in registers).
 #pragma once
-#include "aslr_forward_team.inc.hpp"
+#include "aslr_team_step.hpp"
 
 namespace aslr {
 
@@ -175,9 +176,8 @@ __global__ void __launch_bounds__(64) dyn_team_kernel(KArgs a, int mode) {
   double Krow[NJ], Srow[NJ], Brow[NJ];
   double k_cj = 0.0; // TP: K[cj][cj] of this trajectory
   if constexpr (TP) {
-    const double *tp = traj_params_at(D, b);
-    k_cj = tp[(size_t)cj * B];
-    const double b_cj = tp[(size_t)(NJ + cj) * B];
+    double b_cj;
+    team_table_row<NJ>(traj_params_at(D, b), cj, B, k_cj, b_cj);
     ASLR_UNROLL for (int j = 0; j < NJ; ++j) { Krow[j] = (j == cj) ? k_cj : 0.0; Srow[j] = dm.m.S[cj * NU + j]; Brow[j] = (j == cj) ? b_cj : 0.0; }
   } else {
     ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
@@ -195,38 +195,16 @@ __global__ void __launch_bounds__(64) dyn_team_kernel(KArgs a, int mode) {
   wave_sync();
   double *out = a.dyn + tb * DL;
   if constexpr (PHASE == 0) {
-    const V3 g = v3(chc->gravity);
-    // ---- M columns and nonlinear effects: one RNEA per lane ----
-    {
-      double vv[NJ], aa[NJ], tau[NJ];
-      const bool nl = c == NJ;
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i) { vv[i] = nl ? xT[2 * NJ + i] : 0.0; aa[i] = (!nl && i == c) ? 1.0 : 0.0; }
-      rnea_lds<NJ>(chc, RL, vv, aa, nl ? g : V3{0.0, 0.0, 0.0}, tau);
-      if (c <= NJ) { ASLR_UNROLL for (int i = 0; i < NJ; ++i) ML[8 * c + i] = tau[i]; }
-    }
+    // ---- M columns and nonlinear effects (one RNEA per lane), column cj of M^-1, accelerations, entry cj ----
+    static_assert(C::NU == NJ, "SEA actuation: this kernel forms its torques itself, TeamStep's VSA branch is never taken");
+    const TeamStep<NJ, false, C> ts(tm_, c);
+    ts.mass_columns(chc);
     wave_sync();
-    // ---- column cj of M^-1 ----
-    {
-      double Ms[NJ][NJ], e[NJ];
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i)
-        ASLR_UNROLL for (int j = 0; j <= i; ++j) {
-          Ms[i][j] = (i == j) ? ML[8 * j + i] : 0.5 * (ML[8 * j + i] + ML[8 * i + j]);
-          Ms[j][i] = Ms[i][j];
-        }
-      spd_inverse_col<NJ>(Ms, cj, e);
-      if (jl) {
-        ASLR_UNROLL for (int i = 0; i < NJ; ++i) MiL[8 * c + i] = e[i];
-        if (compute) { ASLR_UNROLL for (int i = 0; i < NJ; ++i) out[2 * NJ + i * NJ + c] = e[i]; } // Minv[i][c]
-      }
-    }
+    ts.template minv_column<true>(out + 2 * NJ + c, NJ, compute); // Minv[i][c]
     wave_sync();
-    // ---- accelerations, entry cj ----
     {
-      double al = 0.0, am = 0.0;
-      ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
-        al += MiL[8 * j + cj] * (-ML[8 * NJ + j] - tcL[j]);
-        am += Brow[j] * (tmL[j] + tcL[j]);
-      }
+      double al, am;
+      ts.accelerations(Brow, al, am);
       if (jl && compute) { out[c] = al; out[NJ + c] = am; }
     }
   } else {

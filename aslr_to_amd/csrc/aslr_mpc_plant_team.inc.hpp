@@ -1,12 +1,11 @@
 // aslr_mpc_plant_team.inc.hpp -- the plant phase of a receding-horizon run on a mismatched plant for the larger chain
 // (7-DoF SEA / VSA): aslr_mpc_run_plant_all, include/aslr_to_amd_mpc_plant_all.h, DESIGN.md 4.18.
 //
-//   mpc_plant_team_kernel   A TEAM OF 8 LANES PER TRAJECTORY, with the lane roles of policy_rollout_team_kernel
-//                           (aslr_policy_team.inc.hpp): lane c < NJ owns row c of the control law (rows c and NJ + c for
-//                           VSA), joint c's rotation, column c of M and of M^-1 and entry c of the Euler step; lane NJ owns
-//                           the nonlinear effects.  The definition is mpc_plant_kernel's (aslr_mpc_plant.inc.hpp): `hold`
-//                           knots of the plan in XS / US / KGAIN applied to the trajectory's own plant.  What differs from
-//                           the policy kernel:
+//   mpc_plant_team_kernel   A TEAM OF 8 LANES PER TRAJECTORY.  The plant step is TeamStep's (aslr_team_step.hpp); on top
+//                           of it lane c < NJ owns row c of the control law (rows c and NJ + c for VSA).  The definition is
+//                           mpc_plant_kernel's (aslr_mpc_plant.inc.hpp): `hold` knots of the plan in XS / US / KGAIN applied
+//                           to the trajectory's own plant.  What is this kernel's own, against policy_rollout_team_kernel
+//                           (aslr_policy_team.inc.hpp):
 //     - there is ONE plant per trajectory, so the eight teams of a wave are eight trajectories and share nothing: no
 //       per-wave stage.  A block is one wave; the grid is over ceil(B / 8) waves;
 //     - every team reads [K_j | xs_j | us_j] of ITS trajectory straight from KGAIN / XS / US, one knot ahead: lane c its
@@ -19,7 +18,7 @@
 //     - the sums of a run continue over its control steps in place (pa.first), there is no terminal cost;
 //     - it writes nothing but the caller's buffers.
 #pragma once
-#include "aslr_forward_team.inc.hpp"
+#include "aslr_team_step.hpp"
 
 namespace aslr {
 
@@ -40,21 +39,17 @@ __global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits
   const int bq = blockIdx.x * TPB + team, b = bq < B ? bq : B - 1;
   const bool on = bq < B;
   double *tm_ = sm + team * TEAM;
-  double *xT = tm_ + C::tX, *uT = tm_ + C::tU, *tcL = tm_ + C::tTc, *tmL = tm_ + C::tTm, *RL = tm_ + C::tR,
-         *ML = tm_ + C::tM, *MiL = tm_ + C::tMi, *xrT = tm_ + tXr, *frT = tm_ + tFr;
-  const bool jl = c < NJ; // this lane owns joint / row cj
-  const int cj = jl ? c : NJ - 1;
+  const TeamStep<NJ, VSA, C> ts(tm_, c);
+  double *const xT = ts.xT, *const uT = ts.uT, *xrT = tm_ + tXr, *frT = tm_ + tFr;
+  const bool jl = ts.jl; // this lane owns joint / row cj
+  const int cj = ts.cj;
   const DevDesc &D = *a.desc;
   const aslr_chain_t &ch = D.chain;
   const chain_cp chc = chain_const(&D.chain);
   const unsigned long long team_bits = 0xffull << (team * 8);
 
-  // joint placements and axes: constants of the chain, staged once in LDS (rollout_team_kernel says why)
   __shared__ double jtab[8][12];
-  if (lane < NJ) {
-    ASLR_UNROLL for (int k = 0; k < 9; ++k) jtab[lane][k] = ch.joint_R[lane][k];
-    ASLR_UNROLL for (int k = 0; k < 3; ++k) jtab[lane][9 + k] = ch.axis[lane][k];
-  }
+  stage_joint_table<NJ>(jtab, ch, lane); // (fenced by the wave_sync at the top of knot 0)
 
   // ---- the model of every applied knot, and the plant of this team, entry cj: the caller's arrays [nj][B] where given,
   // else the trajectory's row of the parameter table where one is set, else the row of the model ----
@@ -63,6 +58,7 @@ __global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits
   const bool table = pa.table != 0, use_k = pa.plant_stiffness || table, use_b = pa.plant_motor_inertia || table;
   double k_cj = 0.0, b_cj = 0.0, lb_c = 0.0, ub_c = 0.0, lb_s = 0.0, ub_s = 0.0; // (lb_s / ub_s: the stiffness row, VSA)
   if (table) {
+    // (team_table_row's text: through the helper this kernel alone issues each of these loads twice)
     const double *tp = traj_params_at(D, b);
     k_cj = tp[(size_t)cj * B];
     b_cj = tp[(size_t)(NJ + cj) * B];
@@ -77,15 +73,7 @@ __global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits
   if (pa.plant_stiffness) k_cj = pa.plant_stiffness[(size_t)cj * B + b];
   if (pa.plant_motor_inertia) b_cj = 1.0 / pa.plant_motor_inertia[(size_t)cj * B + b];
   double Krow[NJ], Srow[NJ], Brow[NJ];
-  ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
-    Krow[j] = 0.0; Srow[j] = 0.0;
-    if (!VSA) {
-      // (pa.diagonal is the host's fact: a plant array or a table, both of which need diagonal models)
-      Krow[j] = pa.diagonal ? ((j == cj) ? (use_k ? k_cj : dm.m.K[cj * NJ + cj]) : 0.0) : dm.m.K[cj * NJ + j];
-      Srow[j] = dm.m.S[cj * NU + j];
-    }
-    Brow[j] = pa.diagonal ? ((j == cj) ? (use_b ? b_cj : dm.Binv[cj * NJ + cj]) : 0.0) : dm.Binv[cj * NJ + j];
-  }
+  team_model_rows<NJ, NU, VSA>(dm, cj, pa.diagonal, use_k, k_cj, use_b, b_cj, Krow, Srow, Brow);
   const double dt = dm.m.dt;
   const bool clamp = pa.clamp && lim.has[mi];
 
@@ -134,11 +122,7 @@ __global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits
   };
   double *x_o = pa.x_rec + (size_t)b * NX + 4 * cj, *u_o = pa.u_rec + (size_t)b * NU; // knot j at + j B NX / + j B NU
   auto store_x = [&](int j) { // the team's state as row j of this step's records, 4 contiguous entries per lane
-    if (on && jl) {
-      double *o = x_o + (size_t)j * B * NX;
-      *reinterpret_cast<double2 *>(o) = make_double2(xT[4 * c], xT[4 * c + 1]);
-      *reinterpret_cast<double2 *>(o + 2) = make_double2(xT[4 * c + 2], xT[4 * c + 3]);
-    }
+    if (on && jl) team_store_state_row(x_o + (size_t)j * B * NX, xT, c);
   };
   const typename Chain3D<NJ>::Consts cc(D, true);
   ModelRegs<NJ, NU> mr; // (the cost stack reads none of it)
@@ -195,70 +179,28 @@ __global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits
       u_o[(size_t)j * B * NU + c] = u_c;
       if constexpr (VSA) u_o[(size_t)j * B * NU + NJ + c] = u_s;
     }
-    // ---- rotation of joint cj ----
-    if (jl) {
-      const M3 R = mul(m3(jtab[cj]), axis_angle(v3(jtab[cj] + 9), xT[cj]));
-      ASLR_UNROLL for (int k = 0; k < 9; ++k) RL[9 * c + k] = R.a[k];
-    }
+    // ---- the plant step (aslr_team_step.hpp) ----
+    ts.rotation(jtab);
     wave_sync();
-    // ---- coupling and motor torques, entry cj ----
-    if (jl) {
-      double sc_ = 0.0, s2 = 0.0;
-      if constexpr (VSA) { // K = diag(stiffness commands), tau_m = the torque commands
-        ASLR_UNROLL for (int i = 0; i < NJ; ++i) sc_ += (i == c ? uT[NJ + c] : 0.0) * (xT[i] - xT[NJ + i]);
-        s2 = uT[c];
-      } else {
-        ASLR_UNROLL for (int i = 0; i < NJ; ++i) { sc_ += Krow[i] * (xT[i] - xT[NJ + i]); s2 += Srow[i] * uT[i]; }
-      }
-      tcL[c] = sc_;
-      tmL[c] = s2;
-    }
-    // ---- one RNEA per lane: column c of M (lanes c < NJ), nonlinear effects (lane NJ) ----
-    if (c <= NJ) {
-      double vv[NJ], aa[NJ], tau[NJ];
-      const bool nl = c == NJ;
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i) { vv[i] = nl ? xT[2 * NJ + i] : 0.0; aa[i] = (!nl && i == c) ? 1.0 : 0.0; }
-      const V3 g = v3(chc->gravity);
-      const V3 grav = nl ? g : V3{0.0, 0.0, 0.0};
-      rnea_lds<NJ>(chc, RL, vv, aa, grav, tau);
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i) ML[8 * c + i] = tau[i];
-    }
+    ts.torques(Krow, Srow);
+    ts.mass_columns(chc);
     wave_sync();
     // the row(s) of K and the entries of xs of the knot ahead: 28 / 56 doubles per lane, issued behind the RNEA -- the
     // register peak of the knot, where they would be spilled to the private segment -- and in flight over the inverse, the
     // accelerations and the Euler step
     prefetch_gains(jn);
-    // ---- column cj of M^-1 (M symmetrised like Chain3D::mass) ----
-    {
-      double Ms[NJ][NJ], e[NJ];
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i)
-        ASLR_UNROLL for (int k = 0; k <= i; ++k) {
-          Ms[i][k] = (i == k) ? ML[8 * k + i] : 0.5 * (ML[8 * k + i] + ML[8 * i + k]);
-          Ms[k][i] = Ms[i][k];
-        }
-      spd_inverse_col<NJ>(Ms, cj, e);
-      if (jl) { ASLR_UNROLL for (int i = 0; i < NJ; ++i) MiL[8 * c + i] = e[i]; }
-    }
+    ts.minv_column();
     wave_sync();
-    // ---- accelerations and semi-implicit Euler, entries cj of q_l, q_m, v_l, v_m ----
-    double al = 0.0, am = 0.0;
-    ASLR_UNROLL for (int i = 0; i < NJ; ++i) {
-      al += MiL[8 * i + cj] * (-ML[8 * NJ + i] - tcL[i]);
-      am += Brow[i] * (tmL[i] + tcL[i]);
-    }
-    const double ql = xT[cj], qm = xT[NJ + cj], vl = xT[2 * NJ + cj], vm = xT[3 * NJ + cj];
-    const double nql = ql + (vl * dt + al * dt * dt), nvl = vl + al * dt;
-    const double nqm = qm + (vm * dt + am * dt * dt), nvm = vm + am * dt;
-    const double nxt[4] = {nql, nvl, nqm, nvm}; // this lane's entries of xnext: |xnext|_inf test, entry by entry
-    const bool bad = jl && inf_norm_bad<4>(fabs(nql) + fabs(nvl) + fabs(nqm) + fabs(nvm), nxt);
+    double nxt[4]; // this lane's entries {q_l, v_l, q_m, v_m} of xnext
+    const bool bad = ts.euler(Brow, dt, nxt);
     if (__ballot(bad) & team_bits) { // NaN / Inf / |xnext|_inf >= 1e30, as the solver's rollout
       failed_here = true;
       if (failed < 0) failed = pa.k0 + j;
     }
     wave_sync(); // every lane of the team has read the old state
     if (jl) {
-      if (wsrc) { xT[c] = nql + w[0]; xT[NJ + c] = nqm + w[1]; xT[2 * NJ + c] = nvl + w[2]; xT[3 * NJ + c] = nvm + w[3]; }
-      else { xT[c] = nql; xT[NJ + c] = nqm; xT[2 * NJ + c] = nvl; xT[3 * NJ + c] = nvm; }
+      if (wsrc) { xT[c] = nxt[0] + w[0]; xT[NJ + c] = nxt[2] + w[1]; xT[2 * NJ + c] = nxt[1] + w[2]; xT[3 * NJ + c] = nxt[3] + w[3]; }
+      else { xT[c] = nxt[0]; xT[NJ + c] = nxt[2]; xT[2 * NJ + c] = nxt[1]; xT[3 * NJ + c] = nxt[3]; }
     }
   }
   wave_sync(); // the state behind the last applied knot is written

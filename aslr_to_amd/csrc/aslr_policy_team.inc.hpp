@@ -1,10 +1,9 @@
 // aslr_policy_team.inc.hpp -- closed-loop roll-outs of the stored policy on a perturbed plant for the larger chain
 // (7-DoF SEA / VSA): aslr_policy_rollout_all, include/aslr_to_amd_policy_all.h, DESIGN.md 4.17.
 //
-//   policy_rollout_team_kernel   A TEAM OF 8 LANES PER (trajectory, SAMPLE), with the lane roles of rollout_team_kernel
-//                                (aslr_forward_team.inc.hpp): lane c < NJ owns row c of the control law (rows c and NJ + c
-//                                for VSA), joint c's rotation, column c of M and of M^-1 and entry c of the Euler step; lane
-//                                NJ owns the nonlinear effects.  What differs:
+//   policy_rollout_team_kernel   A TEAM OF 8 LANES PER (trajectory, SAMPLE).  The plant step is TeamStep's
+//                                (aslr_team_step.hpp); on top of it lane c < NJ owns row c of the control law (rows c and
+//                                NJ + c for VSA).  What is this kernel's own:
 //     - the team index is the sample: one block = 2 waves = 16 samples of ONE trajectory, so what the samples share --
 //       [K_t | xs_t | us_t | reference placement of the knot] -- is staged once per wave and prefetched one knot ahead;
 //     - every team has its own plant: lane c holds K_cc and 1 / B_cc of its sample (the caller's arrays, else the row of
@@ -16,7 +15,7 @@
 //       the time of one evaluation -- what a single lane per team would take, the other seven masked off;
 //     - it writes nothing but the caller's buffers.
 #pragma once
-#include "aslr_forward_team.inc.hpp"
+#include "aslr_team_step.hpp"
 
 namespace aslr {
 
@@ -36,10 +35,10 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
   const int sq = blockIdx.y * TPB + team, s = sq < S ? sq : S - 1;
   const bool on = sq < S;
   double *stg = sm + wv * STG, *tm_ = sm + 2 * STG + team * C::TEAM_LDS;
-  double *xT = tm_ + C::tX, *uT = tm_ + C::tU, *tcL = tm_ + C::tTc, *tmL = tm_ + C::tTm, *RL = tm_ + C::tR,
-         *ML = tm_ + C::tM, *MiL = tm_ + C::tMi;
-  const bool jl = c < NJ; // this lane owns joint / row cj
-  const int cj = jl ? c : NJ - 1;
+  const TeamStep<NJ, VSA, C> ts(tm_, c);
+  double *const xT = ts.xT, *const uT = ts.uT;
+  const bool jl = ts.jl; // this lane owns joint / row cj
+  const int cj = ts.cj;
   const DevDesc &D = *a.desc;
   const aslr_chain_t &ch = D.chain;
   const chain_cp chc = chain_const(&D.chain);
@@ -70,14 +69,7 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
   // parameter table where one is set, else (use_k / use_b false) the row of the knot's model ----
   const bool table = pa.table != 0, use_k = pa.plant_stiffness || table, use_b = pa.plant_motor_inertia || table;
   double k_cj = 0.0, b_cj = 0.0, lb_c = 0.0, ub_c = 0.0, lb_s = 0.0, ub_s = 0.0; // (lb_s / ub_s: the stiffness row, VSA)
-  if (table) {
-    const double *tp = traj_params_at(D, b);
-    k_cj = tp[(size_t)cj * B];
-    b_cj = tp[(size_t)(NJ + cj) * B];
-    lb_c = tp[(size_t)(2 * NJ + cj) * B];
-    ub_c = tp[(size_t)(2 * NJ + NU + cj) * B];
-    if (VSA) { lb_s = tp[(size_t)(3 * NJ + cj) * B]; ub_s = tp[(size_t)(3 * NJ + NU + cj) * B]; }
-  }
+  if (table) team_table_row<NJ, NU, VSA>(traj_params_at(D, b), cj, B, k_cj, b_cj, lb_c, ub_c, lb_s, ub_s);
   if (pa.plant_stiffness) k_cj = pa.plant_stiffness[((size_t)cj * S + s) * B + b];
   if (pa.plant_motor_inertia) b_cj = 1.0 / pa.plant_motor_inertia[((size_t)cj * S + s) * B + b];
   double Krow[NJ], Srow[NJ], Brow[NJ], dt = 0.0;
@@ -85,12 +77,8 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
   bool has_lim = false;
   int m_loaded = -1;
 
-  // joint placements and axes: constants of the chain, staged once in LDS (rollout_team_kernel says why)
   __shared__ double jtab[8][12];
-  if (threadIdx.x < NJ) {
-    ASLR_UNROLL for (int k = 0; k < 9; ++k) jtab[threadIdx.x][k] = ch.joint_R[threadIdx.x][k];
-    ASLR_UNROLL for (int k = 0; k < 3; ++k) jtab[threadIdx.x][9 + k] = ch.axis[threadIdx.x][k];
-  }
+  stage_joint_table<NJ>(jtab, ch, threadIdx.x);
   __syncthreads();
 
   // x0 (+ the sample's offset) into the team's state
@@ -112,11 +100,7 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
   double *xs_o = pa.xs_closed ? pa.xs_closed + ((size_t)s * (T + 1) * B + b) * NX : nullptr; // knot t at + t B NX
   double *us_o = pa.us_closed ? pa.us_closed + ((size_t)s * T * B + b) * NU : nullptr;
   auto store_x = [&](int t) { // the team's state as row t of xs_closed, 4 contiguous entries per lane
-    if (on && jl && xs_o) {
-      double *o = xs_o + (size_t)t * B * NX + 4 * c;
-      *reinterpret_cast<double2 *>(o) = make_double2(xT[4 * c], xT[4 * c + 1]);
-      *reinterpret_cast<double2 *>(o + 2) = make_double2(xT[4 * c + 2], xT[4 * c + 3]);
-    }
+    if (on && jl && xs_o) team_store_state_row(xs_o + (size_t)t * B * NX + 4 * c, xT, c);
   };
   const typename Chain3D<NJ>::Consts cc(D, true);
   ModelRegs<NJ, NU> mr; // (the cost stack reads none of it)
@@ -132,14 +116,7 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
     const DevModel &dm = D.models[mi];
     if (t < T && mi != m_loaded) { // wave-uniform: model constants and control limits, re-read only when the model changes
       dt = dm.m.dt;
-      ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
-        if (!VSA) {
-          // (pa.diagonal is the host's fact: a plant array or a table, both of which need diagonal models)
-          Krow[j] = pa.diagonal ? ((j == cj) ? (use_k ? k_cj : dm.m.K[cj * NJ + cj]) : 0.0) : dm.m.K[cj * NJ + j];
-          Srow[j] = dm.m.S[cj * NU + j];
-        }
-        Brow[j] = pa.diagonal ? ((j == cj) ? (use_b ? b_cj : dm.Binv[cj * NJ + cj]) : 0.0) : dm.Binv[cj * NJ + j];
-      }
+      team_model_rows<NJ, NU, VSA>(dm, cj, pa.diagonal, use_k, k_cj, use_b, b_cj, Krow, Srow, Brow);
       has_lim = lim.has[mi] != 0;
       if (!table) {
         lb_c = lim.lb[mi][cj];
@@ -184,63 +161,21 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
       us_o[(size_t)t * B * NU + c] = u_c;
       if constexpr (VSA) us_o[(size_t)t * B * NU + NJ + c] = u_s;
     }
-    // ---- rotation of joint cj ----
-    if (jl) {
-      const M3 R = mul(m3(jtab[cj]), axis_angle(v3(jtab[cj] + 9), xT[cj]));
-      ASLR_UNROLL for (int k = 0; k < 9; ++k) RL[9 * c + k] = R.a[k];
-    }
+    // ---- the plant step (aslr_team_step.hpp) ----
+    ts.rotation(jtab);
     wave_sync();
-    // ---- coupling and motor torques, entry cj ----
-    if (jl) {
-      double sc_ = 0.0, s2 = 0.0;
-      if constexpr (VSA) { // K = diag(stiffness commands), tau_m = the torque commands
-        ASLR_UNROLL for (int j = 0; j < NJ; ++j) sc_ += (j == c ? uT[NJ + c] : 0.0) * (xT[j] - xT[NJ + j]);
-        s2 = uT[c];
-      } else {
-        ASLR_UNROLL for (int j = 0; j < NJ; ++j) { sc_ += Krow[j] * (xT[j] - xT[NJ + j]); s2 += Srow[j] * uT[j]; }
-      }
-      tcL[c] = sc_;
-      tmL[c] = s2;
-    }
-    // ---- one RNEA per lane: column c of M (lanes c < NJ), nonlinear effects (lane NJ) ----
-    if (c <= NJ) {
-      double vv[NJ], aa[NJ], tau[NJ];
-      const bool nl = c == NJ;
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i) { vv[i] = nl ? xT[2 * NJ + i] : 0.0; aa[i] = (!nl && i == c) ? 1.0 : 0.0; }
-      const V3 g = v3(chc->gravity);
-      const V3 grav = nl ? g : V3{0.0, 0.0, 0.0};
-      rnea_lds<NJ>(chc, RL, vv, aa, grav, tau);
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i) ML[8 * c + i] = tau[i];
-    }
+    ts.torques(Krow, Srow);
+    ts.mass_columns(chc);
     wave_sync();
-    // ---- column cj of M^-1 (M symmetrised like Chain3D::mass) ----
-    {
-      double Ms[NJ][NJ], e[NJ];
-      ASLR_UNROLL for (int i = 0; i < NJ; ++i)
-        ASLR_UNROLL for (int j = 0; j <= i; ++j) {
-          Ms[i][j] = (i == j) ? ML[8 * j + i] : 0.5 * (ML[8 * j + i] + ML[8 * i + j]);
-          Ms[j][i] = Ms[i][j];
-        }
-      spd_inverse_col<NJ>(Ms, cj, e);
-      if (jl) { ASLR_UNROLL for (int i = 0; i < NJ; ++i) MiL[8 * c + i] = e[i]; }
-    }
+    ts.minv_column();
     wave_sync();
-    // ---- accelerations and semi-implicit Euler, entries cj of q_l, q_m, v_l, v_m ----
-    double al = 0.0, am = 0.0;
-    ASLR_UNROLL for (int j = 0; j < NJ; ++j) {
-      al += MiL[8 * j + cj] * (-ML[8 * NJ + j] - tcL[j]);
-      am += Brow[j] * (tmL[j] + tcL[j]);
-    }
-    const double ql = xT[cj], qm = xT[NJ + cj], vl = xT[2 * NJ + cj], vm = xT[3 * NJ + cj];
-    const double nql = ql + (vl * dt + al * dt * dt), nvl = vl + al * dt;
-    const double nqm = qm + (vm * dt + am * dt * dt), nvm = vm + am * dt;
-    const double nxt[4] = {nql, nvl, nqm, nvm}; // this lane's entries of xnext: |xnext|_inf test, entry by entry
-    const bool bad = jl && inf_norm_bad<4>(fabs(nql) + fabs(nvl) + fabs(nqm) + fabs(nvm), nxt);
+    double nxt[4]; // this lane's entries {q_l, v_l, q_m, v_m} of xnext
+    const bool bad = ts.euler(Brow, dt, nxt);
     if ((__ballot(bad) & team_bits) && failed < 0) failed = t; // NaN / Inf / |xnext|_inf >= 1e30, as the solver's rollout
     wave_sync(); // every lane of the team has read the old state
     if (jl) {
-      if (wsrc) { xT[c] = nql + w[0]; xT[NJ + c] = nqm + w[1]; xT[2 * NJ + c] = nvl + w[2]; xT[3 * NJ + c] = nvm + w[3]; }
-      else { xT[c] = nql; xT[NJ + c] = nqm; xT[2 * NJ + c] = nvl; xT[3 * NJ + c] = nvm; }
+      if (wsrc) { xT[c] = nxt[0] + w[0]; xT[NJ + c] = nxt[2] + w[1]; xT[2 * NJ + c] = nxt[1] + w[2]; xT[3 * NJ + c] = nxt[3] + w[3]; }
+      else { xT[c] = nxt[0]; xT[NJ + c] = nxt[2]; xT[2 * NJ + c] = nxt[1]; xT[3 * NJ + c] = nxt[3]; }
     }
   }
   if (!on) return;
@@ -249,11 +184,8 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
     if (pa.cost) pa.cost[sb] = failed >= 0 ? NAN : J;
     if (pa.failed_knot) pa.failed_knot[sb] = failed;
   }
-  if (jl && pa.x_final) { // (the state of knot T: nothing has written it since the loop's last fence)
-    double *o = pa.x_final + sb * NX + 4 * c;
-    *reinterpret_cast<double2 *>(o) = make_double2(xT[4 * c], xT[4 * c + 1]);
-    *reinterpret_cast<double2 *>(o + 2) = make_double2(xT[4 * c + 2], xT[4 * c + 3]);
-  }
+  // (the state of knot T: nothing has written it since the loop's last fence)
+  if (jl && pa.x_final) team_store_state_row(pa.x_final + sb * NX + 4 * c, xT, c);
 }
 
 // the nx = 28 sizes: grid (trajectories, groups of 16 samples), one block = 2 waves of 8 teams
