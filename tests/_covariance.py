@@ -10,7 +10,7 @@ aslr_policy_covariance (include/aslr_to_amd_cov.h), without changing the oracle.
    a relative measure says something.
  - case(): the seeded scenario and candidate of the GPU cases -- seeded controls (clipped to the box where there is one) and
    the oracle's open-loop roll-out of them from x0, the recipe of tests/_policy.case.
- - relerr(): per output array and trajectory max |a - b| / max |b|; the worst trajectory is returned.
+ - traj_relerr(): per output array and trajectory max |a - b| / max |b|; the worst trajectory is returned.
 
 Everything is time-major going in (the oracle's layout) and batch-major coming out, like Engine.policy_covariance: x_var
 [B, T+1, nx], u_var [B, T, nu] (the device's nu), cov_final [B, nx, nx], cov [B, T+1, nx, nx], cost_increase [B]."""
@@ -145,7 +145,7 @@ def expected(oracle, low, xs, us, K, sigma0=None, noise_var=None):
     return propagate(low, records(oracle, low, xs, us), K, sigma0, noise_var)
 
 
-def relerr(a, b):
+def traj_relerr(a, b):
     """max over the trajectories (axis 0) of max |a - b| / max |b|; a trajectory whose reference is all zero must match
     exactly (-> 0.0, else inf)"""
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)

@@ -36,8 +36,10 @@ def to_np(t):
 
 
 def relerr(a, b):
+    """max |a - b| / (1 + |b|), 0 for empty arrays: the one definition (tests/_policy.py and tests/_sensitivity.py pass it on
+    to the host suites under their own names; tests/_covariance.traj_relerr is another measure)"""
     a, b = np.asarray(a), np.asarray(b)
-    return np.max(np.abs(a - b) / (1.0 + np.abs(b))) if a.size else 0.0
+    return float(np.max(np.abs(a - b) / (1.0 + np.abs(b)))) if a.size else 0.0
 
 
 def bits(t):
@@ -46,6 +48,7 @@ def bits(t):
 
 
 def same_bits(a, b, what):
+    """two tensors, compared where they lie; tests/_ext_call.same is the same comparison of numpy arrays and dicts of them"""
     import torch
     assert a.shape == b.shape and torch.equal(bits(a), bits(b)), what
 

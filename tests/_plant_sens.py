@@ -34,7 +34,7 @@ OUTPUTS = ("dx_dstiffness", "dx_dmotor_inertia", "dxT_dstiffness", "dxT_dmotor_i
 
 # tests/test_plant_sens_host.py, the definition against central differences of the nonlinear closed loop with the oracle's
 # gains, per case: (relative step h, disagreement measured at h, at h / 2) on the oracle alone, worst of S_T, V and dJ/dtheta
-# in the measure cv.relerr; the bound of a test is ten times the value (how they were measured: the test's docstring)
+# in the measure cv.traj_relerr; the bound of a test is ten times the value (how they were measured: the test's docstring)
 FD = {
     "sea": (1e-4, 2.58e-7, 6.41e-8),
     "vsa_box": (1e-4, 4.29e-7, 1.08e-7),
@@ -162,7 +162,7 @@ FD_OUTPUTS = ("V", "dxT_dstiffness", "dxT_dmotor_inertia", "dcost_dstiffness", "
 
 
 def fd_disagreement(oracle, low, xs, us, K, h):
-    """worst over FD_OUTPUTS of cv.relerr(definition, central differences at relative step h)"""
+    """worst over FD_OUTPUTS of cv.traj_relerr(definition, central differences at relative step h)"""
     want = expected(oracle, low, xs, us, K)
     got = fd_rollout(oracle, low, xs, us, K, h)
-    return max(cv.relerr(want[k], got[k]) for k in FD_OUTPUTS if want[k] is not None)
+    return max(cv.traj_relerr(want[k], got[k]) for k in FD_OUTPUTS if want[k] is not None)

@@ -13,6 +13,7 @@ import numpy as np
 
 import _ref_path
 import _traj_oracle
+from _gpu_case import relerr  # noqa: F401 (pol.relerr of the host suites)
 from aslr_to_amd import _abi, scenarios
 
 # (scenario, table, path, B, S, T, 3-D chain, clamp): the shapes are the smallest that leave a partial wave of teams (B = 5:
@@ -176,8 +177,3 @@ def rollout(oracle, low, xs, us, K, S, plant_stiffness=None, plant_motor_inertia
 
 
 OUTPUTS = ("cost", "x_final", "xs", "us")
-
-
-def relerr(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return float(np.max(np.abs(a - b) / (1.0 + np.abs(b)))) if a.size else 0.0

@@ -15,6 +15,7 @@ public getters: stiffness [B, nj] (None for VSA), motor_inertia [B, nj], x0 [B, 
 import numpy as np
 
 import _traj_oracle
+from _gpu_case import relerr  # noqa: F401 (sens.relerr of the host suites)
 from aslr_to_amd import _abi
 
 
@@ -150,9 +151,3 @@ def optimum_fd(oracle):
     from aslr_to_amd import scenarios
     sc, sp = optimum_case()
     return fd_optimum(oracle, scenarios.lower(sc), sp, OPT_FD[0])
-
-
-def relerr(got, ref):
-    """max |got - ref| / (1 + |ref|): the measure of tests/_gpu_case.relerr"""
-    got, ref = np.asarray(got), np.asarray(ref)
-    return float(np.max(np.abs(got - ref) / (1.0 + np.abs(ref))))

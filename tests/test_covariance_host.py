@@ -77,7 +77,7 @@ def _fd_disagreement(oracle, low, xs, us, K, h):
             xm = pol.rollout_one(oracle, low, b, xs[:, b], us[:, b], K[:, b], dx0=-e)["xs"][T]
             Phi[:, i] = (xp - xm) / (2 * h)
         got[b] = Phi @ Phi.T
-    return cv.relerr(want, got)
+    return cv.traj_relerr(want, got)
 
 
 @pytest.mark.parametrize("name", sorted(JACOBIAN_FD))
@@ -162,7 +162,7 @@ def test_the_gpu_cases_are_well_conditioned(oracle, key):
         base = cv.expected(oracle, low, c["xs"], c["us"], K, s0, w)
         moved = cv.expected(oracle, low, xs2, us2, K2, s0, w)
         assert all(np.isfinite(base[k]).all() for k in cv.OUTPUTS)
-        worst = max([worst] + [cv.relerr(moved[k], base[k]) for k in cv.OUTPUTS])
+        worst = max([worst] + [cv.traj_relerr(moved[k], base[k]) for k in cv.OUTPUTS])
     zero_rows = int((np.abs(K).max(axis=-1) == 0.0).sum())
     print("%s: worst movement %.2e; %d of %d gain rows are zero" % (key, worst, zero_rows, K.shape[0] * K.shape[1] * K.shape[2]))
     assert worst < 1e-11, worst

@@ -7,21 +7,18 @@ array and trajectory; tests/test_covariance_host.py shows that the inputs are co
 (tests/_covariance.CASES): the smallest that leave a partial wave of teams (B = 9 at nx = 8: 8 trajectories per wave; B = 3 at
 nx = 28: 2 per wave) and the smallest problem there is (B = 1, T = 1).  Every output sits in a buffer of the test's own,
 followed by guard words that must survive."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import _covariance as cv
+import _ext_call as ext
 import _gpu_case as gc
-import _policy as pol
 import _traj_oracle
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = cv.OUTPUTS
-GUARD, SENTINEL = 64, -7.25
 _TO_BATCH_MAJOR = {"x_var": (1, 0, 2), "u_var": (1, 0, 2), "cov_final": (0, 1, 2), "cov": (1, 0, 2, 3), "cost_increase": (0,)}
 
 
@@ -32,51 +29,11 @@ def _shapes(e):
 
 def _raw(e, sigma0, noise_var, which=FIELDS, expect=_abi.OK):
     """aslr_policy_covariance with the batch-major inputs sigma0 [B, nx, nx] and noise_var [B, T, nx] (None: NULL) and the
-    outputs `which` (the others NULL), each output in a buffer with GUARD sentinel words behind it.  -> dict of batch-major
-    numpy arrays (the layout of tests/_covariance.expected; u_var with the device's nu); the guards must be untouched.
-    expect != OK: -> the message of the refusal."""
-    import torch
-    dev = lambda v: torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float64, device=e.device)
-    s0 = None if sigma0 is None else dev(sigma0)
-    w = None if noise_var is None else dev(np.transpose(noise_var, (1, 0, 2)))
-    bufs, n_of = {}, {}
-    for k in which:
-        n_of[k] = int(np.prod(_shapes(e)[k]))
-        bufs[k] = torch.full((n_of[k] + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(e.device):
-        rc = e.lib.aslr_policy_covariance(e.handle, ptr(s0), ptr(w), *[ptr(bufs.get(k)) for k in FIELDS], e._stream())
-    gc.sync()
-    if expect != _abi.OK:
-        assert rc == expect, rc
-        for k, t in bufs.items():
-            assert (t == SENTINEL).all(), "%s was written by a refused call" % k
-        return e.lib.aslr_last_error().decode()
-    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
-    out = {}
-    for k, t in bufs.items():
-        a = gc.to_np(t)
-        assert (a[n_of[k]:] == SENTINEL).all(), "the guard behind %s was overwritten" % k
-        out[k] = np.ascontiguousarray(np.transpose(a[:n_of[k]].reshape(_shapes(e)[k]), _TO_BATCH_MAJOR[k]))
-    return out
-
-
-def _same(a, b, what):
-    assert set(a) == set(b), (what, sorted(a), sorted(b))
-    for k in a:
-        np.testing.assert_array_equal(a[k].view(np.uint64), b[k].view(np.uint64), err_msg="%s: %s" % (what, k))
-
-
-def _with_gains(c):
-    """a fresh engine with the case's candidate in XS / US and the gains of one aslr_calc_diff + aslr_backward_pass on it in
-    KGAIN (the case's own solver: SolverBoxDDP where the scenario has one) -> engine, K [T, B, nu, nx]"""
-    low = c["low"]
-    e = gc.engine(low)
-    deriv = gc.run_calc_diff(e, c["xs"], c["us"])[2]
-    out = gc.run_backward(e, c["sp"], c["us"], deriv, np.zeros((low.T + 1, low.B, low.nx)), pol.XREG, 1)
-    assert (out["status"] & _abi.ST_BACKWARD_ERR == 0).all(), out["status"]
-    assert np.abs(out["K"]).max() > 1e-3
-    return e, out["K"]
+    outputs `which` (the others NULL) through the guarded call of tests/_ext_call.py -> dict of batch-major numpy arrays (the
+    layout of tests/_covariance.expected; u_var with the device's nu), or the message of the refusal"""
+    outs = ext.outputs(e.device, _shapes(e), which, perms=_TO_BATCH_MAJOR)
+    args = [e.handle, ext.dev(e.device, sigma0), ext.dev(e.device, noise_var, (1, 0, 2))] + [outs.get(k) for k in FIELDS] + [e._stream()]
+    return ext.call(e, "aslr_policy_covariance", args, outs, expect)
 
 
 @pytest.fixture(scope="module")
@@ -93,7 +50,7 @@ def loaded(cases):
 
     def get(key):
         if key not in made:
-            made[key] = _with_gains(cases[key])
+            made[key] = ext.with_gains(cases[key])
         return made[key]
     return get
 
@@ -108,7 +65,7 @@ def test_kernel_matches_the_definition(oracle, cases, loaded, key, which):
     want = cv.expected(oracle, c["low"], c["xs"], c["us"], K, s0, w)
     for k in FIELDS:
         assert got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
-        err = cv.relerr(got[k], want[k])
+        err = cv.traj_relerr(got[k], want[k])
         print("%s %s %s: %.2e (max |reference| %.2e)" % (key, which, k, err, np.abs(want[k]).max()))
         assert err < 1e-9, (k, err)
     assert np.abs(want["cost_increase"]).min() > 1e-6
@@ -122,7 +79,7 @@ def test_kernel_matches_the_definition(oracle, cases, loaded, key, which):
         assert (got["u_var"][..., 1] == 0.0).all()   # the padded control
     if getattr(c["low"], "ref_path", None) is not None:   # ... and the path is what the records were evaluated against
         plain = scenarios.lower(dict(c["sc"], ref_path=None))
-        assert cv.relerr(cv.expected(oracle, plain, c["xs"], c["us"], K, s0, w)["cost_increase"], want["cost_increase"]) > 1e-6
+        assert cv.traj_relerr(cv.expected(oracle, plain, c["xs"], c["us"], K, s0, w)["cost_increase"], want["cost_increase"]) > 1e-6
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_vsa"])
@@ -132,9 +89,9 @@ def test_every_output_is_optional(cases, loaded, key):
     e, _ = loaded(key)
     full = _raw(e, c["sigma0"], c["noise_var"])
     for k in FIELDS:
-        _same(_raw(e, c["sigma0"], c["noise_var"], which=(k,)), {k: full[k]}, "alone")
+        ext.same(_raw(e, c["sigma0"], c["noise_var"], which=(k,)), {k: full[k]}, "alone")
     pair = _raw(e, c["sigma0"], c["noise_var"], which=("x_var", "cov_final"))   # (no control terms: the other kernel branch)
-    _same(pair, {k: full[k] for k in pair}, "states only")
+    ext.same(pair, {k: full[k] for k in pair}, "states only")
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_sea"])
@@ -150,7 +107,7 @@ def test_a_trajectory_does_not_depend_on_where_it_sits(cases, loaded, key):
     e1 = gc.engine(_traj_oracle.single(low, b))
     gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
     alone = _raw(e1, c["sigma0"][b:b + 1], c["noise_var"][b:b + 1])
-    _same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
+    ext.same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_vsa"])
@@ -166,17 +123,17 @@ def test_the_outputs_are_consistent_with_each_other(oracle, cases, loaded, key):
     garbage = np.array(c["sigma0"])
     iu = np.triu_indices(low.nx, 1)
     garbage[:, iu[0], iu[1]] = np.random.default_rng(47).uniform(-1e6, 1e6, (low.B, iu[0].size))
-    _same(_raw(e, garbage, c["noise_var"]), got, "garbage above the diagonal of sigma0")
+    ext.same(_raw(e, garbage, c["noise_var"]), got, "garbage above the diagonal of sigma0")
     fresh = gc.engine(low)
     gc._upload(fresh, XS=c["xs"], US=c["us"])
     open_loop = _raw(fresh, c["sigma0"], c["noise_var"])
     want = cv.expected(oracle, low, c["xs"], c["us"], np.zeros((low.T, low.B, low.nu, low.nx)), c["sigma0"], c["noise_var"])
     for k in FIELDS:
-        err = cv.relerr(open_loop[k], want[k])
+        err = cv.traj_relerr(open_loop[k], want[k])
         print("%s open loop %s: %.2e" % (key, k, err))
         assert err < 1e-9, (k, err)
     assert (open_loop["u_var"] == 0.0).all()
-    assert cv.relerr(open_loop["x_var"], got["x_var"]) > 1e-3   # ... and the gains are what closed the loop above
+    assert cv.traj_relerr(open_loop["x_var"], got["x_var"]) > 1e-3   # ... and the gains are what closed the loop above
 
 
 def test_the_call_has_the_side_effects_of_calc_diff(cases):
@@ -206,7 +163,7 @@ def test_refusals_write_nothing_and_leave_a_live_handle(cases, loaded):
     assert msg.startswith("aslr_policy_covariance:") and "outputs" in msg and "NULL" in msg, msg
     msg = _raw(e, None, None, expect=_abi.E_INVALID)
     assert msg.startswith("aslr_policy_covariance:") and "sigma0" in msg and "noise_var" in msg, msg
-    _same(_raw(e, c["sigma0"], c["noise_var"]), ok, "the handle after the refusals")
+    ext.same(_raw(e, c["sigma0"], c["noise_var"]), ok, "the handle after the refusals")
 
 
 def test_python_facade(cases):

@@ -10,22 +10,11 @@ import numpy as np
 import pytest
 
 import _design as D
+import _ext_call as ext
 import _gpu_case as gc
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -7.25
-REGIONS = (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_F, _abi.R_TRAJ_I)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(got, want, what):
-    np.testing.assert_array_equal(_bits(got), _bits(want), err_msg=what)
-
 
 def _table(e):
     import torch
@@ -45,7 +34,7 @@ class _Buffers(object):
                       eta=(B,), grad=(2 * nj, B))
         if history:
             shapes.update(hist_f=(n, 3, B), theta_hist=(n, 2 * nj, B))
-        self.t = {k: torch.full(s, SENTINEL, dtype=torch.float64, device=e.device) for k, s in shapes.items()}
+        self.t = {k: torch.full(s, ext.SENTINEL, dtype=torch.float64, device=e.device) for k, s in shapes.items()}
         if history:
             self.t["hist_i"] = torch.full((n, B), -77, dtype=torch.int32, device=e.device)
         self.t["lo"] = torch.as_tensor(np.ascontiguousarray(lo), dtype=torch.float64, device=e.device)
@@ -67,7 +56,7 @@ class _Buffers(object):
     def untouched(self):
         for k in self.outputs:
             t = self.t[k]
-            assert bool((t == (-77 if t.dtype != self.t["eta"].dtype else SENTINEL)).all()), "%s was written by a refused call" % k
+            assert bool((t == (-77 if t.dtype != self.t["eta"].dtype else ext.SENTINEL)).all()), "%s was written by a refused call" % k
 
     def np(self):
         return {k: gc.to_np(t) for k, t in self.t.items()}
@@ -204,16 +193,16 @@ def test_step_kernel_matches_the_numpy_rule_bit_for_bit(name, B, fields):
             assert set(np.unique(want["flag"])) == ({-1, 0, 1} if s > 0 else {-1, 1}), want["flag"]
         for k, key in (("theta", "theta_best"), ("cost", "cost_best"), ("g_acc", "g_acc"), ("eta", "eta"), ("xs_best", "xs_best"),
                        ("us_best", "us_best")):
-            _same(got[key], st[k], what + key)
-        _same(got["hist_f"][0], want["hist_f"], what + "hist_f")
+            ext.same(got[key], st[k], what + key)
+        ext.same(got["hist_f"][0], want["hist_f"], what + "hist_f")
         np.testing.assert_array_equal(got["hist_i"][0], want["flag"], err_msg=what + "hist_i")
-        _same(got["theta_hist"][0], want["theta_try"], what + "theta_hist")
-        _same(gc.to_np(e.region(_abi.R_XS)), want["xs"], what + "XS")
-        _same(gc.to_np(e.region(_abi.R_US)), want["us"], what + "US")
+        ext.same(got["theta_hist"][0], want["theta_try"], what + "theta_hist")
+        ext.same(gc.to_np(e.region(_abi.R_XS)), want["xs"], what + "XS")
+        ext.same(gc.to_np(e.region(_abi.R_US)), want["us"], what + "US")
         tab = before.copy()
         tab[:2 * nj][active] = want["table"][active]
         assert np.isnan(want["table"][~active]).all() and not np.isnan(want["table"][active]).any()
-        _same(gc.to_np(_table(e)), tab, what + "TRAJ_PARAMS (the box rows untouched)")
+        ext.same(gc.to_np(_table(e)), tab, what + "TRAJ_PARAMS (the box rows untouched)")
         for rid in (_abi.R_KFF, _abi.R_GAPS, _abi.R_VXXF):
             assert not gc.to_np(e.region(rid)).view(np.int64).any(), what + "region %d is not all zero" % rid
 
@@ -224,16 +213,16 @@ WHOLE = [("sea_KB", 1), ("sea_KB", 2), ("sea_K", 1), ("sea_B", 1), ("vsa_B", 1),
 
 def _assert_call_equals_loop(c, e, got, host, r, what):
     st = r["state"]
-    _same(got["theta_best"], st["theta"], what + "theta_best")
-    _same(got["cost_best"], st["cost"], what + "cost_best")
-    _same(got["xs_best"], st["xs_best"], what + "xs_best")
-    _same(got["us_best"], st["us_best"], what + "us_best")
-    _same(got["hist_f"], r["hist_f"], what + "hist_f")
+    ext.same(got["theta_best"], st["theta"], what + "theta_best")
+    ext.same(got["cost_best"], st["cost"], what + "cost_best")
+    ext.same(got["xs_best"], st["xs_best"], what + "xs_best")
+    ext.same(got["us_best"], st["us_best"], what + "us_best")
+    ext.same(got["hist_f"], r["hist_f"], what + "hist_f")
     np.testing.assert_array_equal(got["hist_i"], r["flag"], err_msg=what + "hist_i")
-    _same(got["theta_hist"], r["theta_hist"], what + "theta_hist")
-    _same(gc.to_np(e.region(_abi.R_XS)), r["xs"], what + "XS")
-    _same(gc.to_np(e.region(_abi.R_US)), r["us"], what + "US")
-    _same(gc.to_np(_table(e)), gc.to_np(_table(host)), what + "TRAJ_PARAMS")
+    ext.same(got["theta_hist"], r["theta_hist"], what + "theta_hist")
+    ext.same(gc.to_np(e.region(_abi.R_XS)), r["xs"], what + "XS")
+    ext.same(gc.to_np(e.region(_abi.R_US)), r["us"], what + "US")
+    ext.same(gc.to_np(_table(e)), gc.to_np(_table(host)), what + "TRAJ_PARAMS")
     for rid in (_abi.R_TRAJ_F, _abi.R_TRAJ_I):   # those of the last step's solve
         gc.same_bits(e.region(rid), host.region(rid), what + "region %d" % rid)
 
@@ -290,8 +279,8 @@ def test_the_handle_is_left_on_the_accepted_design(name):
         h.solve(sp, poll_every=0)
         s = h.cost_sensitivity()
         gc.sync()
-        outs.append((s, [gc.to_np(h.region(r)) for r in REGIONS]))
-    for a, b, rid in zip(outs[0][1], outs[1][1], REGIONS):
+        outs.append((s, [gc.to_np(h.region(r)) for r in ext.SOLVE_REGIONS]))
+    for a, b, rid in zip(outs[0][1], outs[1][1], ext.SOLVE_REGIONS):
         np.testing.assert_array_equal(a.view(np.int64) if a.dtype == np.float64 else a, b.view(np.int64) if b.dtype == np.float64 else b,
                                       err_msg="region %d of a solve after the call" % rid)
     for k in ("motor_inertia", "x0", "costate") + (() if vsa else ("stiffness",)):
@@ -401,23 +390,23 @@ def test_python_facade():
         assert (r.stiffness is None) == vsa
         if not vsa:
             assert tuple(r.stiffness.shape) == (B, nj) and tuple(r.stiffness_history.shape) == (B, c["n_steps"], nj)
-            _same(gc.to_np(r.stiffness), raw["theta_best"][:nj].T, "stiffness")
+            ext.same(gc.to_np(r.stiffness), raw["theta_best"][:nj].T, "stiffness")
         assert tuple(r.motor_inertia.shape) == (B, nj) and tuple(r.cost.shape) == (B,)
         assert tuple(r.xs.shape) == (B, T + 1, low.nx) and tuple(r.us.shape) == (B, T, problem.engine.nu_user)
         assert tuple(r.accepted_history.shape) == (B, c["n_steps"]) and tuple(r.motor_inertia_history.shape) == (B, c["n_steps"], nj)
-        _same(gc.to_np(r.motor_inertia), raw["theta_best"][nj:].T, "motor_inertia")
-        _same(gc.to_np(r.cost), raw["cost_best"], "cost")
-        _same(gc.to_np(r.xs), raw["xs_best"].transpose(1, 0, 2), "xs")
+        ext.same(gc.to_np(r.motor_inertia), raw["theta_best"][nj:].T, "motor_inertia")
+        ext.same(gc.to_np(r.cost), raw["cost_best"], "cost")
+        ext.same(gc.to_np(r.xs), raw["xs_best"].transpose(1, 0, 2), "xs")
         np.testing.assert_array_equal(gc.to_np(r.accepted_history), raw["hist_i"].T)
-        _same(gc.to_np(solver.xs), gc.to_np(r.xs), "solver.xs is the accepted plan")
-        _same(problem.lowered.traj_params["motor_inertia"], gc.to_np(r.motor_inertia), "the problem's table")
+        ext.same(gc.to_np(solver.xs), gc.to_np(r.xs), "solver.xs is the accepted plan")
+        ext.same(problem.lowered.traj_params["motor_inertia"], gc.to_np(r.motor_inertia), "the problem's table")
     # scalar bounds, no table: the models' constants are the initial design
     sc = scenarios.two_dof_sea(B=3, T=6, seed=2)
     problem = crocoddyl.ShootingProblem(sc["x0"], sc["running"], sc["terminal"], frame_refs=sc["frame_refs"])
     solver = crocoddyl.SolverFDDP(problem)
     r = solver.optimize_design(2, 2, maxiter=10, stiffness_bounds=(1e-3, 1e6), motor_inertia_bounds=None)
     m0 = D.theta0_of(scenarios.lower(sc))
-    _same(gc.to_np(r.motor_inertia), m0[2:].T, "motor inertia is not optimised: the models' constant")
+    ext.same(gc.to_np(r.motor_inertia), m0[2:].T, "motor inertia is not optimised: the models' constant")
     assert float((r.stiffness - problem.engine.region(_abi.R_XS).new_tensor(m0[:2].T)).abs().max()) > 0.0
     with pytest.raises(_abi.AslrError, match="outside its bounds"):
         solver.optimize_design(2, 2, maxiter=10, stiffness_bounds=(1e-3, 1e-2))

@@ -8,6 +8,7 @@ import pytest
 
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
+import _ext_call as ext
 import _gpu_case as gc
 import _mpc_loop
 import _parity
@@ -15,7 +16,7 @@ import test_mpc_host as H
 
 pytestmark = pytest.mark.gpu
 
-REGIONS = (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_F, _abi.R_TRAJ_I)
+AFTER = "after a declined aslr_mpc_run"
 
 
 def _result_arrays(r):
@@ -132,7 +133,7 @@ def test_device_loop_equals_the_host_driven_loop_bit_for_bit():
         gc.same_bits(getattr(r, k), w["stat_f"][:, i].t(), k)
     gc.same_bits(r.iters, w["stat_i"][:, 0].t(), "iters")
     gc.same_bits(r.status, w["stat_i"][:, 1].t(), "status")
-    for rid in REGIONS + (_abi.R_X0,):
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(dev.region(rid), host.region(rid), "region %d" % rid)
     # (the comparison is not empty: every trajectory iterates in step 0, some trajectory in every step, the states move.
     #  Not every trajectory iterates in every step: with so few iterations this plant runs away on some of them -- costs of
@@ -166,28 +167,18 @@ def test_results_do_not_depend_on_subshards_or_batch():
     e2, r2 = run(sc, dist, 2)
     for k, a in _result_arrays(r1).items():
         gc.same_bits(a, _result_arrays(r2)[k], "%s with two sub-shards" % k)
-    for rid in REGIONS:
+    for rid in ext.SOLVE_REGIONS:
         gc.same_bits(e1.region(rid), e2.region(rid), "region %d with two sub-shards" % rid)
     half = dict(sc)
     half["x0"], half["frame_refs"] = sc["x0"][:64], sc["frame_refs"][:64]
     e3, r3 = run(half, dist[:, :64], 1)
     for k, a in _result_arrays(r1).items():
         gc.same_bits(a[:64], _result_arrays(r3)[k], "%s of the first 64 trajectories in a batch of 64" % k)
-    for rid in REGIONS:
+    for rid in ext.SOLVE_REGIONS:
         gc.same_bits(e1.region(rid)[:, :64], e3.region(rid), "region %d of the first 64 trajectories" % rid)
 
 
 # ---- 5. declines ----
-def _solve_matches_a_fresh_handle(e, low, sp):
-    fresh = gc.engine(low)
-    for h in (e, fresh):
-        h.set_candidate(None, None)
-        h.solve(sp, poll_every=4)
-    gc.sync()
-    for rid in REGIONS:
-        gc.same_bits(e.region(rid), fresh.region(rid), "region %d after a declined aslr_mpc_run" % rid)
-
-
 def test_declines_leave_the_handle_usable():
     sc = scenarios.two_dof_sea(B=4, T=6)
     sp = scenarios.solver_params(sc, solver="SolverFDDP", maxiter=20)
@@ -200,7 +191,7 @@ def test_declines_leave_the_handle_usable():
     e.set_candidate(None, None)
     with pytest.raises(_abi.AslrError, match="more than one action model"):
         e.mpc_run(sp, 2, 5, 2)
-    _solve_matches_a_fresh_handle(e, low, sp)
+    ext.solve_matches_a_fresh_handle(e, low, sp, ext.SOLVE_REGIONS, AFTER)
     # an iteration log that is set
     low = scenarios.lower(sc)
     e = gc.engine(low)
@@ -208,13 +199,13 @@ def test_declines_leave_the_handle_usable():
     e.enable_iteration_log(20)
     with pytest.raises(_abi.AslrError, match="an iteration log is set"):
         e.mpc_run(sp, 2, 5, 2)
-    _solve_matches_a_fresh_handle(e, low, sp)
+    ext.solve_matches_a_fresh_handle(e, low, sp, ext.SOLVE_REGIONS, AFTER)
     e.enable_iteration_log(0)
     # n_steps = 0 (and the other counts)
     for args in ((0, 5, 2), (2, 0, 2), (2, 5, 0)):
         with pytest.raises(_abi.AslrError, match="n_steps, first_maxiter and iters_per_step must be >= 1"):
             e.mpc_run(sp, *args)
-    _solve_matches_a_fresh_handle(e, low, sp)
+    ext.solve_matches_a_fresh_handle(e, low, sp, ext.SOLVE_REGIONS, AFTER)
     e.mpc_run(sp, 2, 5, 2)   # (and the same handle runs once the arguments are right)
     # (7, VSA) with SolverDDP
     sc7 = scenarios.talos_arm_vsa(B=2, T=4)
@@ -223,4 +214,4 @@ def test_declines_leave_the_handle_usable():
     e7.set_candidate(None, None)
     with pytest.raises(_abi.AslrError, match="built for SolverBoxDDP only"):
         e7.mpc_run(scenarios.solver_params(sc7, solver="SolverDDP", maxiter=5), 2, 5, 2)
-    _solve_matches_a_fresh_handle(e7, low7, scenarios.solver_params(sc7, maxiter=10))
+    ext.solve_matches_a_fresh_handle(e7, low7, scenarios.solver_params(sc7, maxiter=10), ext.SOLVE_REGIONS, AFTER)

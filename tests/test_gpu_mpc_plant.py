@@ -4,13 +4,12 @@ mpc_advance_hold_kernel, csrc/aslr_abi.hip) against tests/_mpc_plant.py.
 The oracle's solve returns no gains, so the call is held to its definition by induction: ONE control step against the
 definition (a twin handle's plain solve gives the plan and the gains; the plant phase is a numpy loop over the oracle's
 knot), then the loop against itself, bit for bit; at hold = 1, where no gain is read, the whole loop against the oracle's.
-Kernel outputs are held to 1e-9 relative, max |a - b| / (1 + |b|), the bound of the policy suite.  x_closed and u_closed sit
-in buffers of the test's own, followed by guard words that must survive."""
-import ctypes as C
-
+Kernel outputs are held to 1e-9 relative, max |a - b| / (1 + |b|), the bound of the policy suite.  Every output sits in a
+guarded buffer of tests/_ext_call.py."""
 import numpy as np
 import pytest
 
+import _ext_call as ext
 import _gpu_case as gc
 import _mpc_plant as mp
 import _parity
@@ -21,69 +20,13 @@ from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
 
-REGIONS = (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_F, _abi.R_TRAJ_I, _abi.R_X0)
-GUARD, SENTINEL = 64, -7.25
-KEYS = ("x", "u", "stat_f", "stat_i", "cost", "failed")
+AFTER = "after a refused aslr_mpc_run_plant"
 
 
-def _raw(e, sp, n, first, per, hold=1, pk=None, pb=None, dist=None, clamp=False, cost=True, failed=True, expect=_abi.OK):
-    """aslr_mpc_run_plant.  pk, pb: batch-major [B, nj] or None (NULL); dist: time-major [N, B, nx] or None; cost / failed:
-    whether closed_cost / failed_knot are given.  -> dict of time-major numpy arrays: x [N+1, B, nx], u [N, B, nu], stat_f
-    [n, 4, B], stat_i [n, 2, B], cost [B], failed [B] (None where not given); the guards behind x and u must be untouched.
-    expect != OK: -> the message of the refusal, and nothing was written."""
-    import torch
-    N = max(n, 0) * max(hold, 0)
-    dev = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=e.device)
-    tk, tb, td = dev(None if pk is None else np.transpose(pk)), dev(None if pb is None else np.transpose(pb)), dev(dist)
-    nxw, nuw = (N + 1) * e.B * e.nx, N * e.B * e.nu
-    x = torch.full((nxw + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    u = torch.full((nuw + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    sf = torch.full((max(n, 1), 4, e.B), SENTINEL, dtype=torch.float64, device=e.device)
-    si = torch.full((max(n, 1), 2, e.B), -7, dtype=torch.int32, device=e.device)
-    cc = torch.full((e.B,), SENTINEL, dtype=torch.float64, device=e.device) if cost else None
-    fk = torch.full((e.B,), -7, dtype=torch.int32, device=e.device) if failed else None
-    mpc = _abi.Mpc()
-    mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, first, per
-    mpc.disturbance = td.data_ptr() if td is not None else None
-    mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = x.data_ptr(), u.data_ptr(), sf.data_ptr(), si.data_ptr()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(e.device):
-        rc = e.lib.aslr_mpc_run_plant(e.handle, C.byref(sp), C.byref(mpc), hold, ptr(tk), ptr(tb), 1 if clamp else 0, ptr(cc),
-                                      ptr(fk), e._stream())
-    gc.sync()
-    if expect != _abi.OK:
-        assert rc == expect, rc
-        for t, s in ((x, SENTINEL), (u, SENTINEL), (sf, SENTINEL), (si, -7), (cc, SENTINEL), (fk, -7)):
-            assert t is None or (t == s).all(), "a refused call wrote to an output"
-        return e.lib.aslr_last_error().decode()
-    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
-    xa, ua = gc.to_np(x), gc.to_np(u)
-    assert (xa[nxw:] == SENTINEL).all() and (ua[nuw:] == SENTINEL).all(), "a guard was overwritten"
-    return dict(x=xa[:nxw].reshape(N + 1, e.B, e.nx), u=ua[:nuw].reshape(N, e.B, e.nu), stat_f=gc.to_np(sf), stat_i=gc.to_np(si),
-                cost=None if cc is None else gc.to_np(cc), failed=None if fk is None else gc.to_np(fk))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(a, b, what):
-    np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=what)
-
-
-def _same_runs(a, b, what, keys=KEYS):
-    for k in keys:
-        if a[k] is not None or b[k] is not None:
-            _same(a[k], b[k], "%s: %s" % (what, k))
-
-
-def _fresh(low, nsub=1):
-    e = gc.engine(low)
-    if nsub > 1:
-        e.set_subshards(nsub)
-    e.set_candidate(None, None)
-    return e
+def _raw(e, *args, **kw):
+    """ext.mpc_run_plant(e, "aslr_mpc_run_plant", sp, n, first, per, hold=1, pk=None, pb=None, dist=None, clamp=False,
+    cost=True, failed=True, expect=OK)"""
+    return ext.mpc_run_plant(e, "aslr_mpc_run_plant", *args, **kw)
 
 
 # ---- 1. one control step is the definition ----
@@ -132,7 +75,7 @@ def test_one_control_step_is_the_definition(oracle, monkeypatch, key):
     B, T = low.B, low.T
     pk, pb = mp.plants(low, seed=21, rng_range=0.3) if opt.get("plants", True) else (None, None)
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (hold, B, low.nx))
-    e, twin = _fresh(low), _fresh(low)
+    e, twin = ext.fresh(low), ext.fresh(low)
     row_before = e.reference_row
     got = _raw(e, sp, 1, 3, 3, hold, pk, pb, dist, clamp)
     twin.solve(sp, poll_every=0)
@@ -145,7 +88,7 @@ def test_one_control_step_is_the_definition(oracle, monkeypatch, key):
     want_x, want_u = np.stack([r["x"] for r in ref], axis=1), np.stack([r["u"] for r in ref], axis=1)
     want_c, want_f = np.array([r["cost"] for r in ref]), np.array([r["failed"] for r in ref], dtype=np.int32)
     assert (want_f == -1).all()
-    errs = dict(x=pol.relerr(got["x"], want_x), u=pol.relerr(got["u"], want_u), cost=pol.relerr(got["cost"], want_c))
+    errs = dict(x=gc.relerr(got["x"], want_x), u=gc.relerr(got["u"], want_u), cost=gc.relerr(got["cost"], want_c))
     print("%s: relerr %s" % (key, {k: "%.2e" % v for k, v in errs.items()}))
     assert max(errs.values()) < 1e-9, errs
     np.testing.assert_array_equal(got["failed"], want_f)
@@ -155,27 +98,27 @@ def test_one_control_step_is_the_definition(oracle, monkeypatch, key):
         assert any(r["bound"] for r in ref), "the narrowed box must move some control of the reference"
         free = [mp.plant_phase(oracle, low, b, X[:, b], U[:, b], K[:, b], hold, pick(pk, b), pick(pb, b), dist[:, b], False)
                 for b in range(B)]
-        assert pol.relerr(np.stack([r["u"] for r in free], axis=1), want_u) > 1e-3   # ... and the clamp is what the kernel applied
+        assert gc.relerr(np.stack([r["u"] for r in free], axis=1), want_u) > 1e-3   # ... and the clamp is what the kernel applied
     if opt.get("plants_win"):   # the plants given on top of the table are what the kernel used, not the table's rows
         table = [mp.plant_phase(oracle, low, b, X[:, b], U[:, b], K[:, b], hold, None, None, dist[:, b], clamp) for b in range(B)]
-        assert pol.relerr(np.stack([r["x"] for r in table], axis=1), want_x) > 1e-6
-    _same(got["x"][0], X[0], "x_closed[0] is XS[0]")
+        assert gc.relerr(np.stack([r["x"] for r in table], axis=1), want_x) > 1e-6
+    ext.same(got["x"][0], X[0], "x_closed[0] is XS[0]")
     if not clamp:
-        _same(got["u"][0], U[0], "u_closed[0] is US[0]")
+        ext.same(got["u"][0], U[0], "u_closed[0] is US[0]")
     # the shift, exactly: rows of the twin's plan, the last one repeated; x+ in xs[0], X0 and x_closed[N]
     xs_want, us_want = mp.shifted(X, U, hold, got["x"][hold])
     XS, US = gc.to_np(e.region(_abi.R_XS)), gc.to_np(e.region(_abi.R_US))
-    _same(XS[1:], xs_want[1:], "XS after the shift, away from row 0")
-    _same(US, us_want, "US after the shift")
-    _same(XS[0], got["x"][hold], "xs[0] = x_closed[N]")
-    _same(gc.to_np(e.region(_abi.R_X0)), got["x"][hold], "X0 = x_closed[N]")
+    ext.same(XS[1:], xs_want[1:], "XS after the shift, away from row 0")
+    ext.same(US, us_want, "US after the shift")
+    ext.same(XS[0], got["x"][hold], "xs[0] = x_closed[N]")
+    ext.same(gc.to_np(e.region(_abi.R_X0)), got["x"][hold], "X0 = x_closed[N]")
     for rid in (_abi.R_KFF, _abi.R_GAPS, _abi.R_VXXF):
         assert not gc.to_np(e.region(rid)).view(np.int64).any(), "region %d is not all zero" % rid
     tf, ti = gc.to_np(twin.region(_abi.R_TRAJ_F)), gc.to_np(twin.region(_abi.R_TRAJ_I))
     for i, row in enumerate((_abi.TF_COST, _abi.TF_STOP, _abi.TF_XREG, _abi.TF_STEP)):
-        _same(got["stat_f"][0, i], tf[row], "stat_f[%d]" % i)
-    _same(got["stat_i"][0, 0], ti[_abi.TI_ITER], "iterations")
-    _same(got["stat_i"][0, 1], ti[_abi.TI_STATUS], "status")
+        ext.same(got["stat_f"][0, i], tf[row], "stat_f[%d]" % i)
+    ext.same(got["stat_i"][0, 0], ti[_abi.TI_ITER], "iterations")
+    ext.same(got["stat_i"][0, 1], ti[_abi.TI_STATUS], "status")
     if getattr(low, "ref_path", None) is not None:
         assert e.reference_row == row_before + hold
 
@@ -189,17 +132,17 @@ def test_the_loop_is_its_own_step_bit_for_bit():
     sp = scenarios.solver_params(sc, solver="SolverFDDP", maxiter=400)
     pk, pb = mp.plants(low, seed=21, rng_range=0.3)
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n * hold, B, low.nx))
-    dev, twin = _fresh(low), _fresh(low)
+    dev, twin = ext.fresh(low), ext.fresh(low)
     one = _raw(dev, sp, n, first, per, hold, pk, pb, dist)
     parts = [_raw(twin, sp, 1, first if s == 0 else per, per, hold, pk, pb, dist[s * hold:(s + 1) * hold]) for s in range(n)]
     for s, p in enumerate(parts):
-        _same(one["x"][s * hold:(s + 1) * hold + 1], p["x"], "x_closed of step %d" % s)
-        _same(one["u"][s * hold:(s + 1) * hold], p["u"], "u_closed of step %d" % s)
-        _same(one["stat_f"][s], p["stat_f"][0], "stat_f of step %d" % s)
-        _same(one["stat_i"][s], p["stat_i"][0], "stat_i of step %d" % s)
+        ext.same(one["x"][s * hold:(s + 1) * hold + 1], p["x"], "x_closed of step %d" % s)
+        ext.same(one["u"][s * hold:(s + 1) * hold], p["u"], "u_closed of step %d" % s)
+        ext.same(one["stat_f"][s], p["stat_f"][0], "stat_f of step %d" % s)
+        ext.same(one["stat_i"][s], p["stat_i"][0], "stat_i of step %d" % s)
         assert (p["failed"] == -1).all()
     assert (one["failed"] == -1).all()
-    for rid in REGIONS:
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(dev.region(rid), twin.region(rid), "region %d" % rid)
     assert dev.reference_row == twin.reference_row == n * hold
     total = np.zeros(B)
@@ -224,20 +167,20 @@ def test_a_failing_trajectory_fails_alone_and_is_counted_in_applied_knots():
     n, hold = 2, 2
     pk, pb = mp.plants(low, seed=21, rng_range=0.3)
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n * hold, 5, low.nx))
-    base = _raw(_fresh(low), sp, n, 3, 2, hold, pk, pb, dist)
+    base = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb, dist)
     assert (base["failed"] == -1).all() and np.isfinite(base["cost"]).all()
     pushed, pb0 = np.array(dist), np.array(pb)
     pushed[0, 1], pushed[1, 3], pb0[4] = 1e31, 1e31, 0.0
-    got = _raw(_fresh(low), sp, n, 3, 2, hold, pk, pb0, pushed)
+    got = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb0, pushed)
     np.testing.assert_array_equal(got["failed"], [-1, 1, -1, 2, 0])
     assert np.isnan(got["cost"][[1, 3, 4]]).all()
     ok = [0, 2]
     for k in ("x", "u"):
-        _same(got[k][:, ok], base[k][:, ok], "%s of the other trajectories" % k)
+        ext.same(got[k][:, ok], base[k][:, ok], "%s of the other trajectories" % k)
     for k in ("stat_f", "stat_i"):
-        _same(got[k][:, :, ok], base[k][:, :, ok], "%s of the other trajectories" % k)
-    _same(got["cost"][ok], base["cost"][ok], "closed cost of the other trajectories")
-    _same(got["x"][:2, 3], base["x"][:2, 3], "trajectory 3 before its push")   # (and up to its failure a trajectory is what it was)
+        ext.same(got[k][:, :, ok], base[k][:, :, ok], "%s of the other trajectories" % k)
+    ext.same(got["cost"][ok], base["cost"][ok], "closed cost of the other trajectories")
+    ext.same(got["x"][:2, 3], base["x"][:2, 3], "trajectory 3 before its push")   # (and up to its failure a trajectory is what it was)
 
 
 # ---- 3. the oracle loop at hold = 1 on a mismatched plant ----
@@ -248,7 +191,7 @@ def test_hold_one_matches_the_oracle_loop_on_a_mismatched_plant(oracle, row):
     the final plan within 1e-6 of the trajectory's scale, step costs within 1e-4 of max(1, |cost|)"""
     ref, pk, pb = mp.loop_reference(oracle, row, H)
     sc, sp, dist = H.parity_case(*row)
-    e = _fresh(scenarios.lower(sc))
+    e = ext.fresh(scenarios.lower(sc))
     r = e.mpc_run_plant(sp, H.N_STEPS, H.FIRST_MAXITER, H.ITERS_PER_STEP, 1, pk, pb, np.ascontiguousarray(dist.transpose(1, 0, 2)))
     xc, uc = gc.to_np(r.xs_closed).transpose(1, 0, 2), gc.to_np(e.pad_u(r.us_closed)).transpose(1, 0, 2)
     for s in range(H.N_STEPS):
@@ -259,7 +202,7 @@ def test_hold_one_matches_the_oracle_loop_on_a_mismatched_plant(oracle, row):
     du = (np.abs(uc - ref["u_closed"]).max(axis=(0, 2)) / scale).max()
     dc = (np.abs(gc.to_np(r.cost).T - ref["cost"]) / np.maximum(1.0, np.abs(ref["cost"]))).max()
     dp = (np.abs(gc.to_np(e.region(_abi.R_XS)) - ref["xs"]).max(axis=(0, 2)) / scale).max()
-    dj = pol.relerr(gc.to_np(r.closed_cost), ref["closed_cost"])
+    dj = gc.relerr(gc.to_np(r.closed_cost), ref["closed_cost"])
     print("%s %s: max rel |dx| %.2e |du| %.2e |dcost| %.2e, final plan %.2e, closed cost %.2e" % (row[0], row[1], dx, du, dc, dp, dj))
     assert dx < 1e-6 and du < 1e-6 and dp < 1e-6, (dx, du, dp)
     assert dc < 1e-4 and dj < 1e-4, (dc, dj)
@@ -283,17 +226,17 @@ def test_defaults_are_aslr_mpc_run_bit_for_bit():
     sp = scenarios.solver_params(sc, maxiter=400)
     n, first, per = 4, 6, 2
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n, low.B, low.nx))
-    a, b = _fresh(low), _fresh(low)
+    a, b = ext.fresh(low), ext.fresh(low)
     got = _raw(a, sp, n, first, per, 1, None, None, dist, False, cost=False, failed=False)
     r = b.mpc_run(sp, n, first, per, np.ascontiguousarray(dist.transpose(1, 0, 2)))
     gc.sync()
-    _same(got["x"], gc.to_np(r.xs_closed).transpose(1, 0, 2), "x_closed")
-    _same(got["u"], gc.to_np(r.us_closed).transpose(1, 0, 2), "u_closed")
+    ext.same(got["x"], gc.to_np(r.xs_closed).transpose(1, 0, 2), "x_closed")
+    ext.same(got["u"], gc.to_np(r.us_closed).transpose(1, 0, 2), "u_closed")
     for i, k in enumerate(("cost", "stop", "x_reg", "step")):
-        _same(got["stat_f"][:, i], gc.to_np(getattr(r, k)).T, k)
-    _same(got["stat_i"][:, 0], gc.to_np(r.iters).T, "iters")
-    _same(got["stat_i"][:, 1], gc.to_np(r.status).T, "status")
-    for rid in REGIONS:
+        ext.same(got["stat_f"][:, i], gc.to_np(getattr(r, k)).T, k)
+    ext.same(got["stat_i"][:, 0], gc.to_np(r.iters).T, "iters")
+    ext.same(got["stat_i"][:, 1], gc.to_np(r.status).T, "status")
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(a.region(rid), b.region(rid), "region %d" % rid)
     assert int(r.iters[:, 0].min()) >= 1
 
@@ -309,16 +252,16 @@ def test_the_nominal_plant_is_neutral_and_a_plant_off_is_not(case):
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (1, low.B, low.nx))
     nom = lambda f: np.array([pol.nominal_diag(low, b, f) for b in range(low.B)])
     kn, bn = (nom("K") if low.dam == _abi.DAM_SEA else None), nom("B")
-    base = _fresh(low).mpc_run(sp, 1, 6, 2, np.ascontiguousarray(dist.transpose(1, 0, 2)))
+    base = ext.fresh(low).mpc_run(sp, 1, 6, 2, np.ascontiguousarray(dist.transpose(1, 0, 2)))
     want = gc.to_np(base.xs_closed).transpose(1, 0, 2)
-    got = _raw(_fresh(low), sp, 1, 6, 2, 1, kn, bn, dist)
+    got = _raw(ext.fresh(low), sp, 1, 6, 2, 1, kn, bn, dist)
     scale = np.maximum(1.0, np.abs(want).max(axis=(0, 2)))
     err = (np.abs(got["x"][1] - want[1]).max(axis=1) / scale).max()
     print("%s: x_closed[1] with the nominal plant given against aslr_mpc_run: %.2e of scale" % (case, err))
     assert err < 1e-11
-    _same(got["x"][0], want[0], "x_closed[0]")
+    ext.same(got["x"][0], want[0], "x_closed[0]")
     assert np.isfinite(got["cost"]).all() and (got["failed"] == -1).all()
-    off = _raw(_fresh(low), sp, 1, 6, 2, 1, None if kn is None else 1.2 * kn, 1.2 * bn, dist)
+    off = _raw(ext.fresh(low), sp, 1, 6, 2, 1, None if kn is None else 1.2 * kn, 1.2 * bn, dist)
     assert np.abs(off["x"][1] - want[1]).max() > 1e-6
 
 
@@ -330,32 +273,22 @@ def test_results_do_not_depend_on_subshards_or_batch():
     n, hold, first, per = 3, 2, 6, 2
     pk, pb = mp.plants(low, seed=21, rng_range=0.3)
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n * hold, 65, low.nx))
-    e1, e2 = _fresh(low), _fresh(low, 2)
+    e1, e2 = ext.fresh(low), ext.fresh(low, 2)
     r1, r2 = (_raw(e, sp, n, first, per, hold, pk, pb, dist) for e in (e1, e2))
-    _same_runs(r1, r2, "two sub-shards")
-    for rid in REGIONS:
+    ext.same(r1, r2, "two sub-shards")
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(e1.region(rid), e2.region(rid), "region %d with two sub-shards" % rid)
     five = dict(sc, x0=sc["x0"][:5], frame_refs=sc["frame_refs"][:5])
-    e3 = _fresh(scenarios.lower(five))
+    e3 = ext.fresh(scenarios.lower(five))
     r3 = _raw(e3, sp, n, first, per, hold, pk[:5], pb[:5], dist[:, :5])
     cut = {k: (v[:5] if k in ("cost", "failed") else v[:, :5] if k in ("x", "u") else v[:, :, :5]) for k, v in r1.items()}
-    _same_runs(cut, r3, "trajectories 0..4 of 65 in a batch of 5")
+    ext.same(cut, r3, "trajectories 0..4 of 65 in a batch of 5")
     for rid in (_abi.R_XS, _abi.R_US):
         gc.same_bits(e1.region(rid)[:, :5], e3.region(rid), "region %d of the first five trajectories" % rid)
     assert (r1["stat_i"][:, 0].max(axis=1) >= 1).all()
 
 
 # ---- 6. refusals ----
-def _solve_matches_a_fresh_handle(e, low, sp):
-    fresh = gc.engine(low)
-    for h in (e, fresh):
-        h.set_candidate(None, None)
-        h.solve(sp, poll_every=4)
-    gc.sync()
-    for rid in REGIONS[:4]:
-        gc.same_bits(e.region(rid), fresh.region(rid), "region %d after a refused aslr_mpc_run_plant" % rid)
-
-
 def _refused(e, sp, word, *args, **kw):
     msg = _raw(e, sp, *args, expect=_abi.E_INVALID, **kw)
     assert msg.startswith("aslr_mpc_run_plant:") and word in msg, msg
@@ -366,7 +299,7 @@ def test_refusals_enqueue_nothing_and_leave_the_handle_usable():
     sc = _sea(4, 6)
     sp = scenarios.solver_params(sc, solver="SolverFDDP", maxiter=20)
     low = scenarios.lower(sc)
-    e = _fresh(low)
+    e = ext.fresh(low)
     ones = np.ones((4, 2))
     # what aslr_mpc_run refuses
     for args in ((0, 5, 2), (2, 0, 2), (2, 5, 0)):
@@ -377,38 +310,38 @@ def test_refusals_enqueue_nothing_and_leave_the_handle_usable():
     # the hold
     for hold in (0, -1, 7):
         _refused(e, sp, "hold", 2, 5, 2, hold=hold)
-    _solve_matches_a_fresh_handle(e, low, sp)
+    ext.solve_matches_a_fresh_handle(e, low, sp, ext.SOLVE_REGIONS, AFTER)
     assert _raw(e, sp, 2, 5, 2, 6, ones, 1e-2 * ones)["x"].shape == (13, 4, 8)   # (hold = T runs, on the same handle)
     # two distinct running models
     mixed = dict(sc)
     mixed["running"] = [sc["running"][0]] * 3 + [copy.copy(sc["running"][0])] * 3
     lowm = scenarios.lower(mixed)
-    em = _fresh(lowm)
+    em = ext.fresh(lowm)
     _refused(em, sp, "more than one action model", 2, 5, 2, hold=2)
-    _solve_matches_a_fresh_handle(em, lowm, sp)
+    ext.solve_matches_a_fresh_handle(em, lowm, sp, ext.SOLVE_REGIONS, AFTER)
     # plant_stiffness on a VSA model
     scv = scenarios.two_dof_vsa_boxddp(B=4, T=6, seed=4)
     lowv, spv = scenarios.lower(scv), scenarios.solver_params(scv, maxiter=20)
-    ev = _fresh(lowv)
+    ev = ext.fresh(lowv)
     _refused(ev, spv, "VSA", 2, 5, 2, hold=2, pk=ones)
-    _solve_matches_a_fresh_handle(ev, lowv, spv)
+    ext.solve_matches_a_fresh_handle(ev, lowv, spv, ext.SOLVE_REGIONS, AFTER)
     # K that is not diagonal: refused with a plant argument, run without one
     lown = scenarios.lower(_sea(2, 3))
     for i in range(lown.desc.nmodels):   # (the lowered description is what aslr_problem_create reads)
         lown.desc.models[i].K[1] = lown.desc.models[i].K[2] = 0.1
-    en = _fresh(lown)
+    en = ext.fresh(lown)
     _refused(en, sp, "diagonal", 2, 5, 2, hold=2, pb=np.full((2, 2), 1e-2))
     assert np.isfinite(_raw(en, sp, 2, 5, 2, 2)["cost"]).all()
     # a 7-joint handle
     sc7 = scenarios.talos_arm_sea(B=2, T=4, seed=4)
     low7, sp7 = scenarios.lower(sc7), scenarios.solver_params(sc7, maxiter=10)
-    e7 = _fresh(low7)
+    e7 = ext.fresh(low7)
     _refused(e7, sp7, "7-joint", 2, 5, 2, hold=2)
     _refused(e7, sp7, "nx = 8", 2, 5, 2, hold=1, cost=False, failed=False)
-    _solve_matches_a_fresh_handle(e7, low7, sp7)
+    ext.solve_matches_a_fresh_handle(e7, low7, sp7, ext.SOLVE_REGIONS, AFTER)
     # (7, VSA) with SolverDDP: aslr_mpc_run's refusal comes first
     sc7v = scenarios.talos_arm_vsa(B=2, T=4)
-    e7v = _fresh(scenarios.lower(sc7v))
+    e7v = ext.fresh(scenarios.lower(sc7v))
     _refused(e7v, scenarios.solver_params(sc7v, solver="SolverDDP", maxiter=5), "built for SolverBoxDDP only", 2, 5, 2, hold=2)
 
 

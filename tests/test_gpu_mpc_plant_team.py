@@ -5,14 +5,15 @@ As tests/test_gpu_mpc_plant.py: the oracle's solve returns no gains, so the call
 ONE control step against the definition (a twin handle's plain solve gives the plan and the gains; the plant phase is a numpy
 loop over the oracle's knot), then the loop against itself, bit for bit; at hold = 1, where no gain is read, the whole loop
 against the oracle's.  Kernel outputs are held to 1e-9 relative, max |a - b| / (1 + |b|); tests/test_mpc_plant_team_host.py
-shows that the inputs are conditioned for it.  Shapes: tests/_mpc_plant_team.py.  x_closed and u_closed sit in buffers of the
-test's own, followed by guard words that must survive."""
+shows that the inputs are conditioned for it.  Shapes: tests/_mpc_plant_team.py.  Every output sits in a guarded buffer of
+tests/_ext_call.py."""
 import copy
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import _ext_call as ext
 import _gpu_case as gc
 import _mpc_plant as mp
 import _mpc_plant_team as mt
@@ -25,71 +26,14 @@ from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
 
-REGIONS = (_abi.R_XS, _abi.R_US, _abi.R_TRAJ_F, _abi.R_TRAJ_I, _abi.R_X0)
-GUARD, SENTINEL = 64, -7.25
-KEYS = ("x", "u", "stat_f", "stat_i", "cost", "failed")
 NAME = mt.NAME
+AFTER = "after a refused " + NAME
 
 
-def _raw(e, sp, n, first, per, hold=1, pk=None, pb=None, dist=None, clamp=False, cost=True, failed=True, expect=_abi.OK,
-         name=NAME):
-    """the entry point `name`.  pk, pb: batch-major [B, nj] or None (NULL); dist: time-major [N, B, nx] or None; cost /
-    failed: whether closed_cost / failed_knot are given.  -> dict of time-major numpy arrays: x [N+1, B, nx], u [N, B, nu],
-    stat_f [n, 4, B], stat_i [n, 2, B], cost [B], failed [B] (None where not given); the guards behind x and u must be
-    untouched.  expect != OK: -> the message of the refusal, and nothing was written."""
-    import torch
-    N = max(n, 0) * max(hold, 0)
-    dev = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=e.device)
-    tk, tb, td = dev(None if pk is None else np.transpose(pk)), dev(None if pb is None else np.transpose(pb)), dev(dist)
-    nxw, nuw = (N + 1) * e.B * e.nx, N * e.B * e.nu
-    x = torch.full((nxw + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    u = torch.full((nuw + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    sf = torch.full((max(n, 1), 4, e.B), SENTINEL, dtype=torch.float64, device=e.device)
-    si = torch.full((max(n, 1), 2, e.B), -7, dtype=torch.int32, device=e.device)
-    cc = torch.full((e.B,), SENTINEL, dtype=torch.float64, device=e.device) if cost else None
-    fk = torch.full((e.B,), -7, dtype=torch.int32, device=e.device) if failed else None
-    mpc = _abi.Mpc()
-    mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, first, per
-    mpc.disturbance = td.data_ptr() if td is not None else None
-    mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = x.data_ptr(), u.data_ptr(), sf.data_ptr(), si.data_ptr()
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(e.device):
-        rc = getattr(e.lib, name)(e.handle, C.byref(sp), C.byref(mpc), hold, ptr(tk), ptr(tb), 1 if clamp else 0, ptr(cc), ptr(fk),
-                                  e._stream())
-    gc.sync()
-    if expect != _abi.OK:
-        assert rc == expect, rc
-        for t, s in ((x, SENTINEL), (u, SENTINEL), (sf, SENTINEL), (si, -7), (cc, SENTINEL), (fk, -7)):
-            assert t is None or (t == s).all(), "a refused call wrote to an output"
-        return e.lib.aslr_last_error().decode()
-    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
-    xa, ua = gc.to_np(x), gc.to_np(u)
-    assert (xa[nxw:] == SENTINEL).all() and (ua[nuw:] == SENTINEL).all(), "a guard was overwritten"
-    return dict(x=xa[:nxw].reshape(N + 1, e.B, e.nx), u=ua[:nuw].reshape(N, e.B, e.nu), stat_f=gc.to_np(sf), stat_i=gc.to_np(si),
-                cost=None if cc is None else gc.to_np(cc), failed=None if fk is None else gc.to_np(fk))
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def _same(a, b, what):
-    np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=what)
-
-
-def _same_runs(a, b, what, keys=KEYS):
-    for k in keys:
-        if a[k] is not None or b[k] is not None:
-            _same(a[k], b[k], "%s: %s" % (what, k))
-
-
-def _fresh(low, nsub=1):
-    e = gc.engine(low)
-    if nsub > 1:
-        e.set_subshards(nsub)
-    e.set_candidate(None, None)
-    return e
+def _raw(e, *args, name=NAME, **kw):
+    """ext.mpc_run_plant(e, name, sp, n, first, per, hold=1, pk=None, pb=None, dist=None, clamp=False, cost=True, failed=True,
+    expect=OK)"""
+    return ext.mpc_run_plant(e, name, *args, **kw)
 
 
 def _arm(name, B, T):
@@ -114,7 +58,7 @@ def test_one_control_step_is_the_definition(oracle, key):
     (tests/_mpc_plant_team.py says why)."""
     c = mt.one_step(key)
     low, sp, hold, clamp, pk, pb, dist = (c[k] for k in ("low", "sp", "hold", "clamp", "pk", "pb", "dist"))
-    e, twin = _fresh(low), _fresh(low)
+    e, twin = ext.fresh(low), ext.fresh(low)
     row_before = e.reference_row
     got = _raw(e, sp, 1, 3, 3, hold, pk, pb, dist, clamp)
     twin.solve(sp, poll_every=0)
@@ -123,7 +67,7 @@ def test_one_control_step_is_the_definition(oracle, key):
     assert (gc.to_np(twin.traj_i(_abi.TI_ITER)) >= 1).any() and (hold == 1 or np.abs(K[1:hold]).max() > 1e-3)
     want = mt.reference(oracle, c, X, U[..., :low.nu], K[..., :low.nu, :])
     assert (want["failed"] == -1).all()
-    errs = dict(x=pol.relerr(got["x"], want["x"]), u=pol.relerr(got["u"][..., :low.nu], want["u"]), cost=pol.relerr(got["cost"], want["cost"]))
+    errs = dict(x=gc.relerr(got["x"], want["x"]), u=gc.relerr(got["u"][..., :low.nu], want["u"]), cost=gc.relerr(got["cost"], want["cost"]))
     print("%s: relerr %s" % (key, {k: "%.2e" % v for k, v in errs.items()}))
     assert max(errs.values()) < 1e-9, errs
     np.testing.assert_array_equal(got["failed"], want["failed"])
@@ -132,27 +76,27 @@ def test_one_control_step_is_the_definition(oracle, key):
     if clamp:
         assert want["bound"].any() and not want["bound"].all(), "the narrowed box must move some control of the reference, not on every trajectory"
         free = mt.reference(oracle, c, X, U[..., :low.nu], K[..., :low.nu, :], clamp=False)
-        assert pol.relerr(free["u"], want["u"]) > 1e-3   # ... and the clamp is what the kernel applied
+        assert gc.relerr(free["u"], want["u"]) > 1e-3   # ... and the clamp is what the kernel applied
     if c["table"] and c["arrays"]:   # the plants given on top of the table are what the kernel used, not the table's rows
         table = mt.reference(oracle, c, X, U[..., :low.nu], K[..., :low.nu, :], plants=False)
-        assert pol.relerr(table["x"], want["x"]) > 1e-6
-    _same(got["x"][0], X[0], "x_closed[0] is XS[0]")
+        assert gc.relerr(table["x"], want["x"]) > 1e-6
+    ext.same(got["x"][0], X[0], "x_closed[0] is XS[0]")
     if not clamp:
-        _same(got["u"][0], U[0], "u_closed[0] is US[0]")
+        ext.same(got["u"][0], U[0], "u_closed[0] is US[0]")
     # the shift, exactly: rows of the twin's plan, the last one repeated; x+ in xs[0], X0 and x_closed[N]
     xs_want, us_want = mp.shifted(X, U, hold, got["x"][hold])
     XS, US = gc.to_np(e.region(_abi.R_XS)), gc.to_np(e.region(_abi.R_US))
-    _same(XS[1:], xs_want[1:], "XS after the shift, away from row 0")
-    _same(US, us_want, "US after the shift")
-    _same(XS[0], got["x"][hold], "xs[0] = x_closed[N]")
-    _same(gc.to_np(e.region(_abi.R_X0)), got["x"][hold], "X0 = x_closed[N]")
+    ext.same(XS[1:], xs_want[1:], "XS after the shift, away from row 0")
+    ext.same(US, us_want, "US after the shift")
+    ext.same(XS[0], got["x"][hold], "xs[0] = x_closed[N]")
+    ext.same(gc.to_np(e.region(_abi.R_X0)), got["x"][hold], "X0 = x_closed[N]")
     for rid in (_abi.R_KFF, _abi.R_GAPS, _abi.R_VXXF):
         assert not gc.to_np(e.region(rid)).view(np.int64).any(), "region %d is not all zero" % rid
     tf, ti = gc.to_np(twin.region(_abi.R_TRAJ_F)), gc.to_np(twin.region(_abi.R_TRAJ_I))
     for i, row in enumerate((_abi.TF_COST, _abi.TF_STOP, _abi.TF_XREG, _abi.TF_STEP)):
-        _same(got["stat_f"][0, i], tf[row], "stat_f[%d]" % i)
-    _same(got["stat_i"][0, 0], ti[_abi.TI_ITER], "iterations")
-    _same(got["stat_i"][0, 1], ti[_abi.TI_STATUS], "status")
+        ext.same(got["stat_f"][0, i], tf[row], "stat_f[%d]" % i)
+    ext.same(got["stat_i"][0, 0], ti[_abi.TI_ITER], "iterations")
+    ext.same(got["stat_i"][0, 1], ti[_abi.TI_STATUS], "status")
     if getattr(low, "ref_path", None) is not None:
         assert e.reference_row == row_before + hold
 
@@ -164,17 +108,17 @@ def test_the_loop_is_its_own_step_bit_for_bit(name):
     n, hold, first, per = 3, 2, 3, 2
     sc, low, sp = _arm(name, 9, 6)
     pk, pb, dist = _plants_and_noise(low, n * hold)
-    dev, twin = _fresh(low), _fresh(low)
+    dev, twin = ext.fresh(low), ext.fresh(low)
     one = _raw(dev, sp, n, first, per, hold, pk, pb, dist)
     parts = [_raw(twin, sp, 1, first if s == 0 else per, per, hold, pk, pb, dist[s * hold:(s + 1) * hold]) for s in range(n)]
     for s, p in enumerate(parts):
-        _same(one["x"][s * hold:(s + 1) * hold + 1], p["x"], "x_closed of step %d" % s)
-        _same(one["u"][s * hold:(s + 1) * hold], p["u"], "u_closed of step %d" % s)
-        _same(one["stat_f"][s], p["stat_f"][0], "stat_f of step %d" % s)
-        _same(one["stat_i"][s], p["stat_i"][0], "stat_i of step %d" % s)
+        ext.same(one["x"][s * hold:(s + 1) * hold + 1], p["x"], "x_closed of step %d" % s)
+        ext.same(one["u"][s * hold:(s + 1) * hold], p["u"], "u_closed of step %d" % s)
+        ext.same(one["stat_f"][s], p["stat_f"][0], "stat_f of step %d" % s)
+        ext.same(one["stat_i"][s], p["stat_i"][0], "stat_i of step %d" % s)
         assert (p["failed"] == -1).all()
     assert (one["failed"] == -1).all()
-    for rid in REGIONS:
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(dev.region(rid), twin.region(rid), "region %d" % rid)
     total = np.zeros(low.B)
     for p in parts:
@@ -194,7 +138,7 @@ def test_hold_one_matches_the_oracle_loop_on_a_mismatched_plant(oracle, row):
     plan within 1e-6 of the trajectory's scale, step costs and the closed cost within 1e-4 of max(1, |cost|)"""
     ref, pk, pb = mp.loop_reference(oracle, row, H)
     sc, sp, dist = H.parity_case(*row)
-    e = _fresh(scenarios.lower(sc))
+    e = ext.fresh(scenarios.lower(sc))
     r = e.mpc_run_plant(sp, H.N_STEPS, H.FIRST_MAXITER, H.ITERS_PER_STEP, 1, pk, pb, np.ascontiguousarray(dist.transpose(1, 0, 2)))
     xc, uc = gc.to_np(r.xs_closed).transpose(1, 0, 2), gc.to_np(e.pad_u(r.us_closed)).transpose(1, 0, 2)
     for s in range(H.N_STEPS):
@@ -218,17 +162,17 @@ def test_defaults_are_aslr_mpc_run_bit_for_bit():
     sc, low, sp = _arm("talos_arm_sea", 9, 6)
     n, first, per = 3, 3, 2
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n, low.B, low.nx))
-    a, b = _fresh(low), _fresh(low)
+    a, b = ext.fresh(low), ext.fresh(low)
     got = _raw(a, sp, n, first, per, 1, None, None, dist, False, cost=False, failed=False)
     r = b.mpc_run(sp, n, first, per, np.ascontiguousarray(dist.transpose(1, 0, 2)))
     gc.sync()
-    _same(got["x"], gc.to_np(r.xs_closed).transpose(1, 0, 2), "x_closed")
-    _same(got["u"], gc.to_np(b.pad_u(r.us_closed)).transpose(1, 0, 2), "u_closed")
+    ext.same(got["x"], gc.to_np(r.xs_closed).transpose(1, 0, 2), "x_closed")
+    ext.same(got["u"], gc.to_np(b.pad_u(r.us_closed)).transpose(1, 0, 2), "u_closed")
     for i, k in enumerate(("cost", "stop", "x_reg", "step")):
-        _same(got["stat_f"][:, i], gc.to_np(getattr(r, k)).T, k)
-    _same(got["stat_i"][:, 0], gc.to_np(r.iters).T, "iters")
-    _same(got["stat_i"][:, 1], gc.to_np(r.status).T, "status")
-    for rid in REGIONS:
+        ext.same(got["stat_f"][:, i], gc.to_np(getattr(r, k)).T, k)
+    ext.same(got["stat_i"][:, 0], gc.to_np(r.iters).T, "iters")
+    ext.same(got["stat_i"][:, 1], gc.to_np(r.status).T, "status")
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(a.region(rid), b.region(rid), "region %d" % rid)
     assert int(r.iters[:, 0].min()) >= 1
 
@@ -242,16 +186,16 @@ def test_the_nominal_plant_is_neutral_and_a_plant_off_is_not(name):
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (1, low.B, low.nx))
     nom = lambda f: np.array([pol.nominal_diag(low, b, f) for b in range(low.B)])
     kn, bn = (nom("K") if low.dam == _abi.DAM_SEA else None), nom("B")
-    base = _fresh(low).mpc_run(sp, 1, 3, 2, np.ascontiguousarray(dist.transpose(1, 0, 2)))
+    base = ext.fresh(low).mpc_run(sp, 1, 3, 2, np.ascontiguousarray(dist.transpose(1, 0, 2)))
     want = gc.to_np(base.xs_closed).transpose(1, 0, 2)
-    got = _raw(_fresh(low), sp, 1, 3, 2, 1, kn, bn, dist)
+    got = _raw(ext.fresh(low), sp, 1, 3, 2, 1, kn, bn, dist)
     scale = np.maximum(1.0, np.abs(want).max(axis=(0, 2)))
     err = (np.abs(got["x"][1] - want[1]).max(axis=1) / scale).max()
     print("%s: x_closed[1] with the nominal plant given against aslr_mpc_run: %.2e of scale" % (name, err))
     assert err < 1e-11
-    _same(got["x"][0], want[0], "x_closed[0]")
+    ext.same(got["x"][0], want[0], "x_closed[0]")
     assert np.isfinite(got["cost"]).all() and (got["failed"] == -1).all()
-    off = _raw(_fresh(low), sp, 1, 3, 2, 1, None if kn is None else 1.2 * kn, 1.2 * bn, dist)
+    off = _raw(ext.fresh(low), sp, 1, 3, 2, 1, None if kn is None else 1.2 * kn, 1.2 * bn, dist)
     assert np.abs(off["x"][1] - want[1]).max() > 1e-6
 
 
@@ -262,20 +206,20 @@ def test_results_do_not_depend_on_subshards_or_batch():
     n, hold, first, per = 2, 2, 3, 2
     sc, low, sp = _arm("talos_arm_sea", 65, 4)
     pk, pb, dist = _plants_and_noise(low, n * hold)
-    e1, e2 = _fresh(low), _fresh(low, 2)
+    e1, e2 = ext.fresh(low), ext.fresh(low, 2)
     r1, r2 = (_raw(e, sp, n, first, per, hold, pk, pb, dist) for e in (e1, e2))
-    _same_runs(r1, r2, "two sub-shards")
-    for rid in REGIONS:
+    ext.same(r1, r2, "two sub-shards")
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(e1.region(rid), e2.region(rid), "region %d with two sub-shards" % rid)
     sc9, low9, _ = _arm("talos_arm_sea", 9, 4)
     pk9, pb9, dist9 = _plants_and_noise(low9, n * hold)
-    e9 = _fresh(low9)
+    e9 = ext.fresh(low9)
     r9 = _raw(e9, sp, n, first, per, hold, pk9, pb9, dist9)
     three = dict(sc9, x0=sc9["x0"][:3], frame_refs=sc9["frame_refs"][:3])
-    e3 = _fresh(scenarios.lower(three))
+    e3 = ext.fresh(scenarios.lower(three))
     r3 = _raw(e3, sp, n, first, per, hold, pk9[:3], pb9[:3], dist9[:, :3])
     cut = {k: (v[:3] if k in ("cost", "failed") else v[:, :3] if k in ("x", "u") else v[:, :, :3]) for k, v in r9.items()}
-    _same_runs(cut, r3, "trajectories 0..2 of 9 in a batch of 3")
+    ext.same(cut, r3, "trajectories 0..2 of 9 in a batch of 3")
     for rid in (_abi.R_XS, _abi.R_US):
         gc.same_bits(e9.region(rid)[:, :3], e3.region(rid), "region %d of the first three trajectories" % rid)
     assert (r9["stat_i"][:, 0].max(axis=1) >= 1).all()
@@ -292,20 +236,20 @@ def test_a_failing_trajectory_fails_alone_and_is_counted_in_applied_knots(name):
     n, hold = 2, 2
     sc, low, sp = _arm(name, 9, 4)
     pk, pb, dist = _plants_and_noise(low, n * hold)
-    base = _raw(_fresh(low), sp, n, 3, 2, hold, pk, pb, dist)
+    base = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb, dist)
     assert (base["failed"] == -1).all() and np.isfinite(base["cost"]).all()
     pushed, pb0 = np.array(dist), np.array(pb)
     pushed[2, 2], pb0[4] = 1e31, 0.0
-    got = _raw(_fresh(low), sp, n, 3, 2, hold, pk, pb0, pushed)
+    got = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb0, pushed)
     np.testing.assert_array_equal(got["failed"], [-1, -1, 3, -1, 0, -1, -1, -1, -1])
     assert np.isnan(got["cost"][[2, 4]]).all()
     ok = [0, 1, 3, 5, 6, 7, 8]
     for k in ("x", "u"):
-        _same(got[k][:, ok], base[k][:, ok], "%s of the other trajectories" % k)
+        ext.same(got[k][:, ok], base[k][:, ok], "%s of the other trajectories" % k)
     for k in ("stat_f", "stat_i"):
-        _same(got[k][:, :, ok], base[k][:, :, ok], "%s of the other trajectories" % k)
-    _same(got["cost"][ok], base["cost"][ok], "closed cost of the other trajectories")
-    _same(got["x"][:3, 2], base["x"][:3, 2], "trajectory 2 before its push")   # (and up to its failure a trajectory is what it was)
+        ext.same(got[k][:, :, ok], base[k][:, :, ok], "%s of the other trajectories" % k)
+    ext.same(got["cost"][ok], base["cost"][ok], "closed cost of the other trajectories")
+    ext.same(got["x"][:3, 2], base["x"][:3, 2], "trajectory 2 before its push")   # (and up to its failure a trajectory is what it was)
 
 
 # ---- 7. against the other kernel ----
@@ -321,7 +265,7 @@ def test_one_step_over_the_whole_horizon_is_the_policy_rollout(oracle, name):
     sc, low, sp = _arm(name, 9, 4)
     B, T = low.B, low.T
     pk, pb, _ = _plants_and_noise(low, T)
-    e, twin = _fresh(low), _fresh(low)
+    e, twin = ext.fresh(low), ext.fresh(low)
     got = _raw(e, sp, 1, 3, 3, T, pk, pb, None)
     twin.solve(sp, poll_every=0)
     roll = twin.policy_rollout(1, None if pk is None else pk[:, None], pb[:, None], keep_trajectories=True)
@@ -329,14 +273,14 @@ def test_one_step_over_the_whole_horizon_is_the_policy_rollout(oracle, name):
     assert np.abs(gc.to_np(twin.region(_abi.R_KGAIN))[1:]).max() > 1e-3
     xs = gc.to_np(roll.xs)[:, 0].transpose(1, 0, 2)
     us = gc.to_np(twin.pad_u(roll.us[:, 0])).transpose(1, 0, 2)
-    ex, eu = pol.relerr(got["x"], xs), pol.relerr(got["u"], us)
+    ex, eu = gc.relerr(got["x"], xs), gc.relerr(got["u"], us)
     term = np.array([oracle.knot(_traj_oracle.single(low, i), int(low.node_model[T]), xs[T, i], None,
                                  frame_ref=None if low.frame_ref is None else low.frame_ref[i], diff=False)["cost"] for i in range(B)])
-    ec = pol.relerr(got["cost"], gc.to_np(roll.cost)[:, 0] - term)
+    ec = gc.relerr(got["cost"], gc.to_np(roll.cost)[:, 0] - term)
     print("%s: against the policy roll-out: x %.2e, u %.2e, cost %.2e" % (name, ex, eu, ec))
     assert (got["failed"] == -1).all() and (gc.to_np(roll.failed_knot) == -1).all()
-    _same(got["x"], xs, "x_closed against xs_closed")  # (gc.same_bits on numpy arrays)
-    _same(got["u"], us, "u_closed against us_closed")
+    ext.same(got["x"], xs, "x_closed against xs_closed")  # (gc.same_bits on numpy arrays)
+    ext.same(got["u"], us, "u_closed against us_closed")
     assert ec < 1e-9, ec
     assert np.abs(got["x"][1:] - gc.to_np(twin.region(_abi.R_XS))[1:]).max() > 1e-6   # (the plant moved the loop off the plan)
 
@@ -349,26 +293,16 @@ def test_two_joint_handles_get_the_bits_of_aslr_mpc_run_plant(case):
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc, solver="SolverFDDP" if case == "sea" else "SolverBoxDDP", maxiter=3)
     pk, pb, dist = _plants_and_noise(low, n * hold)
-    a, b = _fresh(low), _fresh(low)
+    a, b = ext.fresh(low), ext.fresh(low)
     new = _raw(a, sp, n, first, per, hold, pk, pb, dist, case != "sea")
     old = _raw(b, sp, n, first, per, hold, pk, pb, dist, case != "sea", name="aslr_mpc_run_plant")
-    _same_runs(new, old, "aslr_mpc_run_plant_all against aslr_mpc_run_plant")
-    for rid in REGIONS:
+    ext.same(new, old, "aslr_mpc_run_plant_all against aslr_mpc_run_plant")
+    for rid in ext.MPC_REGIONS:
         gc.same_bits(a.region(rid), b.region(rid), "region %d" % rid)
     assert (new["failed"] == -1).all() and (new["stat_i"][:, 0].max(axis=1) >= 1).all()
 
 
 # ---- 9. refusals ----
-def _solve_matches_a_fresh_handle(e, low, sp):
-    fresh = gc.engine(low)
-    for h in (e, fresh):
-        h.set_candidate(None, None)
-        h.solve(sp, poll_every=4)
-    gc.sync()
-    for rid in REGIONS[:4]:
-        gc.same_bits(e.region(rid), fresh.region(rid), "region %d after a refused %s" % (rid, NAME))
-
-
 def _refused(e, sp, word, *args, **kw):
     name = kw.get("name", NAME)
     msg = _raw(e, sp, *args, expect=_abi.E_INVALID, **kw)
@@ -378,7 +312,7 @@ def _refused(e, sp, word, *args, **kw):
 
 def test_refusals_enqueue_nothing_and_leave_the_handle_usable():
     sc, low, sp = _arm("talos_arm_sea", 3, 4)
-    e = _fresh(low)
+    e = ext.fresh(low)
     ones = np.ones((3, 7))
     # what aslr_mpc_run refuses
     for args in ((0, 3, 2), (2, 0, 2), (2, 3, 0)):
@@ -390,46 +324,41 @@ def test_refusals_enqueue_nothing_and_leave_the_handle_usable():
     for hold in (0, -1, 5):
         _refused(e, sp, "hold", 2, 3, 2, hold=hold)
     # n_steps * hold beyond INT32_MAX: refused before anything is sized by it (the small buffers here are never touched)
-    import torch
-    buf = torch.full((64,), SENTINEL, dtype=torch.float64, device=e.device)
-    ibuf = torch.full((64,), -7, dtype=torch.int32, device=e.device)
+    small = ext.outputs(e.device, {"f": (0,), "i": (0,)}, ("f", "i"), int32=("i",))   # (GUARD words each)
     mpc = _abi.Mpc()
     mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = 2 ** 29, 3, 2
-    mpc.x_closed, mpc.u_closed, mpc.stat_f, mpc.stat_i = buf.data_ptr(), buf.data_ptr(), buf.data_ptr(), ibuf.data_ptr()
-    with torch.cuda.device(e.device):
-        assert e.lib.aslr_mpc_run_plant_all(e.handle, C.byref(sp), C.byref(mpc), 4, None, None, 0, None, None, e._stream()) == _abi.E_INVALID
-    msg = e.lib.aslr_last_error().decode()
+    mpc.x_closed = mpc.u_closed = mpc.stat_f = small["f"].buf.data_ptr()
+    mpc.stat_i = small["i"].buf.data_ptr()
+    msg = ext.call(e, NAME, [e.handle, C.byref(sp), C.byref(mpc), 4, None, None, 0, None, None, e._stream()], small, _abi.E_INVALID)
     assert msg.startswith(NAME + ":") and "overflow" in msg, msg
-    gc.sync()
-    assert (buf == SENTINEL).all() and (ibuf == -7).all()
-    _solve_matches_a_fresh_handle(e, low, sp)
+    ext.solve_matches_a_fresh_handle(e, low, sp, ext.SOLVE_REGIONS, AFTER)
     assert _raw(e, sp, 2, 3, 2, 4, ones * pol.nominal_diag(low, 0, "K"), ones * pol.nominal_diag(low, 0, "B"))["x"].shape == (9, 3, 28)   # (hold = T runs, on the same handle)
     # two distinct running models
     mixed = dict(sc)
     mixed["running"] = [sc["running"][0]] * 2 + [copy.copy(sc["running"][0])] * 2
     lowm = scenarios.lower(mixed)
-    em = _fresh(lowm)
+    em = ext.fresh(lowm)
     _refused(em, sp, "more than one action model", 2, 3, 2, hold=2)
-    _solve_matches_a_fresh_handle(em, lowm, sp)
+    ext.solve_matches_a_fresh_handle(em, lowm, sp, ext.SOLVE_REGIONS, AFTER)
     # plant_stiffness on a VSA model; (7, VSA) with SolverDDP: aslr_mpc_run's refusal
     scv, lowv, spv = _arm("talos_arm_vsa", 3, 4)
-    ev = _fresh(lowv)
+    ev = ext.fresh(lowv)
     _refused(ev, spv, "VSA", 2, 3, 2, hold=2, pk=ones)
     _refused(ev, scenarios.solver_params(scv, solver="SolverDDP", maxiter=3), "built for SolverBoxDDP only", 2, 3, 2, hold=2)
-    _solve_matches_a_fresh_handle(ev, lowv, spv)
+    ext.solve_matches_a_fresh_handle(ev, lowv, spv, ext.SOLVE_REGIONS, AFTER)
     # K that is not diagonal: refused with a plant argument, run on the model's full rows without one
     lown = scenarios.lower(scenarios.talos_arm_sea(B=3, T=4, seed=mt.SCENARIO_SEED))
     for i in range(lown.desc.nmodels):   # (the lowered description is what aslr_problem_create reads)
         lown.desc.models[i].K[1] = lown.desc.models[i].K[7] = 0.03
-    en = _fresh(lown)
+    en = ext.fresh(lown)
     _refused(en, sp, "diagonal", 2, 3, 2, hold=2, pb=np.full((3, 7), 1e-2))
-    _solve_matches_a_fresh_handle(en, lown, sp)
+    ext.solve_matches_a_fresh_handle(en, lown, sp, ext.SOLVE_REGIONS, AFTER)
     # the old entry point still refuses the 7-joint handle, in its own name, also when nothing is asked of the plant
-    e7 = _fresh(low)   # (the run above moved X0 of `e`)
+    e7 = ext.fresh(low)   # (the run above moved X0 of `e`)
     msg = _refused(e7, sp, "7-joint", 2, 3, 2, hold=2, name="aslr_mpc_run_plant")
     assert "nx = 8" in msg
     _refused(e7, sp, "nx = 8", 2, 3, 2, hold=1, cost=False, failed=False, name="aslr_mpc_run_plant")
-    _solve_matches_a_fresh_handle(e7, low, sp)
+    ext.solve_matches_a_fresh_handle(e7, low, sp, ext.SOLVE_REGIONS, AFTER)
 
 
 def test_a_model_that_is_not_diagonal_runs_on_its_full_rows(oracle):
@@ -441,17 +370,17 @@ def test_a_model_that_is_not_diagonal_runs_on_its_full_rows(oracle):
     for i in range(lown.desc.nmodels):
         lown.desc.models[i].K[1] = lown.desc.models[i].K[7] = 0.03
     dist = np.random.default_rng(mt.DIST_SEED).uniform(-mt.DIST, mt.DIST, (hold, 3, low.nx))
-    e, twin = _fresh(lown), _fresh(lown)
+    e, twin = ext.fresh(lown), ext.fresh(lown)
     got = _raw(e, sp, 1, 3, 3, hold, None, None, dist)
     twin.solve(sp, poll_every=0)
     gc.sync()
     X, U, K = (gc.to_np(twin.region(r)) for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN))
     ref = [mp.plant_phase(oracle, lown, b, X[:, b], U[:, b], K[:, b], hold, None, None, dist[:, b]) for b in range(3)]
-    errs = dict(x=pol.relerr(got["x"], np.stack([r["x"] for r in ref], axis=1)), u=pol.relerr(got["u"], np.stack([r["u"] for r in ref], axis=1)),
-                cost=pol.relerr(got["cost"], np.array([r["cost"] for r in ref])))
+    errs = dict(x=gc.relerr(got["x"], np.stack([r["x"] for r in ref], axis=1)), u=gc.relerr(got["u"], np.stack([r["u"] for r in ref], axis=1)),
+                cost=gc.relerr(got["cost"], np.array([r["cost"] for r in ref])))
     print("not diagonal: relerr %s" % {k: "%.2e" % v for k, v in errs.items()})
     assert max(errs.values()) < 1e-9, errs
-    diag = _raw(_fresh(low), sp, 1, 3, 3, hold, None, None, dist)
+    diag = _raw(ext.fresh(low), sp, 1, 3, 3, hold, None, None, dist)
     assert np.abs(diag["x"][1] - got["x"][1]).max() > 1e-6
 
 

@@ -2,17 +2,16 @@
 csrc/aslr_plant_sens.inc.hpp) against tests/_plant_sens.py: the definition in numpy with full matrices on the oracle's
 records, fed the DEVICE's own gains so that only this sweep is compared.
 
-Kernel outputs are held to 1e-9 in the measure max |a - b| / max |b| per output array and trajectory (cv.relerr);
+Kernel outputs are held to 1e-9 in the measure max |a - b| / max |b| per output array and trajectory (cv.traj_relerr);
 tests/test_plant_sens_host.py shows that the inputs are conditioned for it and pins the definition on the oracle alone.
 Shapes (tests/_covariance.CASES): the smallest that leave a partial wave of teams (B = 9 at nx = 8: 8 trajectories per wave;
 B = 3 at nx = 28: 2 per wave) and the smallest problem there is (B = 1, T = 1).  Every output sits in a buffer of the test's
 own, followed by guard words that must survive."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import _covariance as cv
+import _ext_call as ext
 import _gpu_case as gc
 import _plant_sens as ps
 import _policy as pol
@@ -23,7 +22,6 @@ from aslr_to_amd import _abi, crocoddyl, scenarios
 pytestmark = pytest.mark.gpu
 
 FIELDS = ps.OUTPUTS   # in the order of the C arguments
-GUARD, SENTINEL = 64, -7.25
 _TO_BATCH_MAJOR = {"dx_dstiffness": (1, 0, 2, 3), "dx_dmotor_inertia": (1, 0, 2, 3), "dxT_dstiffness": (0, 1, 2),
                    "dxT_dmotor_inertia": (0, 1, 2), "dcost_dstiffness": (1, 0), "dcost_dmotor_inertia": (1, 0),
                    "x_var": (1, 0, 2), "u_var": (1, 0, 2)}
@@ -45,52 +43,11 @@ def _fields(low):
 
 def _raw(e, stiffness_var, motor_inertia_var, which=None, expect=_abi.OK):
     """aslr_policy_plant_sensitivity with the batch-major variances [B, nj] (None: NULL) and the outputs `which` (default:
-    all the model has; the others NULL), each output in a buffer with GUARD sentinel words behind it.  -> dict of batch-major
-    numpy arrays (the layout of tests/_plant_sens.expected; u_var with the device's nu); the guards must be untouched.
-    expect != OK: -> the message of the refusal."""
-    import torch
-    if which is None:
-        which = _fields(e.low)
-    dev = lambda v: None if v is None else torch.as_tensor(np.ascontiguousarray(np.asarray(v).T), dtype=torch.float64, device=e.device)
-    vk, vb = dev(stiffness_var), dev(motor_inertia_var)
-    bufs, n_of = {}, {}
-    for k in which:
-        n_of[k] = int(np.prod(_shapes(e)[k]))
-        bufs[k] = torch.full((n_of[k] + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-    with torch.cuda.device(e.device):
-        rc = e.lib.aslr_policy_plant_sensitivity(e.handle, ptr(vk), ptr(vb), *[ptr(bufs.get(k)) for k in FIELDS], e._stream())
-    gc.sync()
-    if expect != _abi.OK:
-        assert rc == expect, rc
-        for k, t in bufs.items():
-            assert (t == SENTINEL).all(), "%s was written by a refused call" % k
-        return e.lib.aslr_last_error().decode()
-    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
-    out = {}
-    for k, t in bufs.items():
-        a = gc.to_np(t)
-        assert (a[n_of[k]:] == SENTINEL).all(), "the guard behind %s was overwritten" % k
-        out[k] = np.ascontiguousarray(np.transpose(a[:n_of[k]].reshape(_shapes(e)[k]), _TO_BATCH_MAJOR[k]))
-    return out
-
-
-def _same(a, b, what):
-    assert set(a) == set(b), (what, sorted(a), sorted(b))
-    for k in a:
-        np.testing.assert_array_equal(a[k].view(np.uint64), b[k].view(np.uint64), err_msg="%s: %s" % (what, k))
-
-
-def _with_gains(c):
-    """a fresh engine with the case's candidate in XS / US and the gains of one aslr_calc_diff + aslr_backward_pass on it in
-    KGAIN (the case's own solver: SolverBoxDDP where the scenario has one) -> engine, K [T, B, nu, nx]"""
-    low = c["low"]
-    e = gc.engine(low)
-    deriv = gc.run_calc_diff(e, c["xs"], c["us"])[2]
-    out = gc.run_backward(e, c["sp"], c["us"], deriv, np.zeros((low.T + 1, low.B, low.nx)), pol.XREG, 1)
-    assert (out["status"] & _abi.ST_BACKWARD_ERR == 0).all(), out["status"]
-    assert np.abs(out["K"]).max() > 1e-3
-    return e, out["K"]
+    all the model has; the others NULL) through the guarded call of tests/_ext_call.py -> dict of batch-major numpy arrays
+    (the layout of tests/_plant_sens.expected; u_var with the device's nu), or the message of the refusal"""
+    outs = ext.outputs(e.device, _shapes(e), _fields(e.low) if which is None else which, perms=_TO_BATCH_MAJOR)
+    args = [e.handle, ext.dev(e.device, stiffness_var, (1, 0)), ext.dev(e.device, motor_inertia_var, (1, 0))]
+    return ext.call(e, "aslr_policy_plant_sensitivity", args + [outs.get(k) for k in FIELDS] + [e._stream()], outs, expect)
 
 
 @pytest.fixture(scope="module")
@@ -112,7 +69,7 @@ def loaded(cases):
 
     def get(key):
         if key not in made:
-            made[key] = _with_gains(cases[key])
+            made[key] = ext.with_gains(cases[key])
         return made[key]
     return get
 
@@ -128,7 +85,7 @@ def test_kernel_matches_the_definition(oracle, cases, loaded, key):
     assert set(got) == set(_fields(low))
     for k in got:
         assert got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
-        err = cv.relerr(got[k], want[k])   # (a trajectory whose reference is all zero must match exactly)
+        err = cv.traj_relerr(got[k], want[k])   # (a trajectory whose reference is all zero must match exactly)
         print("%s %s: %.2e (max |reference| %.2e)" % (key, k, err, np.abs(want[k]).max()))
         assert err < 1e-9, (k, err)
     assert np.abs(want["dxT_dmotor_inertia"]).max() > 1e-3 and np.abs(want["x_var"]).max() > 1e-6
@@ -145,7 +102,7 @@ def test_kernel_matches_the_definition(oracle, cases, loaded, key):
     if getattr(low, "ref_path", None) is not None:   # ... and the path is what the records were evaluated against
         plain = scenarios.lower(dict(c["sc"], ref_path=None))
         other = ps.expected(oracle, plain, c["xs"], c["us"], K, vk, vb)
-        assert cv.relerr(other["dcost_dmotor_inertia"], want["dcost_dmotor_inertia"]) > 1e-6
+        assert cv.traj_relerr(other["dcost_dmotor_inertia"], want["dcost_dmotor_inertia"]) > 1e-6
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_sea", "arm_vsa"])
@@ -158,15 +115,15 @@ def test_every_output_is_optional(cases, loaded, key):
     vk, vb = c["var"]
     full = _raw(e, vk, vb)
     for k in full:
-        _same(_raw(e, vk, vb, which=(k,)), {k: full[k]}, "alone")
-    _same(_raw(e, None, vb, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia only")
+        ext.same(_raw(e, vk, vb, which=(k,)), {k: full[k]}, "alone")
+    ext.same(_raw(e, None, vb, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia only")
     if vk is not None:
-        _same(_raw(e, vk, None, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia outputs, stiffness variance")
+        ext.same(_raw(e, vk, None, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia outputs, stiffness variance")
         lean = _raw(e, None, vb, which=MOTOR + ("x_var", "u_var"))
         wide = _raw(e, None, vb, which=MOTOR + ("x_var", "u_var", "dx_dstiffness"))
-        _same(lean, {k: wide[k] for k in lean}, "variances with and without the stiffness columns")
-        _same({"dx_dstiffness": wide["dx_dstiffness"]}, {"dx_dstiffness": full["dx_dstiffness"]}, "stiffness columns")
-        assert cv.relerr(lean["x_var"], full["x_var"]) > 1e-6   # (the stiffness variance is what was left out)
+        ext.same(lean, {k: wide[k] for k in lean}, "variances with and without the stiffness columns")
+        ext.same({"dx_dstiffness": wide["dx_dstiffness"]}, {"dx_dstiffness": full["dx_dstiffness"]}, "stiffness columns")
+        assert cv.traj_relerr(lean["x_var"], full["x_var"]) > 1e-6   # (the stiffness variance is what was left out)
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_sea", "arm_vsa"])
@@ -183,7 +140,7 @@ def test_a_trajectory_does_not_depend_on_where_it_sits(cases, loaded, key):
     e1 = gc.engine(_traj_oracle.single(low, b))
     gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
     alone = _raw(e1, None if vk is None else vk[b:b + 1], vb[b:b + 1])
-    _same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
+    ext.same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_vsa"])
@@ -208,12 +165,12 @@ def test_the_outputs_are_consistent_with_each_other(cases, loaded, key):
             assert adjoint.stiffness is None
             continue
         ref = gc.to_np(getattr(adjoint, kind))
-        err = cv.relerr(open_loop["dcost_d" + kind], ref)
+        err = cv.traj_relerr(open_loop["dcost_d" + kind], ref)
         print("%s open loop dcost_d%s against the adjoint sweep: %.2e (max |reference| %.2e)" % (key, kind, err, np.abs(ref).max()))
         assert err < 1e-9, (kind, err)
         assert np.abs(ref).max() > 1e-3
     assert (open_loop["u_var"] == 0.0).all()
-    assert cv.relerr(open_loop["dxT_dmotor_inertia"], got["dxT_dmotor_inertia"]) > 1e-3   # ... the gains closed the loop above
+    assert cv.traj_relerr(open_loop["dxT_dmotor_inertia"], got["dxT_dmotor_inertia"]) > 1e-3   # ... the gains closed the loop above
 
 
 def test_the_sweep_agrees_with_sampled_plants(cases, loaded):
@@ -245,7 +202,7 @@ def test_the_sweep_agrees_with_sampled_plants(cases, loaded):
             dxT[:, :, j] = (xf[:, 2 * (p0 + j)] - xf[:, 2 * (p0 + j) + 1]) / step[:, None]
             dJ[:, j] = (cost[:, 2 * (p0 + j)] - cost[:, 2 * (p0 + j) + 1]) / step
         for name, fd in (("dxT_d" + kind, dxT), ("dcost_d" + kind, dJ)):
-            err = cv.relerr(got[name], fd)
+            err = cv.traj_relerr(got[name], fd)
             print("%s against sampled plants: %.2e (bound %.1e)" % (name, err, 10 * measured))
             assert err < 10 * measured, (name, err)
 
@@ -281,7 +238,7 @@ def test_refusals_write_nothing_and_leave_a_live_handle_that_still_solves(cases,
     vk, vb = c["var"]
     sp = scenarios.solver_params(sc, maxiter=8)
     _, fresh = gc.solve_gpu(low, sp)
-    e, K = _with_gains(c)
+    e, K = ext.with_gains(c)
     ok = _raw(e, vk, vb)
     _refused(e, vk, vb, (), "outputs", "NULL")
     _refused(e, None, None, ("x_var",), "stiffness_var", "motor_inertia_var")
@@ -296,7 +253,7 @@ def test_refusals_write_nothing_and_leave_a_live_handle_that_still_solves(cases,
     assert set(_raw(e, None, vb, which=MOTOR + ("x_var", "u_var"))) == set(MOTOR + ("x_var", "u_var"))
     e.set_trajectory_params(**tp)
     gc._upload(e, XS=c["xs"], US=c["us"], KGAIN=K)
-    _same(_raw(e, vk, vb), ok, "the handle after the refusals")
+    ext.same(_raw(e, vk, vb), ok, "the handle after the refusals")
     # ... in the models: a zero stiffness, a K and a B that are not diagonal
     nj = low.nj
     lb = sens.moved(low, 0, "K", 1, 0.0)

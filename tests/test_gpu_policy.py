@@ -6,86 +6,22 @@ Kernel outputs are held to 1e-9 relative, the per-kernel bound of the parity sui
 tests/test_policy_host.py shows that the inputs are conditioned for it.  Shapes (tests/_policy.CASES): the smallest that
 leave a partial wave of teams (B = 5) and a sample group with one live lane (S = 17), the smallest problem there is, and a
 full wave.  Every output sits in a buffer of the test's own, followed by guard words that must survive."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import _ext_call as ext
 import _gpu_case as gc
 import _policy as pol
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("cost", "failed_knot", "x_final", "xs", "us")
-GUARD, SENTINEL = 64, -7.25
+FIELDS = ext.POLICY_FIELDS
 
 
-def _shapes(e, S):
-    return {"cost": (S, e.B), "failed_knot": (S, e.B), "x_final": (S, e.B, e.nx), "xs": (S, e.T + 1, e.B, e.nx),
-            "us": (S, e.T, e.B, e.nu)}
-
-
-_TO_BATCH_MAJOR = {"cost": (1, 0), "failed_knot": (1, 0), "x_final": (1, 0, 2), "xs": (2, 0, 1, 3), "us": (2, 0, 1, 3)}
-_TO_DEVICE = {"plant_stiffness": (2, 1, 0), "plant_motor_inertia": (2, 1, 0), "dx0": (1, 0, 2), "disturbance": (1, 2, 0, 3)}
-
-
-def _raw(e, S, pert=None, clamp=False, which=FIELDS, expect=_abi.OK):
-    """aslr_policy_rollout with the batch-major inputs `pert` (missing or None: NULL) and the outputs `which` (the others
-    NULL), each output in a buffer with GUARD sentinel words behind it.  -> dict of batch-major numpy arrays (the layout of
-    tests/_policy.rollout); the guards must be untouched.  expect != OK: -> the message of the refusal."""
-    import torch
-    ins = {}
-    for k, perm in _TO_DEVICE.items():
-        v = (pert or {}).get(k)
-        if v is not None:
-            ins[k] = torch.as_tensor(np.ascontiguousarray(np.transpose(v, perm)), dtype=torch.float64, device=e.device)
-    bufs, n_of = {}, {}
-    for k in which:
-        n_of[k] = int(np.prod(_shapes(e, max(S, 1))[k]))
-        if k == "failed_knot":
-            bufs[k] = torch.full((n_of[k] + GUARD,), -7, dtype=torch.int32, device=e.device)
-        else:
-            bufs[k] = torch.full((n_of[k] + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    ptr = lambda d, k: C.c_void_p(d[k].data_ptr()) if k in d else None
-    with torch.cuda.device(e.device):
-        rc = e.lib.aslr_policy_rollout(e.handle, S, ptr(ins, "plant_stiffness"), ptr(ins, "plant_motor_inertia"), ptr(ins, "dx0"),
-                                       ptr(ins, "disturbance"), 1 if clamp else 0, ptr(bufs, "cost"), ptr(bufs, "failed_knot"),
-                                       ptr(bufs, "x_final"), ptr(bufs, "xs"), ptr(bufs, "us"), e._stream())
-    gc.sync()
-    sentinel = lambda k: -7 if k == "failed_knot" else SENTINEL
-    if expect != _abi.OK:
-        assert rc == expect, rc
-        for k, t in bufs.items():
-            assert (t == sentinel(k)).all(), "%s was written by a refused call" % k
-        return e.lib.aslr_last_error().decode()
-    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
-    out = {}
-    for k, t in bufs.items():
-        a = gc.to_np(t)
-        assert (a[n_of[k]:] == sentinel(k)).all(), "the guard behind %s was overwritten" % k
-        out[k] = np.ascontiguousarray(np.transpose(a[:n_of[k]].reshape(_shapes(e, S)[k]), _TO_BATCH_MAJOR[k]))
-    return out
-
-
-def _with_gains(c, monkeypatch):
-    """a fresh engine with the case's candidate in XS / US and the gains of one aslr_calc_diff + aslr_backward_pass on it in
-    KGAIN -> engine, K [T, B, nu, nx]"""
-    if c["three_d"]:
-        monkeypatch.setenv("ASLR_NO_PLANAR", "1")   # (read when the handle is created: the general 3-D chain path)
-    low = c["low"]
-    e = gc.engine(low)
-    deriv = gc.run_calc_diff(e, c["xs"], c["us"])[2]
-    out = gc.run_backward(e, c["sp"], c["us"], deriv, np.zeros((low.T + 1, low.B, low.nx)), pol.XREG, 1)
-    assert (out["status"] & _abi.ST_BACKWARD_ERR == 0).all(), out["status"]
-    assert np.abs(out["K"]).max() > 1e-3
-    return e, out["K"]
-
-
-def _same(a, b, what):
-    for k in a:
-        v, w = (x.view(np.uint64) if x.dtype == np.float64 else x for x in (a[k], b[k]))
-        np.testing.assert_array_equal(v, w, err_msg="%s: %s" % (what, k))
+def _raw(e, *args, **kw):
+    """ext.policy_rollout(e, "aslr_policy_rollout", S, pert=None, clamp=False, which=FIELDS, expect=OK)"""
+    return ext.policy_rollout(e, "aslr_policy_rollout", *args, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -98,7 +34,7 @@ def cases(oracle):
 def test_kernel_matches_the_definition(oracle, cases, monkeypatch, key):
     c = cases[key]
     low, S = c["low"], c["S"]
-    e, K = _with_gains(c, monkeypatch)
+    e, K = ext.with_gains(c, monkeypatch)
     got = _raw(e, S, c["pert"], c["clamp"])
     want = pol.rollout(oracle, low, c["xs"], c["us"], K, S, clamp=c["clamp"], **c["pert"])
     assert (want["failed_knot"] == -1).all()
@@ -141,14 +77,14 @@ def test_the_nominal_plant_given_explicitly_is_the_null_plant(cases, monkeypatch
     """the trajectories' own K and B passed as plant arrays: the bits of passing NULL (dx0 and disturbance as in the case)"""
     c = cases[key]
     low, S = c["low"], c["S"]
-    e, _ = _with_gains(c, monkeypatch)
+    e, _ = ext.with_gains(c, monkeypatch)
     nom = lambda f: np.repeat(np.array([pol.nominal_diag(low, b, f) for b in range(low.B)])[:, None, :], S, axis=1)
     sea = low.dam == _abi.DAM_SEA
     none = dict(c["pert"], plant_stiffness=None, plant_motor_inertia=None)
     explicit = dict(none, plant_stiffness=nom("K") if sea else None, plant_motor_inertia=nom("B"))
-    _same(_raw(e, S, explicit, c["clamp"]), _raw(e, S, none, c["clamp"]), "explicit nominal plant against NULL")
+    ext.same(_raw(e, S, explicit, c["clamp"]), _raw(e, S, none, c["clamp"]), "explicit nominal plant against NULL")
     if sea:   # ... and each plant argument alone
-        _same(_raw(e, S, dict(none, plant_stiffness=nom("K")), c["clamp"]), _raw(e, S, none, c["clamp"]), "stiffness alone")
+        ext.same(_raw(e, S, dict(none, plant_stiffness=nom("K")), c["clamp"]), _raw(e, S, none, c["clamp"]), "stiffness alone")
 
 
 @pytest.mark.parametrize("key", ["sea_table", "sea_path"])
@@ -157,7 +93,7 @@ def test_a_sample_does_not_depend_on_where_it_sits(cases, monkeypatch, key):
     (its own row of the table, its own path, the batch's gains): bit for bit"""
     c = cases[key]
     sc, low, S = c["sc"], c["low"], c["S"]
-    e, K = _with_gains(c, monkeypatch)
+    e, K = ext.with_gains(c, monkeypatch)
     batch = _raw(e, S, c["pert"])
     for b, s in ((0, 0), (3, 15), (4, 16), (4, 0), (1, 16)):
         one = dict(sc, x0=sc["x0"][b:b + 1], frame_refs=sc["frame_refs"][b:b + 1])
@@ -167,7 +103,7 @@ def test_a_sample_does_not_depend_on_where_it_sits(cases, monkeypatch, key):
         e1 = gc.engine(scenarios.lower(one))
         gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
         alone = _raw(e1, 1, {k: (None if v is None else v[b:b + 1, s:s + 1]) for k, v in c["pert"].items()})
-        _same({k: v[0, 0] for k, v in alone.items()}, {k: v[b, s] for k, v in batch.items()}, "sample %d of trajectory %d" % (s, b))
+        ext.same({k: v[0, 0] for k, v in alone.items()}, {k: v[b, s] for k, v in batch.items()}, "sample %d of trajectory %d" % (s, b))
 
 
 def test_a_failing_sample_fails_alone(cases, monkeypatch):
@@ -175,7 +111,7 @@ def test_a_failing_sample_fails_alone(cases, monkeypatch):
     those of the run without it"""
     c = cases["sea_table"]
     S = c["S"]
-    e, _ = _with_gains(c, monkeypatch)
+    e, _ = ext.with_gains(c, monkeypatch)
     base = _raw(e, S, c["pert"])
     dx0 = np.array(c["pert"]["dx0"])
     dx0[2, 5] = 1e31
@@ -184,21 +120,21 @@ def test_a_failing_sample_fails_alone(cases, monkeypatch):
     keep = np.ones((c["low"].B, S), dtype=bool)
     keep[2, 5] = False
     assert (got["failed_knot"][keep] == -1).all()
-    _same({k: v[keep] for k, v in got.items()}, {k: v[keep] for k, v in base.items()}, "the other samples")
+    ext.same({k: v[keep] for k, v in got.items()}, {k: v[keep] for k, v in base.items()}, "the other samples")
 
 
 @pytest.mark.parametrize("key", ["sea_table", "vsa_box"])
 def test_every_output_is_optional(cases, monkeypatch, key):
     """each output alone: the bits of the call with all five, and nothing written past any buffer (_raw checks the guards)"""
     c = cases[key]
-    e, _ = _with_gains(c, monkeypatch)
+    e, _ = ext.with_gains(c, monkeypatch)
     full = _raw(e, c["S"], c["pert"], c["clamp"])
     for k in FIELDS:
         alone = _raw(e, c["S"], c["pert"], c["clamp"], which=(k,))
         assert list(alone) == [k]
-        _same(alone, {k: full[k]}, "alone")
+        ext.same(alone, {k: full[k]}, "alone")
     both = _raw(e, c["S"], c["pert"], c["clamp"], which=("xs", "us"))
-    _same(both, {k: full[k] for k in both}, "trajectories only")
+    ext.same(both, {k: full[k] for k in both}, "trajectories only")
 
 
 def test_the_call_leaves_a_solve_in_progress_as_it_was(cases):
@@ -220,12 +156,12 @@ def test_the_call_leaves_a_solve_in_progress_as_it_was(cases):
     gc.sync()
     six = gc.solution(e6)
     assert (six["traj_i"][_abi.TI_ITER] == 6).all()
-    _same(with_call, six, "3 + call + 3 against 6")
+    ext.same(with_call, six, "3 + call + 3 against 6")
 
 
 def test_refusals_write_nothing_and_leave_a_live_handle(cases, monkeypatch):
     c = cases["vsa_box"]
-    e, _ = _with_gains(c, monkeypatch)
+    e, _ = ext.with_gains(c, monkeypatch)
     S = c["S"]
     ok = _raw(e, S, c["pert"], True)
     for bad_s in (0, -3):
@@ -236,7 +172,7 @@ def test_refusals_write_nothing_and_leave_a_live_handle(cases, monkeypatch):
     stiff = dict(c["pert"], plant_stiffness=np.ones((c["low"].B, S, 2)))
     msg = _raw(e, S, stiff, expect=_abi.E_INVALID)
     assert msg.startswith("aslr_policy_rollout:") and "VSA" in msg, msg
-    _same(_raw(e, S, c["pert"], True), ok, "the handle after the refusals")
+    ext.same(_raw(e, S, c["pert"], True), ok, "the handle after the refusals")
     # K that is not diagonal: refused with a plant argument, rolled out without one
     low = scenarios.lower(scenarios.two_dof_sea(B=2, T=3, seed=4))
     for i in range(low.desc.nmodels):   # (the lowered description is what aslr_problem_create reads)

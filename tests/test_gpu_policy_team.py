@@ -5,12 +5,11 @@ fed the DEVICE's own gains so that only the roll-out is compared.
 Kernel outputs are held to 1e-9 relative, the per-kernel bound of the parity suites (max |a - b| / (1 + |b|));
 tests/test_policy_team_host.py shows that the inputs are conditioned for it.  Shapes: tests/_policy_team.CASES.  The entry
 point is called raw, every output in a buffer of the test's own, followed by guard words that must survive."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import _covariance as cv
+import _ext_call as ext
 import _gpu_case as gc
 import _plant_sens as ps
 import _policy as pol
@@ -19,76 +18,13 @@ from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
 
-FIELDS = ("cost", "failed_knot", "x_final", "xs", "us")
-GUARD, SENTINEL = 64, -7.25
+FIELDS = ext.POLICY_FIELDS
 NAME = "aslr_policy_rollout_all"
 
 
-def _shapes(e, S):
-    return {"cost": (S, e.B), "failed_knot": (S, e.B), "x_final": (S, e.B, e.nx), "xs": (S, e.T + 1, e.B, e.nx),
-            "us": (S, e.T, e.B, e.nu)}
-
-
-_TO_BATCH_MAJOR = {"cost": (1, 0), "failed_knot": (1, 0), "x_final": (1, 0, 2), "xs": (2, 0, 1, 3), "us": (2, 0, 1, 3)}
-_TO_DEVICE = {"plant_stiffness": (2, 1, 0), "plant_motor_inertia": (2, 1, 0), "dx0": (1, 0, 2), "disturbance": (1, 2, 0, 3)}
-
-
-def _raw(e, S, pert=None, clamp=False, which=FIELDS, expect=_abi.OK, name=NAME, room=None):
-    """the entry point `name` with the batch-major inputs `pert` (missing or None: NULL) and the outputs `which` (the others
-    NULL), each output in a buffer (sized for `room` samples, default S) with GUARD sentinel words behind it.  -> dict of
-    batch-major numpy arrays (the layout of tests/_policy.rollout); the guards must be untouched.  expect != OK: -> the
-    message of the refusal."""
-    import torch
-    ins = {}
-    for k, perm in _TO_DEVICE.items():
-        v = (pert or {}).get(k)
-        if v is not None:
-            ins[k] = torch.as_tensor(np.ascontiguousarray(np.transpose(v, perm)), dtype=torch.float64, device=e.device)
-    bufs, n_of = {}, {}
-    for k in which:
-        n_of[k] = int(np.prod(_shapes(e, max(S if room is None else room, 1))[k]))
-        if k == "failed_knot":
-            bufs[k] = torch.full((n_of[k] + GUARD,), -7, dtype=torch.int32, device=e.device)
-        else:
-            bufs[k] = torch.full((n_of[k] + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    ptr = lambda d, k: C.c_void_p(d[k].data_ptr()) if k in d else None
-    with torch.cuda.device(e.device):
-        rc = getattr(e.lib, name)(e.handle, S, ptr(ins, "plant_stiffness"), ptr(ins, "plant_motor_inertia"), ptr(ins, "dx0"),
-                                  ptr(ins, "disturbance"), 1 if clamp else 0, ptr(bufs, "cost"), ptr(bufs, "failed_knot"),
-                                  ptr(bufs, "x_final"), ptr(bufs, "xs"), ptr(bufs, "us"), e._stream())
-    gc.sync()
-    sentinel = lambda k: -7 if k == "failed_knot" else SENTINEL
-    if expect != _abi.OK:
-        assert rc == expect, rc
-        for k, t in bufs.items():
-            assert (t == sentinel(k)).all(), "%s was written by a refused call" % k
-        return e.lib.aslr_last_error().decode()
-    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
-    out = {}
-    for k, t in bufs.items():
-        a = gc.to_np(t)
-        assert (a[n_of[k]:] == sentinel(k)).all(), "the guard behind %s was overwritten" % k
-        out[k] = np.ascontiguousarray(np.transpose(a[:n_of[k]].reshape(_shapes(e, S)[k]), _TO_BATCH_MAJOR[k]))
-    return out
-
-
-def _with_gains(c):
-    """a fresh engine with the case's candidate in XS / US and the gains of one aslr_calc_diff + aslr_backward_pass on it in
-    KGAIN -> engine, K [T, B, nu, nx]"""
-    low = c["low"]
-    e = gc.engine(low)
-    deriv = gc.run_calc_diff(e, c["xs"], c["us"])[2]
-    out = gc.run_backward(e, c["sp"], c["us"], deriv, np.zeros((low.T + 1, low.B, low.nx)), pol.XREG, 1)
-    assert (out["status"] & _abi.ST_BACKWARD_ERR == 0).all(), out["status"]
-    assert np.abs(out["K"]).max() > 1e-3
-    return e, out["K"]
-
-
-def _same(a, b, what):
-    assert set(a) == set(b), (what, sorted(a), sorted(b))
-    for k in a:
-        v, w = (x.view(np.uint64) if x.dtype == np.float64 else x for x in (a[k], b[k]))
-        np.testing.assert_array_equal(v, w, err_msg="%s: %s" % (what, k))
+def _raw(e, *args, name=NAME, **kw):
+    """ext.policy_rollout(e, name, S, pert=None, clamp=False, which=FIELDS, expect=OK, room=None)"""
+    return ext.policy_rollout(e, name, *args, **kw)
 
 
 @pytest.fixture(scope="module")
@@ -112,7 +48,7 @@ def loaded(cases):
     def get(key):
         if key not in made:
             c = cases(key)
-            e, K = _with_gains(c)
+            e, K = ext.with_gains(c)
             made[key] = (e, K, _raw(e, c["S"], c["pert"], c["clamp"]))
         return made[key]
     return get
@@ -165,14 +101,14 @@ def test_a_sample_does_not_depend_on_where_it_sits(cases, loaded):
     c = cases("arm_sea_table")
     sc, S = c["sc"], c["S"]
     e, K, batch = loaded("arm_sea_table")
-    _same(_raw(e, S, c["pert"], which=("cost",)), {"cost": batch["cost"]}, "cost alone")
+    ext.same(_raw(e, S, c["pert"], which=("cost",)), {"cost": batch["cost"]}, "cost alone")
     for b, s in ((0, 0), (1, 7), (2, 8), (2, 16), (1, 15)):
         one = dict(sc, x0=sc["x0"][b:b + 1], frame_refs=sc["frame_refs"][b:b + 1])
         one["traj_params"] = {k: (None if v is None else v[b:b + 1]) for k, v in sc["traj_params"].items()}
         e1 = gc.engine(scenarios.lower(one))
         gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
         alone = _raw(e1, 1, {k: (None if v is None else v[b:b + 1, s:s + 1]) for k, v in c["pert"].items()})
-        _same({k: v[0, 0] for k, v in alone.items()}, {k: v[b, s] for k, v in batch.items()}, "sample %d of trajectory %d" % (s, b))
+        ext.same({k: v[0, 0] for k, v in alone.items()}, {k: v[b, s] for k, v in batch.items()}, "sample %d of trajectory %d" % (s, b))
 
 
 @pytest.mark.parametrize("key", ["arm_sea_table", "arm_sea_plain"])
@@ -184,8 +120,8 @@ def test_the_nominal_plant_given_explicitly_is_the_null_plant(cases, loaded, key
     nom = lambda f: np.repeat(np.array([pol.nominal_diag(low, b, f) for b in range(low.B)])[:, None, :], S, axis=1)
     none = dict(c["pert"], plant_stiffness=None, plant_motor_inertia=None)
     null = _raw(e, S, none)
-    _same(_raw(e, S, dict(none, plant_stiffness=nom("K"), plant_motor_inertia=nom("B"))), null, "explicit nominal plant against NULL")
-    _same(_raw(e, S, dict(none, plant_stiffness=nom("K"))), null, "stiffness alone")
+    ext.same(_raw(e, S, dict(none, plant_stiffness=nom("K"), plant_motor_inertia=nom("B"))), null, "explicit nominal plant against NULL")
+    ext.same(_raw(e, S, dict(none, plant_stiffness=nom("K"))), null, "stiffness alone")
 
 
 def test_the_call_leaves_a_solve_in_progress_as_it_was(cases):
@@ -206,7 +142,7 @@ def test_the_call_leaves_a_solve_in_progress_as_it_was(cases):
     gc.sync()
     six = gc.solution(e6)
     assert (six["traj_i"][_abi.TI_ITER] == 6).all()
-    _same(with_call, six, "3 + call + 3 against 6")
+    ext.same(with_call, six, "3 + call + 3 against 6")
 
 
 def test_a_diverging_sample_fails_alone(oracle, cases):
@@ -215,7 +151,7 @@ def test_a_diverging_sample_fails_alone(oracle, cases):
     without it"""
     c = cases(("talos_arm_sea", False, False, 2, 3, 4, False, False))
     low, S = c["low"], c["S"]
-    e, K = _with_gains(c)
+    e, K = ext.with_gains(c)
     base = _raw(e, S, c["pert"])
     pb = np.array(c["pert"]["plant_motor_inertia"])
     pb[1, 1] = -1e-300
@@ -228,14 +164,14 @@ def test_a_diverging_sample_fails_alone(oracle, cases):
     keep = np.ones((low.B, S), dtype=bool)
     keep[1, 1] = False
     assert (got["failed_knot"][keep] == -1).all()
-    _same({k: v[keep] for k, v in got.items()}, {k: v[keep] for k, v in base.items()}, "the other samples")
+    ext.same({k: v[keep] for k, v in got.items()}, {k: v[keep] for k, v in base.items()}, "the other samples")
 
 
 @pytest.mark.parametrize("key", ["sea_table", "vsa_box"])
 def test_a_two_joint_handle_gets_the_bits_of_the_old_entry_point(cases, key):
     c = cases(key)
-    e, _ = _with_gains(c)
-    _same(_raw(e, c["S"], c["pert"], c["clamp"]), _raw(e, c["S"], c["pert"], c["clamp"], name="aslr_policy_rollout"),
+    e, _ = ext.with_gains(c)
+    ext.same(_raw(e, c["S"], c["pert"], c["clamp"]), _raw(e, c["S"], c["pert"], c["clamp"], name="aslr_policy_rollout"),
           "aslr_policy_rollout_all against aslr_policy_rollout")
 
 
@@ -253,7 +189,7 @@ def test_refusals_write_nothing_and_leave_a_live_handle(oracle, cases, loaded):
     refused(e, 16 * 65535 + 1, None, "n_samples", "above", room=1)
     refused(e, S, c["pert"], "NULL", which=())
     refused(e, S, dict(c["pert"], plant_stiffness=np.ones((c["low"].B, S, 7))), "VSA")
-    _same(_raw(e, S, c["pert"], True), ok, "the handle after the refusals")
+    ext.same(_raw(e, S, c["pert"], True), ok, "the handle after the refusals")
     # K that is not diagonal: refused with a plant argument, rolled out on the full rows without one (open loop: K = 0)
     low = scenarios.lower(scenarios.talos_arm_sea(B=2, T=3, seed=4))
     for i in range(low.desc.nmodels):   # (the lowered description is what aslr_problem_create reads)
@@ -278,7 +214,7 @@ def test_the_first_order_sweep_agrees_with_sampled_plants(oracle):
     aslr_policy_plant_sensitivity, within ten times the disagreement tests/_plant_sens.FD records for that step"""
     c = cv.case(oracle, "arm_sea")
     low = c["low"]
-    e, _ = _with_gains(c)
+    e, _ = ext.with_gains(c)
     h, measured, _ = ps.FD["arm_sea"]
     B, nj = low.B, low.nj
     assert nj == 7
@@ -301,7 +237,7 @@ def test_the_first_order_sweep_agrees_with_sampled_plants(oracle):
             dxT[:, :, j] = (xf[:, 2 * (p0 + j)] - xf[:, 2 * (p0 + j) + 1]) / step[:, None]
             dJ[:, j] = (cost[:, 2 * (p0 + j)] - cost[:, 2 * (p0 + j) + 1]) / step
         for name, fd in (("dx_final_d" + kind, dxT), ("dcost_d" + kind, dJ)):
-            err = cv.relerr(gc.to_np(getattr(sweep, name)), fd)
+            err = cv.traj_relerr(gc.to_np(getattr(sweep, name)), fd)
             print("%s against sampled plants: %.2e (bound %.1e)" % (name, err, 10 * measured))
             assert err < 10 * measured, (name, err)
 

@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import _ext_call as ext
 import _gpu_case as gc
 import _mpc_loop
 import _ref_path as RP
@@ -20,6 +21,7 @@ from aslr_to_amd import _abi, crocoddyl, scenarios
 pytestmark = pytest.mark.gpu
 
 SOLUTION = ("xs", "us", "traj_f", "traj_i")
+AFTER = "after a declined call"
 
 
 def _same_solution(a, b, what):
@@ -239,15 +241,6 @@ def test_mpc_slides_along_the_path():
 
 
 # ---- 7. declines ----
-def _solve_matches_a_fresh_handle(e, low, sp):
-    fresh = gc.engine(low)
-    for h in (e, fresh):
-        h.set_candidate(None, None)
-        h.solve(sp, poll_every=4)
-    gc.sync()
-    _same_solution(gc.solution(e), gc.solution(fresh), "after a declined call")
-
-
 def test_declines_leave_the_handle_as_it_was():
     import torch
     B = 4
@@ -262,19 +255,19 @@ def test_declines_leave_the_handle_as_it_was():
         with pytest.raises(_abi.AslrError, match="aslr_set_reference_path: " + msg):
             e._call("aslr_set_reference_path", ptr, n_rows, row0, e._stream())
         assert e.reference_row == 0
-    _solve_matches_a_fresh_handle(e, low, sp)      # no path was set by any of them
+    ext.solve_matches_a_fresh_handle(e, low, sp, ext.SOLVE_REGIONS, AFTER)      # no path was set by any of them
     # ... and a path that IS set survives a declined call
     e._call("aslr_set_reference_path", ptr, 3, 1, e._stream())
     with pytest.raises(_abi.AslrError, match="row0 must lie in"):
         e._call("aslr_set_reference_path", ptr, 3, 7, e._stream())
     assert e.reference_row == 1
     low_path = scenarios.lower(RP.with_path(sc, RP.random_path(sc, 3, seed=1), 1))
-    _solve_matches_a_fresh_handle(e, low_path, sp)
+    ext.solve_matches_a_fresh_handle(e, low_path, sp, ext.SOLVE_REGIONS, AFTER)
     # a pool solve on a handle with a path set
     with pytest.raises(_abi.AslrError, match="aslr_solve_pool: the handle has a reference path set"):
         e.solve_pool(low.x0, low.frame_ref, sp)
     assert e.reference_row == 1
-    _solve_matches_a_fresh_handle(e, low_path, sp)
+    ext.solve_matches_a_fresh_handle(e, low_path, sp, ext.SOLVE_REGIONS, AFTER)
     e.set_reference_path(None)
     assert e.solve_pool(low.x0, low.frame_ref, sp)["xs"].shape[0] == B   # cleared: the pool runs
     # no frame-placement cost in the problem
@@ -284,4 +277,4 @@ def test_declines_leave_the_handle_as_it_was():
     one = torch.zeros((1, 1, 12), dtype=torch.float64, device=ep.device)
     with pytest.raises(_abi.AslrError, match="aslr_set_reference_path: no model of the problem has a frame-placement cost"):
         ep._call("aslr_set_reference_path", C.c_void_p(one.data_ptr()), 1, 0, ep._stream())
-    _solve_matches_a_fresh_handle(ep, lowp, scenarios.solver_params(pc, maxiter=10))
+    ext.solve_matches_a_fresh_handle(ep, lowp, scenarios.solver_params(pc, maxiter=10), ext.SOLVE_REGIONS, AFTER)

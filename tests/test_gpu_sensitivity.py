@@ -5,11 +5,10 @@ the definition, none of the kernel's closed-form identities.
 Kernel outputs are held to 1e-9 relative, the per-kernel bound of the parity suites (max |a - b| / (1 + |b|)).  Shapes: the
 smallest that still leave a partial wave and a partial group of teams (B = 70 at nx = 8: 8 trajectories per wave), a wave
 with an empty team (B = 3 at nx = 28: 2 per wave), and the smallest problem there is (B = 1, T = 1)."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+import _ext_call as ext
 import _gpu_case as gc
 import _ref_path
 import _sensitivity as sens
@@ -18,7 +17,6 @@ from aslr_to_amd import _abi, crocoddyl, scenarios
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("stiffness", "motor_inertia", "x0", "costate")
-GUARD, SENTINEL = 64, -7.25
 
 
 def _pendulum(fn, B, T):
@@ -65,33 +63,14 @@ def _shapes(e):
     return {"stiffness": (nj, e.B), "motor_inertia": (nj, e.B), "x0": (e.nx, e.B), "costate": (e.T + 1, e.B, e.nx)}
 
 
+_TO_BATCH_MAJOR = {"stiffness": (1, 0), "motor_inertia": (1, 0), "x0": (1, 0), "costate": (1, 0, 2)}
+
+
 def _raw(e, which=FIELDS, expect=_abi.OK):
-    """aslr_cost_sensitivity with the outputs `which` (the others NULL), each in a buffer of the test's own with GUARD
-    sentinel words behind it.  -> dict of batch-major numpy arrays (the layout of tests/_sensitivity.expected); the guards
-    must be untouched.  expect != OK: -> the message of the refusal."""
-    import torch
-    bufs = {}
-    for k in which:
-        n = int(np.prod(_shapes(e)[k]))
-        bufs[k] = torch.full((n + GUARD,), SENTINEL, dtype=torch.float64, device=e.device)
-    ptr = lambda k: C.c_void_p(bufs[k].data_ptr()) if k in bufs else None
-    with torch.cuda.device(e.device):
-        rc = e.lib.aslr_cost_sensitivity(e.handle, ptr("stiffness"), ptr("motor_inertia"), ptr("x0"), ptr("costate"), e._stream())
-    gc.sync()
-    if expect != _abi.OK:
-        assert rc == expect, rc
-        for k, t in bufs.items():
-            assert (t == SENTINEL).all(), "%s was written by a refused call" % k
-        return e.lib.aslr_last_error().decode()
-    assert rc == _abi.OK, e.lib.aslr_last_error().decode()
-    out = {}
-    for k, t in bufs.items():
-        a = gc.to_np(t)
-        n = a.size - GUARD
-        assert (a[n:] == SENTINEL).all(), "the guard behind %s was overwritten" % k
-        a = a[:n].reshape(_shapes(e)[k])
-        out[k] = a.transpose(1, 0, 2).copy() if k == "costate" else a.T.copy()
-    return out
+    """aslr_cost_sensitivity with the outputs `which` (the others NULL) through the guarded call of tests/_ext_call.py ->
+    dict of batch-major numpy arrays (the layout of tests/_sensitivity.expected), or the message of the refusal"""
+    outs = ext.outputs(e.device, _shapes(e), which, perms=_TO_BATCH_MAJOR)
+    return ext.call(e, "aslr_cost_sensitivity", [e.handle] + [outs.get(k) for k in FIELDS] + [e._stream()], outs, expect)
 
 
 def _loaded(low, xs, us):
@@ -191,7 +170,7 @@ def test_python_facade_at_a_solution_matches_finite_differences_of_the_optimal_c
     gc.sync()
     fd = sens.optimum_fd(oracle)
     for k in ("stiffness", "motor_inertia"):
-        err = sens.relerr(gc.to_np(getattr(got, k)), fd[k])
+        err = gc.relerr(gc.to_np(getattr(got, k)), fd[k])
         print("d%s: disagreement %.2e (bound %.1e)" % (k, err, 10 * sens.OPT_FD[1]))
         assert err < 10 * sens.OPT_FD[1], (k, err)
     assert tuple(got.costate.shape) == (sens.OPT_B, sens.OPT_T + 1, 8)

@@ -75,7 +75,7 @@ def cases(oracle):
 def test_the_definition_is_the_derivative_of_the_nonlinear_closed_loop(oracle, cases, key, halve):
     """S_T, V and dJ_cl/dtheta of the definition (closed forms of G_t included) against central differences of
     _policy.rollout_one with the oracle's gains, no clamp, on plants whose theta_p is theta_p (1 +- h), one parameter at a
-    time, in the measure cv.relerr; at the step h and at h / 2.
+    time, in the measure cv.traj_relerr; at the step h and at h / 2.
 
     Finite-difference error is not rounding error and has no a-priori bound, so steps and bounds were fixed as in
     tests/test_sensitivity_host.py and test_covariance_host.py: the disagreement measured on the oracle alone over a scan of
@@ -101,7 +101,7 @@ def test_the_definition_is_the_derivative_of_the_nonlinear_closed_loop(oracle, c
 @pytest.mark.parametrize("key", sorted(ps.CASES))
 def test_open_loop_cost_derivatives_are_the_adjoint_ones(oracle, cases, key):
     """K = 0: dJ_cl/dtheta of the definition (tangent sweep) against the adjoint reference of tests/_sensitivity.expected,
-    which sums lambda_{t+1}^T dxnext_t/dtheta with the oracle's own differences of the step: 1e-11 in cv.relerr, the
+    which sums lambda_{t+1}^T dxnext_t/dtheta with the oracle's own differences of the step: 1e-11 in cv.traj_relerr, the
     measure of every other check of this call (per trajectory, max |a - b| / max |b|).  The two sweeps are dual, and the
     closed forms of G_t are the step's parameter derivatives.
 
@@ -119,7 +119,7 @@ def test_open_loop_cost_derivatives_are_the_adjoint_ones(oracle, cases, key):
         if want[kind] is None:
             assert got["dcost_d" + kind] is None
             continue
-        err = cv.relerr(got["dcost_d" + kind], want[kind])
+        err = cv.traj_relerr(got["dcost_d" + kind], want[kind])
         print("%s d/d%s: %.2e (max |reference| %.2e)" % (key, kind, err, np.abs(want[kind]).max()))
         assert err < 1e-11, (kind, err)
         if low.T > 1:   # (T = 1: the terminal cost's gradient has no motor entries, so dJ/dB is exactly 0)
@@ -129,7 +129,7 @@ def test_open_loop_cost_derivatives_are_the_adjoint_ones(oracle, cases, key):
 @pytest.mark.parametrize("key", sorted(ps.CASES))
 def test_the_gpu_cases_are_well_conditioned(oracle, cases, key):
     """x0 and K moved by 1e-13 relative (seeded signs; the candidate is rolled out again from the moved x0): every output of
-    the definition must move by less than 1e-11 in the measure of the GPU tests (cv.relerr), so that 1e-9 there is a
+    the definition must move by less than 1e-11 in the measure of the GPU tests (cv.traj_relerr), so that 1e-9 there is a
     statement about the kernel.  A condition on the choice of inputs: the cases, candidates and gains are those of
     tests/_covariance.py as they are.  Measured movement, worst output: arm_sea 1.7e-12, arm_vsa 5.2e-13, nu1 6.6e-13, sea
     2.6e-12, sea_one 0, sea_path 2.6e-12, vsa_box 5.4e-12: no case had to be changed."""
@@ -148,6 +148,6 @@ def test_the_gpu_cases_are_well_conditioned(oracle, cases, key):
         if base[k] is None:
             continue
         assert np.isfinite(base[k]).all(), k
-        worst = max(worst, cv.relerr(moved[k], base[k]))
+        worst = max(worst, cv.traj_relerr(moved[k], base[k]))
     print("%s: worst movement %.2e" % (key, worst))
     assert worst < 1e-11, worst
