@@ -210,6 +210,9 @@ POLICY_ALL_SYMBOLS = ["aslr_policy_rollout_all"]
 # what include/aslr_to_amd_mpc_plant_all.h declares: a ninth extension header, in a list of its own for the same reason
 MPC_PLANT_ALL_SYMBOLS = ["aslr_mpc_run_plant_all"]
 
+# what include/aslr_to_amd_policy_noise.h declares: a tenth extension header, in a list of its own for the same reason
+POLICY_NOISE_SYMBOLS = ["aslr_policy_rollout_noise"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -291,6 +294,8 @@ def load_library():
     lib.aslr_policy_rollout.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     lib.aslr_policy_rollout_all.restype = C.c_int
     lib.aslr_policy_rollout_all.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    lib.aslr_policy_rollout_noise.restype = C.c_int
+    lib.aslr_policy_rollout_noise.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp, C.c_int] + [vp] * 10
     lib.aslr_mpc_run_plant.restype = C.c_int
     lib.aslr_mpc_run_plant.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
     lib.aslr_mpc_run_plant_all.restype = C.c_int

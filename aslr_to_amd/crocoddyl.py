@@ -239,6 +239,22 @@ class ShootingProblem(object):
         return self._with_policy(xs, us, K, lambda: e.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0,
                                                                      disturbance, clamp, keep_trajectories))
 
+    def policy_monte_carlo(self, xs, us, K, n_samples, seed, noise_std=None, dx0_std=None, stiffness_rel_std=None,
+                           motor_inertia_rel_std=None, clamp=False, keep_trajectories=False, keep_draws=False, sample0=0,
+                           trajectory0=0):
+        """policy_rollout with the perturbations drawn on the device from `seed` (Engine.policy_rollout_noise;
+        aslr_policy_rollout_noise): xs, us, K as policy_rollout takes them, all three None: the policy the engine holds.
+        The engine's own XS / US / KGAIN are put back afterwards.  -> engine.PolicyRolloutResult (with `draws` when
+        keep_draws).  This shard's trajectories only; trajectory0 is the shard's offset in the whole batch."""
+        e = self.engine
+        run = lambda: e.policy_rollout_noise(n_samples, seed, noise_std, dx0_std, stiffness_rel_std, motor_inertia_rel_std, clamp,
+                                             keep_trajectories, keep_draws, sample0, trajectory0)
+        if xs is None and us is None and K is None:
+            return run()
+        if xs is None or us is None or K is None:
+            raise ValueError("policy_monte_carlo: give xs, us and K together (or none of them: the engine's own policy)")
+        return self._with_policy(xs, us, K, run)
+
     def policy_covariance(self, xs, us, K, sigma0=None, noise_var=None, keep_cov=False):
         """First-order state and control covariance under the policy u_t = us_t - K_t (x_t - xs_t) (Engine.policy_covariance;
         aslr_policy_covariance): xs, us, K as policy_rollout takes them, all three None: the policy the engine holds.  The
@@ -593,6 +609,24 @@ class SolverDDP(object):
             clamp = self._solver == _abi.SOLVER_BOXDDP
         return self.problem.engine.policy_rollout(n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance,
                                                   bool(clamp), keep_trajectories)
+
+    def policy_monte_carlo(self, n_samples, seed, noise_std=None, dx0_std=None, stiffness_rel_std=None,
+                           motor_inertia_rel_std=None, clamp=None, keep_trajectories=False, keep_draws=False, sample0=0,
+                           trajectory0=0):
+        """policy_rollout as a Monte-Carlo run whose perturbations are drawn on the device: sample s of trajectory b gets
+        disturbance = noise_std z, dx0 = dx0_std z, K_j = Knom_j exp(stiffness_rel_std z) and B_j likewise, z standard
+        normals of a counter-based generator (Philox4x32-10, Box-Muller; include/aslr_to_amd_policy_noise.h) that depend on
+        (seed, knot, sample0 + s, trajectory0 + b, entry) alone.  So n_samples is bounded by time, not by memory; a run is
+        reproducible from `seed`; a shard draws what the whole batch would (trajectory0); and one sample can be replayed
+        alone (sample0, n_samples = 1) with keep_trajectories.  Each sigma: None (absent), a scalar, [nx] / [nj] or
+        [B, nx] / [B, nj]; no stiffness_rel_std for a VSA model.  clamp as in policy_rollout.  -> engine.PolicyRolloutResult;
+        with keep_draws it carries `draws`: plant_stiffness, plant_motor_inertia, dx0, disturbance, the very arguments
+        policy_rollout accepts."""
+        if clamp is None:
+            clamp = self._solver == _abi.SOLVER_BOXDDP
+        return self.problem.engine.policy_rollout_noise(n_samples, seed, noise_std, dx0_std, stiffness_rel_std,
+                                                        motor_inertia_rel_std, bool(clamp), keep_trajectories, keep_draws,
+                                                        sample0, trajectory0)
 
     def policy_covariance(self, sigma0=None, noise_var=None, keep_cov=False):
         """What the policy of the last solve (its xs, us and Riccati gains K) does to uncertainty, to first order and without

@@ -15,6 +15,7 @@
 #include "../../include/aslr_to_amd_cov.h"
 #include "../../include/aslr_to_amd_plant_sens.h"
 #include "../../include/aslr_to_amd_policy_all.h"
+#include "../../include/aslr_to_amd_policy_noise.h"
 #include "../../include/aslr_to_amd_mpc_plant_all.h"
 #include "../../include/aslr_to_amd_design.h"
 
@@ -1246,12 +1247,42 @@ int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var
   return launch_plant_sens(p->nx, p->nu, a, st);
 }
 
-// aslr_policy_rollout and aslr_policy_rollout_all (include/aslr_to_amd_policy_all.h): one body.  fn: the entry point a
-// refusal names; arms: 7-joint handles are admitted (their roll-out is policy_rollout_team_kernel's)
+// aslr_policy_rollout, aslr_policy_rollout_all (include/aslr_to_amd_policy_all.h) and aslr_policy_rollout_noise
+// (include/aslr_to_amd_policy_noise.h): one body.  fn: the entry point a refusal names; arms: 7-joint handles are admitted
+// (their roll-out is policy_rollout_team_kernel's); draw: the drawing form -- its sigma pointers, drawn_* outputs and counter
+// offsets are filled in by the caller, the four input arrays are NULL, and the rest of it is filled in here
 namespace {
+// what the drawing form refuses beyond the shared body
+int noise_refusals(const char *fn, const aslr_problem *p, int n_samples, int sample0, int trajectory0, const PolicyNoiseArgs &d) {
+  if (!d.noise_std && !d.dx0_std && !d.stiffness_rel_std && !d.motor_inertia_rel_std)
+    return fail(ASLR_E_INVALID, "%s: all four sigma arrays are NULL: nothing to draw", fn);
+  if (sample0 < 0) return fail(ASLR_E_INVALID, "%s: sample0 is %d, must be >= 0", fn, sample0);
+  if (trajectory0 < 0) return fail(ASLR_E_INVALID, "%s: trajectory0 is %d, must be >= 0", fn, trajectory0);
+  if ((int64_t)sample0 + n_samples > INT32_MAX)
+    return fail(ASLR_E_INVALID, "%s: sample0 + n_samples = %lld overflows the 32-bit sample counter", fn, (long long)sample0 + n_samples);
+  if (d.stiffness_rel_std && p->dam != ASLR_DAM_SEA)
+    return fail(ASLR_E_INVALID, "%s: stiffness_rel_std on a VSA model, which takes its stiffness from u", fn);
+  if (!d.stiffness_rel_std && !d.motor_inertia_rel_std) return ASLR_OK;
+  const int nj = p->nj;
+  const aslr_model_t *M = p->desc.models;
+  for (int i = 0; i < p->desc.nmodels; ++i)
+    if (!is_diagonal(nj, M[i].K) || !is_diagonal(nj, M[i].B))
+      return fail(ASLR_E_INVALID, "%s: a plant sigma needs diagonal K and B, and those of model %d are not", fn, i);
+  if (p->ks->traj_params) return ASLR_OK; // (the nominal is the trajectory's row of the table)
+  for (int i = 0; i < p->desc.nmodels; ++i)
+    for (int j = 0; j < nj; ++j) {
+      if (d.stiffness_rel_std && M[i].K[j * nj + j] != M[0].K[j * nj + j])
+        return fail(ASLR_E_INVALID, "%s: the models differ in K: no single nominal for stiffness_rel_std (set a parameter table)", fn);
+      if (d.motor_inertia_rel_std && M[i].B[j * nj + j] != M[0].B[j * nj + j])
+        return fail(ASLR_E_INVALID, "%s: the models differ in B: no single nominal for motor_inertia_rel_std (set a parameter table)", fn);
+    }
+  return ASLR_OK;
+}
+
 int policy_rollout(const char *fn, bool arms, aslr_problem_t *p, int n_samples, const double *plant_stiffness,
                    const double *plant_motor_inertia, const double *dx0, const double *disturbance, int clamp, double *cost,
-                   int32_t *failed_knot, double *x_final, double *xs_closed, double *us_closed, void *stream) {
+                   int32_t *failed_knot, double *x_final, double *xs_closed, double *us_closed, void *stream,
+                   PolicyNoiseArgs *draw = nullptr, int sample0 = 0, int trajectory0 = 0) {
   if (!p) return no_handle(fn);
   if (n_samples <= 0) return fail(ASLR_E_INVALID, "%s: n_samples is %d, must be positive", fn, n_samples);
   // (16 samples per block along grid y for both kernels)
@@ -1262,15 +1293,23 @@ int policy_rollout(const char *fn, bool arms, aslr_problem_t *p, int n_samples, 
     return fail(ASLR_E_INVALID, "%s: the roll-out kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint team form is not built); aslr_policy_rollout_all serves every size", fn, p->nj);
   if (p->nj != 2 && p->nj != 7)
     return fail(ASLR_E_INVALID, "%s: no roll-out kernel for this %d-joint handle", fn, p->nj);
-  if (int rc = plant_arg_refusals(fn, p, plant_stiffness, plant_motor_inertia)) return rc;
+  if (int rc = draw ? noise_refusals(fn, p, n_samples, sample0, trajectory0, *draw) : plant_arg_refusals(fn, p, plant_stiffness, plant_motor_inertia)) return rc;
   const bool table = p->ks->traj_params;
-  PolicyArgs a;
-  memset(&a, 0, sizeof a);
+  PolicyArgs own;
+  memset(&own, 0, sizeof own);
+  PolicyArgs &a = draw ? *draw : own; // (the drawing form: the PolicyArgs part of its own argument block)
   a.plant_stiffness = plant_stiffness; a.plant_motor_inertia = plant_motor_inertia; a.dx0 = dx0; a.disturbance = disturbance;
   a.cost = cost; a.failed_knot = failed_knot; a.x_final = x_final; a.xs_closed = xs_closed; a.us_closed = us_closed;
   a.S = n_samples; a.clamp = clamp != 0;
   a.table = table; a.diagonal = table || plant_stiffness || plant_motor_inertia;
-  return (p->nj == 2 ? launch_policy_rollout : launch_policy_rollout_team)(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+  if (!draw) return (p->nj == 2 ? launch_policy_rollout : launch_policy_rollout_team)(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+  draw->diagonal = table || draw->stiffness_rel_std || draw->motor_inertia_rel_std;
+  draw->key.sample0 = (uint32_t)sample0; draw->key.trajectory0 = (uint32_t)trajectory0;
+  for (int j = 0; j < p->nj; ++j) { // (read by the kernel only where noise_refusals found one nominal)
+    draw->knom[j] = p->desc.models[0].K[j * p->nj + j];
+    draw->bnom[j] = p->desc.models[0].B[j * p->nj + j];
+  }
+  return (p->nj == 2 ? launch_policy_rollout_noise : launch_policy_rollout_noise_team)(p->nj, p->dam, p->k, p->limits, *draw, static_cast<hipStream_t>(stream));
 }
 } // namespace
 
@@ -1284,6 +1323,19 @@ int aslr_policy_rollout_all(aslr_problem_t *p, int n_samples, const double *plan
                             const double *dx0, const double *disturbance, int clamp, double *cost, int32_t *failed_knot,
                             double *x_final, double *xs_closed, double *us_closed, void *stream) {
   return policy_rollout("aslr_policy_rollout_all", true, p, n_samples, plant_stiffness, plant_motor_inertia, dx0, disturbance, clamp, cost, failed_knot, x_final, xs_closed, us_closed, stream);
+}
+
+int aslr_policy_rollout_noise(aslr_problem_t *p, int n_samples, int sample0, int trajectory0, uint64_t seed,
+                              const double *noise_std, const double *dx0_std, const double *stiffness_rel_std,
+                              const double *motor_inertia_rel_std, int clamp, double *cost, int32_t *failed_knot, double *x_final,
+                              double *xs_closed, double *us_closed, double *drawn_stiffness, double *drawn_motor_inertia,
+                              double *drawn_dx0, double *drawn_disturbance, void *stream) {
+  PolicyNoiseArgs d;
+  memset(&d, 0, sizeof d);
+  d.noise_std = noise_std; d.dx0_std = dx0_std; d.stiffness_rel_std = stiffness_rel_std; d.motor_inertia_rel_std = motor_inertia_rel_std;
+  d.drawn_stiffness = drawn_stiffness; d.drawn_motor_inertia = drawn_motor_inertia; d.drawn_dx0 = drawn_dx0; d.drawn_disturbance = drawn_disturbance;
+  d.key.k0 = (uint32_t)(seed & 0xffffffffu); d.key.k1 = (uint32_t)(seed >> 32);
+  return policy_rollout("aslr_policy_rollout_noise", true, p, n_samples, nullptr, nullptr, nullptr, nullptr, clamp, cost, failed_knot, x_final, xs_closed, us_closed, stream, &d, sample0, trajectory0);
 }
 
 int aslr_backward_pass(aslr_problem_t *p, const aslr_solver_params_t *sp, void *stream) {

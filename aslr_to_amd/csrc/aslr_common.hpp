@@ -247,6 +247,21 @@ int launch_policy_rollout(int nj, int dam, const KArgs &k, const ModelLimits &li
 // the nx = 28 sizes of the same roll-out (aslr_policy_rollout_all, aslr_policy_team.inc.hpp): 8-lane teams, the same arguments
 int launch_policy_rollout_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st);
 
+// The same roll-outs with the perturbations drawn inside the kernel (aslr_policy_rollout_noise, aslr_policy_noise.hpp): the
+// input pointers of the PolicyArgs part are NULL, the sigma arrays stand in their place.  The same kernel templates, with this
+// type as their argument type, in units of their own (aslr_policy_noise_nj2.hip, aslr_policy_noise_team.hip).
+struct NoiseKey { uint32_t k0, k1, sample0, trajectory0; }; // the Philox key (seed, low and high word) and the counter offsets
+struct PolicyNoiseArgs : PolicyArgs {
+  const double *noise_std, *dx0_std;                       // [B][nx], each nullable (that source is absent)
+  const double *stiffness_rel_std, *motor_inertia_rel_std; // [B][nj], each nullable
+  double *drawn_stiffness, *drawn_motor_inertia;           // [nj][S][B]; every output nullable
+  double *drawn_dx0, *drawn_disturbance;                   // [S][B][nx], [S][T][B][nx]
+  NoiseKey key;
+  double knom[ASLR_MAX_NJ], bnom[ASLR_MAX_NJ]; // the diagonals of K and B the models share: the nominal while no table is set
+};
+int launch_policy_rollout_noise(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyNoiseArgs &pa, hipStream_t st);
+int launch_policy_rollout_noise_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyNoiseArgs &pa, hipStream_t st);
+
 // The plant phase of one control step of aslr_mpc_run_plant (aslr_mpc_plant.inc.hpp): the caller's arrays, by value, beside
 // the KArgs and ModelLimits of the handle; `table` and `diagonal` as in PolicyArgs.  Like the policy kernel it has no row in
 // the table of kernel sets.

@@ -11,6 +11,7 @@
 // The kernel writes nothing but the caller's buffers: no workspace region, no solver state.
 #pragma once
 #include "aslr_common.hpp"
+#include "aslr_policy_noise.hpp"
 
 namespace aslr {
 
@@ -18,9 +19,13 @@ namespace aslr {
 #define ASLR_POLICY_FUSED 1 // 1: dynamics and cost of a knot from one knot_eval; 0: two evaluations (dynamics, then cost alone)
 #endif
 
-template <int NJ, int DAM, bool PLANAR>
-__global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits lim, PolicyArgs pa) {
+// PA: where the perturbations come from.  PolicyArgs (the default): the caller's arrays.  PolicyNoiseArgs
+// (aslr_policy_rollout_noise, the instantiations of aslr_policy_noise_nj2.hip): the lane draws them (aslr_policy_noise.hpp) at
+// the places where the arrays are read, and writes them out where a drawn_* buffer is given.
+template <int NJ, int DAM, bool PLANAR, class PA = PolicyArgs>
+__global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits lim, PA pa) {
   constexpr int NX = 4 * NJ, NU = ModelDims<NJ, DAM>::nu;
+  constexpr bool DRAW = std::is_same_v<PA, PolicyNoiseArgs>;
   constexpr int TEAM = 16, TPW = 4;
   using CH = std::conditional_t<PLANAR, ChainPlanar<NJ>, Chain3D<NJ>>;
   const int lane = threadIdx.x, team = lane / TEAM, al = lane % TEAM;
@@ -43,10 +48,24 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
         x[2 * p] += v.x; x[2 * p + 1] += v.y;
       }
     }
+    if constexpr (DRAW) {
+      if (pa.dx0_std) {
+        const double *sd = pa.dx0_std + (size_t)b * NX;
+        ASLR_UNROLL for (int p = 0; p < NX / 2; ++p) {
+          double za, zb;
+          noise_pair(pa.key, kNoiseDx0, 0, s, b, p, za, zb);
+          const double2 v = make_double2(noise_settled(sd[2 * p] * za), noise_settled(sd[2 * p + 1] * zb));
+          x[2 * p] += v.x; x[2 * p + 1] += v.y;
+          if (on && pa.drawn_dx0) *reinterpret_cast<double2 *>(pa.drawn_dx0 + ((size_t)s * B + b) * NX + 2 * p) = v;
+        }
+      }
+    }
   }
   // the plant of this lane: diag K and diag 1 / B -- the caller's arrays [nj][S][B] where given, else the trajectory's row
   // of the parameter table where one is set, else (use_k / use_b false) the diagonal of the knot's model
-  const bool table = pa.table != 0, use_k = pa.plant_stiffness || table, use_b = pa.plant_motor_inertia || table;
+  bool drawn_k = false, drawn_b = false;
+  if constexpr (DRAW) { drawn_k = pa.stiffness_rel_std != nullptr; drawn_b = pa.motor_inertia_rel_std != nullptr; }
+  const bool table = pa.table != 0, use_k = pa.plant_stiffness || table || drawn_k, use_b = pa.plant_motor_inertia || table || drawn_b;
   double pk[NJ], pbinv[NJ], lim_lb[NU], lim_ub[NU];
   ASLR_UNROLL for (int i = 0; i < NJ; ++i) { pk[i] = 0.0; pbinv[i] = 0.0; }
   ASLR_UNROLL for (int i = 0; i < NU; ++i) { lim_lb[i] = 0.0; lim_ub[i] = 0.0; }
@@ -60,6 +79,34 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
   }
   if (pa.plant_motor_inertia) {
     ASLR_UNROLL for (int i = 0; i < NJ; ++i) pbinv[i] = 1.0 / pa.plant_motor_inertia[((size_t)i * S + s) * B + b];
+  }
+  if constexpr (DRAW) {
+    // K_j = Knom_j exp(sigma_j z), B_j likewise: the nominal is the trajectory's row of the table (for B the reciprocal of
+    // the row, which holds 1 / B), else the diagonal the models share (the host's fact)
+    ASLR_UNROLL for (int p = 0; p < (NJ + 1) / 2; ++p) {
+      double z[2];
+      if (drawn_k) {
+        noise_pair(pa.key, kNoiseStiffness, 0, s, b, p, z[0], z[1]);
+        ASLR_UNROLL for (int h = 0; h < 2; ++h) {
+          const int i = 2 * p + h;
+          if (i < NJ) {
+            pk[i] = noise_settled((table ? pk[i] : pa.knom[i]) * exp(pa.stiffness_rel_std[(size_t)b * NJ + i] * z[h]));
+            if (on && pa.drawn_stiffness) pa.drawn_stiffness[((size_t)i * S + s) * B + b] = pk[i];
+          }
+        }
+      }
+      if (drawn_b) {
+        noise_pair(pa.key, kNoiseMotorInertia, 0, s, b, p, z[0], z[1]);
+        ASLR_UNROLL for (int h = 0; h < 2; ++h) {
+          const int i = 2 * p + h;
+          if (i < NJ) {
+            const double bi = noise_settled((table ? 1.0 / pbinv[i] : pa.bnom[i]) * exp(pa.motor_inertia_rel_std[(size_t)b * NJ + i] * z[h]));
+            if (on && pa.drawn_motor_inertia) pa.drawn_motor_inertia[((size_t)i * S + s) * B + b] = bi;
+            pbinv[i] = 1.0 / bi;
+          }
+        }
+      }
+    }
   }
   const typename CH::Consts cc(D, true);
   ModelRegs<NJ, NU> mr;
@@ -87,7 +134,10 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
   }
   int mi_next = 0;
   auto prefetch = [&](int t) {
-    const unsigned base = lds_address(stgD[t & 1]);
+    unsigned base = lds_address(stgD[t & 1]);
+    // (the drawing form feeds t to VALU work, and the compiler then keeps the knot counter in a vector register: the DMA's
+    // M0 operand needs the scalar)
+    if constexpr (DRAW) base = __builtin_amdgcn_readfirstlane(base);
     const size_t row = (size_t)min(a.ref_row0 + t, a.ref_last); // (the knot's row of the reference path)
     ASLR_UNROLL for (int q = 0; q < NPI; ++q) {
       if (don[q] && (!dctl[q] || t < T)) dma16<0, false>(dsrc[q] + (dref[q] ? row : (size_t)t) * dstr[q], base + q * DMAW * 8);
@@ -107,6 +157,35 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
     }
   };
   if (wsrc && T > 0) load_w(0);
+  // the drawing form: wdraw stands where wsrc does; the row of knot t is drawn where it would be loaded and, when
+  // drawn_disturbance is given, stored with the optional stores of the knot (nsw of them, behind the loads of the prefetch)
+  bool wdraw = false;
+  int nsw = 0;
+  double wsd[DRAW ? NX : 1];
+  double *wd_o = nullptr;
+  if constexpr (DRAW) {
+    wdraw = pa.noise_std != nullptr;
+    if (wdraw) {
+      ASLR_UNROLL for (int i = 0; i < NX; ++i) wsd[i] = pa.noise_std[(size_t)b * NX + i];
+      if (pa.drawn_disturbance) { wd_o = pa.drawn_disturbance + ((size_t)s * T * B + b) * NX; nsw = NX / 2; }
+    }
+  }
+  auto draw_w = [&](int t) {
+    if constexpr (DRAW) {
+      ASLR_UNROLL for (int p = 0; p < NX / 2; ++p) {
+        double za, zb;
+        noise_pair(pa.key, kNoiseDisturbance, t, s, b, p, za, zb);
+        wn[2 * p] = noise_settled(wsd[2 * p] * za); wn[2 * p + 1] = noise_settled(wsd[2 * p + 1] * zb);
+      }
+    }
+  };
+  auto store_w = [&](int t) { // wn, the row of knot t
+    if (on && wd_o) {
+      ASLR_UNROLL for (int p = 0; p < NX / 2; ++p)
+        *reinterpret_cast<double2 *>(wd_o + (size_t)t * B * NX + 2 * p) = make_double2(wn[2 * p], wn[2 * p + 1]);
+    }
+  };
+  if (wdraw && T > 0) { draw_w(0); store_w(0); }
   double *xs_o = pa.xs_closed ? pa.xs_closed + ((size_t)s * (T + 1) * B + b) * NX : nullptr; // knot t at + t B NX
   double *us_o = pa.us_closed ? pa.us_closed + ((size_t)s * T * B + b) * NU : nullptr;
 
@@ -114,9 +193,10 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
   int failed = -1;
   prefetch(0);
   for (int t = 0; t <= T; ++t) {
-    if (t == 0 || nst == 0) wait_vmcnt<0>();
-    else if (nst >= NX / 2 + NU / 2) wait_vmcnt<NX / 2 + NU / 2>();
-    else if (nst >= NX / 2) wait_vmcnt<NX / 2>();
+    const int nsk = nst + (t < T ? nsw : 0); // (knot t - 1 stored a drawn row only if knot t has one)
+    if (t == 0 || nsk == 0) wait_vmcnt<0>();
+    else if (nsk >= NX / 2 + NU / 2) wait_vmcnt<NX / 2 + NU / 2>();
+    else if (nsk >= NX / 2) wait_vmcnt<NX / 2>();
     else wait_vmcnt<NU / 2>();
     wave_sync();
     const double *stgT = stgD[t & 1] + team * BS;
@@ -128,7 +208,9 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
     ASLR_UNROLL for (int i = 0; i < NX; ++i) w[i] = wn[i];
     if (t < T) {
       if (wsrc && t + 1 < T) load_w(t + 1); // in flight while knot t computes
+      if (wdraw && t + 1 < T) draw_w(t + 1);
       prefetch(t + 1);
+      if (wdraw && t + 1 < T) store_w(t + 1);
     }
     if (on && xs_o) {
       ASLR_UNROLL for (int p = 0; p < NX / 2; ++p)
@@ -174,7 +256,7 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
     double mx = 0.0;
     ASLR_UNROLL for (int i = 0; i < NX; ++i) mx += fabs(xnext[i]);
     if (inf_norm_bad<NX>(mx, xnext) && failed < 0) failed = t; // NaN / Inf / |xnext|_inf >= 1e30, as the solver's rollout
-    if (wsrc) { ASLR_UNROLL for (int i = 0; i < NX; ++i) x[i] = xnext[i] + w[i]; }
+    if (wsrc || wdraw) { ASLR_UNROLL for (int i = 0; i < NX; ++i) x[i] = xnext[i] + w[i]; }
     else { ASLR_UNROLL for (int i = 0; i < NX; ++i) x[i] = xnext[i]; }
   }
   if (!on) return;
@@ -187,17 +269,19 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
   }
 }
 
-// the nx = 8 sizes; the 7-joint team form is policy_rollout_team_kernel (aslr_policy_team.inc.hpp, aslr_policy_rollout_all)
-int launch_policy_rollout(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st) {
+// the nx = 8 sizes; the 7-joint team form is policy_rollout_team_kernel (aslr_policy_team.inc.hpp, aslr_policy_rollout_all).
+// One launcher body for both argument types: fn is the entry point a refusal names.
+template <class PA>
+int launch_policy_rollout_as(const char *fn, int nj, int dam, const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st) {
   const dim3 grid((k.B + 3) / 4, (pa.S + 15) / 16), block(64);
   const auto go = [&](auto NJc, auto DAMc) {
     with_planar<decltype(NJc)::value>(k, [&](auto P) {
-      hipLaunchKernelGGL((policy_rollout_kernel<decltype(NJc)::value, decltype(DAMc)::value, decltype(P)::value>), grid, block, 0, st, k, lim, pa);
+      hipLaunchKernelGGL((policy_rollout_kernel<decltype(NJc)::value, decltype(DAMc)::value, decltype(P)::value, PA>), grid, block, 0, st, k, lim, pa);
     });
   };
   if (nj == 2 && dam == ASLR_DAM_SEA) go(std::integral_constant<int, 2>{}, std::integral_constant<int, ASLR_DAM_SEA>{});
   else if (nj == 2 && dam == ASLR_DAM_VSA) go(std::integral_constant<int, 2>{}, std::integral_constant<int, ASLR_DAM_VSA>{});
-  else return fail(ASLR_E_INVALID, "aslr_policy_rollout: no policy roll-out kernel for nj = %d", nj);
+  else return fail(ASLR_E_INVALID, "%s: no policy roll-out kernel for nj = %d", fn, nj);
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

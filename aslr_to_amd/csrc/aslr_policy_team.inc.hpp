@@ -16,12 +16,17 @@
 //     - it writes nothing but the caller's buffers.
 #pragma once
 #include "aslr_team_step.hpp"
+#include "aslr_policy_noise.hpp"
 
 namespace aslr {
 
-template <int NJ, int DAM>
-__global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, ModelLimits lim, PolicyArgs pa) {
+// PA: where the perturbations come from, as in policy_rollout_kernel (aslr_policy.inc.hpp).  With PolicyNoiseArgs lane c
+// draws the pairs that hold the entries it owns (the other half of a pair is thrown away: what matters is that every entry
+// has the value of the definition).
+template <int NJ, int DAM, class PA = PolicyArgs>
+__global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, ModelLimits lim, PA pa) {
   using C = FwdTeam<NJ, DAM>;
+  constexpr bool DRAW = std::is_same_v<PA, PolicyNoiseArgs>;
   constexpr int NX = C::NX, NU = C::NU;
   constexpr bool VSA = C::VSA;
   constexpr int TPB = 16; // teams (samples) per block
@@ -67,11 +72,26 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
 
   // ---- the plant of this team, entry cj: the caller's arrays [nj][S][B] where given, else the trajectory's row of the
   // parameter table where one is set, else (use_k / use_b false) the row of the knot's model ----
-  const bool table = pa.table != 0, use_k = pa.plant_stiffness || table, use_b = pa.plant_motor_inertia || table;
+  bool drawn_k = false, drawn_b = false;
+  if constexpr (DRAW) { drawn_k = pa.stiffness_rel_std != nullptr; drawn_b = pa.motor_inertia_rel_std != nullptr; }
+  const bool table = pa.table != 0, use_k = pa.plant_stiffness || table || drawn_k, use_b = pa.plant_motor_inertia || table || drawn_b;
   double k_cj = 0.0, b_cj = 0.0, lb_c = 0.0, ub_c = 0.0, lb_s = 0.0, ub_s = 0.0; // (lb_s / ub_s: the stiffness row, VSA)
   if (table) team_table_row<NJ, NU, VSA>(traj_params_at(D, b), cj, B, k_cj, b_cj, lb_c, ub_c, lb_s, ub_s);
   if (pa.plant_stiffness) k_cj = pa.plant_stiffness[((size_t)cj * S + s) * B + b];
   if (pa.plant_motor_inertia) b_cj = 1.0 / pa.plant_motor_inertia[((size_t)cj * S + s) * B + b];
+  if constexpr (DRAW) {
+    // K_cj = Knom exp(sigma z), B_cj likewise: the nominal is the trajectory's row of the table (for B the reciprocal of the
+    // row, which holds 1 / B), else the diagonal the models share (the host's fact)
+    if (drawn_k) {
+      k_cj = noise_settled((table ? k_cj : pa.knom[cj]) * exp(pa.stiffness_rel_std[(size_t)b * NJ + cj] * noise_entry(pa.key, kNoiseStiffness, 0, s, b, cj)));
+      if (on && jl && pa.drawn_stiffness) pa.drawn_stiffness[((size_t)cj * S + s) * B + b] = k_cj;
+    }
+    if (drawn_b) {
+      const double bi = noise_settled((table ? 1.0 / b_cj : pa.bnom[cj]) * exp(pa.motor_inertia_rel_std[(size_t)b * NJ + cj] * noise_entry(pa.key, kNoiseMotorInertia, 0, s, b, cj)));
+      if (on && jl && pa.drawn_motor_inertia) pa.drawn_motor_inertia[((size_t)cj * S + s) * B + b] = bi;
+      b_cj = 1.0 / bi;
+    }
+  }
   double Krow[NJ], Srow[NJ], Brow[NJ], dt = 0.0;
   ASLR_UNROLL for (int j = 0; j < NJ; ++j) { Krow[j] = 0.0; Srow[j] = 0.0; Brow[j] = 0.0; }
   bool has_lim = false;
@@ -87,6 +107,13 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
     if (e < NX) {
       double v = a.x0[(size_t)b * NX + e];
       if (pa.dx0) v += pa.dx0[((size_t)s * B + b) * NX + e]; // (no `+ 0.0` without it: the sign of a zero is a bit too)
+      if constexpr (DRAW) {
+        if (pa.dx0_std) {
+          const double d = noise_settled(pa.dx0_std[(size_t)b * NX + e] * noise_entry(pa.key, kNoiseDx0, 0, s, b, e));
+          v += d;
+          if (on && pa.drawn_dx0) pa.drawn_dx0[((size_t)s * B + b) * NX + e] = d;
+        }
+      }
       xT[e] = v;
     }
   }
@@ -97,6 +124,27 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
     ASLR_UNROLL for (int k = 0; k < 4; ++k) wn[k] = wsrc[(size_t)t * B * NX + k * NJ];
   };
   if (wsrc && T > 0) load_w(0);
+  // the drawing form: wdraw stands where wsrc does; the lane's four entries of the row of knot t are drawn where they would
+  // be loaded and, when drawn_disturbance is given, stored with the optional stores of the knot
+  bool wdraw = false;
+  double wsd[4] = {0.0, 0.0, 0.0, 0.0};
+  double *wd_o = nullptr;
+  if constexpr (DRAW) {
+    wdraw = pa.noise_std != nullptr;
+    if (wdraw) {
+      ASLR_UNROLL for (int k = 0; k < 4; ++k) wsd[k] = pa.noise_std[(size_t)b * NX + cj + k * NJ];
+      if (pa.drawn_disturbance) wd_o = pa.drawn_disturbance + ((size_t)s * T * B + b) * NX + cj;
+    }
+  }
+  auto draw_w = [&](int t) {
+    if constexpr (DRAW) {
+      ASLR_UNROLL for (int k = 0; k < 4; ++k) wn[k] = noise_settled(wsd[k] * noise_entry(pa.key, kNoiseDisturbance, t, s, b, cj + k * NJ));
+    }
+  };
+  auto store_w = [&](int t) { // wn, the row of knot t
+    if (on && jl && wd_o) { ASLR_UNROLL for (int k = 0; k < 4; ++k) wd_o[(size_t)t * B * NX + k * NJ] = wn[k]; }
+  };
+  if (wdraw && T > 0) { draw_w(0); store_w(0); }
   double *xs_o = pa.xs_closed ? pa.xs_closed + ((size_t)s * (T + 1) * B + b) * NX : nullptr; // knot t at + t B NX
   double *us_o = pa.us_closed ? pa.us_closed + ((size_t)s * T * B + b) * NU : nullptr;
   auto store_x = [&](int t) { // the team's state as row t of xs_closed, 4 contiguous entries per lane
@@ -155,6 +203,7 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
     ASLR_UNROLL for (int k = 0; k < 4; ++k) w[k] = wn[k];
     prefetch(t + 1); // in flight while the dynamics of knot t compute
     if (wsrc && t + 1 < T) load_w(t + 1);
+    if (wdraw && t + 1 < T) { draw_w(t + 1); store_w(t + 1); }
     // (the optional stores of a knot go out after the loads of the next one)
     store_x(t);
     if (on && jl && us_o) {
@@ -174,7 +223,7 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
     if ((__ballot(bad) & team_bits) && failed < 0) failed = t; // NaN / Inf / |xnext|_inf >= 1e30, as the solver's rollout
     wave_sync(); // every lane of the team has read the old state
     if (jl) {
-      if (wsrc) { xT[c] = nxt[0] + w[0]; xT[NJ + c] = nxt[2] + w[1]; xT[2 * NJ + c] = nxt[1] + w[2]; xT[3 * NJ + c] = nxt[3] + w[3]; }
+      if (wsrc || wdraw) { xT[c] = nxt[0] + w[0]; xT[NJ + c] = nxt[2] + w[1]; xT[2 * NJ + c] = nxt[1] + w[2]; xT[3 * NJ + c] = nxt[3] + w[3]; }
       else { xT[c] = nxt[0]; xT[NJ + c] = nxt[2]; xT[2 * NJ + c] = nxt[1]; xT[3 * NJ + c] = nxt[3]; }
     }
   }
@@ -188,12 +237,14 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
   if (jl && pa.x_final) team_store_state_row(pa.x_final + sb * NX + 4 * c, xT, c);
 }
 
-// the nx = 28 sizes: grid (trajectories, groups of 16 samples), one block = 2 waves of 8 teams
-int launch_policy_rollout_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st) {
+// the nx = 28 sizes: grid (trajectories, groups of 16 samples), one block = 2 waves of 8 teams.  One launcher body for both
+// argument types: fn is the entry point a refusal names.
+template <class PA>
+int launch_policy_rollout_team_as(const char *fn, int nj, int dam, const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st) {
   const dim3 grid(k.B, (pa.S + 15) / 16), block(128);
-  if (nj == 7 && dam == ASLR_DAM_SEA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_SEA>), grid, block, 0, st, k, lim, pa);
-  else if (nj == 7 && dam == ASLR_DAM_VSA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_VSA>), grid, block, 0, st, k, lim, pa);
-  else return fail(ASLR_E_INVALID, "aslr_policy_rollout_all: no team roll-out kernel for nj = %d", nj);
+  if (nj == 7 && dam == ASLR_DAM_SEA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_SEA, PA>), grid, block, 0, st, k, lim, pa);
+  else if (nj == 7 && dam == ASLR_DAM_VSA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_VSA, PA>), grid, block, 0, st, k, lim, pa);
+  else return fail(ASLR_E_INVALID, "%s: no team roll-out kernel for nj = %d", fn, nj);
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -397,6 +397,53 @@ class Engine(object):
                                    xs=None if xs is None else xs.permute(2, 0, 1, 3),
                                    us=None if us is None else self.cut_u(us.permute(2, 0, 1, 3)))
 
+    def _sigma(self, v, n, name):
+        """a sigma of policy_rollout_noise: None, a scalar, [n] or [B, n] -> None or a contiguous [B, n] device tensor"""
+        if v is None:
+            return None
+        t = self._f64(v)
+        if t.dim() > 2 or (t.dim() >= 1 and t.shape[-1] != n) or (t.dim() == 2 and t.shape[0] != self.B):
+            raise ValueError("%s must be a scalar or have shape [%d] or [%d, %d], not %s" % (name, n, self.B, n, list(t.shape)))
+        return t.expand(self.B, n).contiguous()
+
+    def policy_rollout_noise(self, n_samples, seed, noise_std=None, dx0_std=None, stiffness_rel_std=None,
+                             motor_inertia_rel_std=None, clamp=False, keep_trajectories=False, keep_draws=False, sample0=0,
+                             trajectory0=0):
+        """policy_rollout with the perturbations drawn on the device (aslr_policy_rollout_noise,
+        include/aslr_to_amd_policy_noise.h, which defines the generator): sample s of trajectory b gets disturbance =
+        noise_std z, dx0 = dx0_std z, K_j = Knom_j exp(stiffness_rel_std z), B_j = Bnom_j exp(motor_inertia_rel_std z) with
+        standard normals z that depend on (seed, knot, sample0 + s, trajectory0 + b, entry) alone.  Each sigma is None (that
+        source is absent), a scalar, [nx] / [nj] or [B, nx] / [B, nj]; at least one is given.  seed: an integer in
+        [0, 2^64).  -> PolicyRolloutResult; with keep_draws it also has `draws`, a dict of batch-major tensors
+        plant_stiffness, plant_motor_inertia [B, S, nj], dx0 [B, S, nx], disturbance [B, S, T, nx] (None for an absent
+        source): the very arguments policy_rollout accepts.  Writes nothing into the workspace."""
+        torch = _torch()
+        S, B, T, nx, nu, nj = int(n_samples), self.B, self.T, self.nx, self.nu, self.nx // 4
+        seed = int(seed)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must lie in [0, 2^64), not %d" % seed)
+        sw, s0 = self._sigma(noise_std, nx, "noise_std"), self._sigma(dx0_std, nx, "dx0_std")
+        sk, sb = self._sigma(stiffness_rel_std, nj, "stiffness_rel_std"), self._sigma(motor_inertia_rel_std, nj, "motor_inertia_rel_std")
+        n = max(S, 0)  # (S <= 0: the library refuses by name)
+        with torch.cuda.device(self.device):
+            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
+            cost, failed, xf = new(torch.float64, n, B), new(torch.int32, n, B), new(torch.float64, n, B, nx)
+            xs = new(torch.float64, n, T + 1, B, nx) if keep_trajectories else None
+            us = new(torch.float64, n, T, B, nu) if keep_trajectories else None
+            kept = lambda sigma, *shape: new(torch.float64, *shape) if keep_draws and sigma is not None else None
+            dk, db, d0, dw = kept(sk, nj, n, B), kept(sb, nj, n, B), kept(s0, n, B, nx), kept(sw, n, T, B, nx)
+        self._call("aslr_policy_rollout_noise", S, int(sample0), int(trajectory0), C.c_uint64(seed), _ptr(sw), _ptr(s0), _ptr(sk),
+                   _ptr(sb), 1 if clamp else 0, _ptr(cost), _ptr(failed), _ptr(xf), _ptr(xs), _ptr(us), _ptr(dk), _ptr(db),
+                   _ptr(d0), _ptr(dw), self._stream())
+        r = PolicyRolloutResult(cost=cost.t(), failed_knot=failed.t(), x_final=xf.permute(1, 0, 2),
+                                xs=None if xs is None else xs.permute(2, 0, 1, 3),
+                                us=None if us is None else self.cut_u(us.permute(2, 0, 1, 3)))
+        if keep_draws:
+            back = lambda t, *perm: None if t is None else t.permute(*perm)
+            r.draws = dict(plant_stiffness=back(dk, 2, 1, 0), plant_motor_inertia=back(db, 2, 1, 0), dx0=back(d0, 1, 0, 2),
+                           disturbance=back(dw, 2, 0, 1, 3))
+        return r
+
     def policy_covariance(self, sigma0=None, noise_var=None, keep_cov=False):
         """First-order state and control covariance under the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), by
         one calcDiff sweep and one forward sweep (aslr_policy_covariance, include/aslr_to_amd_cov.h): Sigma_{t+1} =
