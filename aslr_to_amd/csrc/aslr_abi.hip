@@ -630,12 +630,23 @@ SolverDev to_dev(const aslr_solver_params_t *sp, int standalone, int store_v) {
 }
 
 // ---- the supported sizes: one row each; aslr_problem_create looks the row up and is the only place that refuses a size ----
-// (TP: the row a handle switches to while a per-trajectory parameter table is set; dam_eval / dam_residuals / frame
-//  placements keep the models' constants and are shared by both rows)
+// (TP: the row a handle switches to while a per-trajectory parameter table is set.  Shared by both rows: dam_eval / dam_residuals /
+//  frame placements, which keep the models' constants, and the extension kernels, which are told of the table in their arguments)
+// the roll-out and the plant phase of a size: by 8-lane teams, or a sample / trajectory per lane (only the form named is referenced)
+template <int NJ, int DAM, class PA> constexpr auto policy_launcher() {
+  if constexpr (SizeTraits<NJ, DAM>::team_rollout) return launch_policy_rollout_team<NJ, DAM, PA>; else return launch_policy_rollout<NJ, DAM, PA>;
+}
+template <int NJ, int DAM> constexpr auto mpc_plant_launcher() {
+  if constexpr (SizeTraits<NJ, DAM>::team_rollout) return launch_mpc_plant_team<NJ, DAM>; else return launch_mpc_plant<NJ, DAM>;
+}
 template <int NJ, int DAM, bool TP = false>
 constexpr KernelSet kernel_set() {
-  return {NJ, DAM, TP, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM, TP>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
-          launch_quasi_static<NJ, DAM, TP>, launch_forward<NJ, DAM, TP>, launch_backward<NJ, DAM, TP>};
+  constexpr KernelSet ks = {NJ, DAM, TP, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM, TP>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
+                            launch_quasi_static<NJ, DAM, TP>, launch_forward<NJ, DAM, TP>, launch_backward<NJ, DAM, TP>, launch_adjoint<NJ, DAM>, launch_covariance<NJ, DAM>,
+                            launch_plant_sens<NJ, DAM>, policy_launcher<NJ, DAM, PolicyArgs>(), policy_launcher<NJ, DAM, PolicyNoiseArgs>(), mpc_plant_launcher<NJ, DAM>()};
+  static_assert(ks.calc && ks.dam_eval && ks.dam_residuals && ks.frame_placement && ks.quasi_static && ks.forward && ks.backward && ks.adjoint && ks.covariance &&
+                ks.plant_sens && ks.policy_rollout && ks.policy_rollout_noise && ks.mpc_plant, "a row of kKernelSets lacks a launcher");
+  return ks;
 }
 constexpr KernelSet kKernelSets[] = {
     kernel_set<2, ASLR_DAM_SEA>(),
@@ -932,26 +943,30 @@ int build_param_rows(const char *fn, const aslr_problem *p, const aslr_traj_para
 // The two sweeps behind aslr_cost_sensitivity, shared with aslr_design_descent: calcDiff on (XS, US) as aslr_calc_diff runs it,
 // then adjoint_kernel with the diagonals of the models (the table's rows while one is set) into the outputs given (each
 // nullable).  Refuses nothing: the callers have checked what they must (diagonal K and B, no zero the kernel divides by).
-int adjoint_sweeps(aslr_problem *p, double *d_stiffness, double *d_motor_inertia, double *d_x0, double *costate, hipStream_t st) {
-  const int nj = p->nj, nm = p->desc.nmodels;
-  const bool sea = p->dam == ASLR_DAM_SEA;
-  const aslr_model_t *M = p->desc.models;
-  AdjointArgs a;
-  memset(&a, 0, sizeof a);
-  for (int i = 0; i < nm; ++i) {
-    a.dt[i] = M[i].dt;
+// dt and the diagonals of K (SEA; 0 for VSA) and of 1 / B of every model, for the adjoint and the tangent sweep; `pl` is zeroed
+void fill_sweep_plant(const aslr_problem *p, SweepPlant *pl) {
+  const int nj = p->nj;
+  for (int i = 0; i < p->desc.nmodels; ++i) {
+    const aslr_model_t &M = p->desc.models[i];
+    pl->dt[i] = M.dt;
     for (int j = 0; j < nj; ++j) {
-      a.K[i][j] = sea ? M[i].K[j * nj + j] : 0.0;
-      a.Binv[i][j] = 1.0 / M[i].B[j * nj + j];
+      pl->K[i][j] = p->dam == ASLR_DAM_SEA ? M.K[j * nj + j] : 0.0;
+      pl->Binv[i][j] = 1.0 / M.B[j * nj + j];
     }
   }
+}
+
+int adjoint_sweeps(aslr_problem *p, double *d_stiffness, double *d_motor_inertia, double *d_x0, double *costate, hipStream_t st) {
+  AdjointArgs a;
+  memset(&a, 0, sizeof a);
+  fill_sweep_plant(p, &a.plant);
   if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
   const KArgs &k = p->k;
   a.deriv = k.deriv; a.xs = k.xs; a.xnext = k.xnext; a.node_model = k.node_model;
   a.traj_params = p->ks->traj_params ? reinterpret_cast<const double *>(region(p, ASLR_R_TRAJ_PARAMS)) : nullptr;
   a.d_stiffness = d_stiffness; a.d_motor_inertia = d_motor_inertia; a.d_x0 = d_x0; a.costate = costate;
   a.B = k.B; a.T = k.T;
-  return launch_adjoint(p->nx, p->nu, a, st);
+  return p->ks->adjoint(a, st);
 }
 
 // the motor inertia behind the reciprocal rows of build_param_rows, [nj][n]
@@ -1192,8 +1207,6 @@ int aslr_policy_covariance(aslr_problem_t *p, const double *sigma0, const double
     return fail(ASLR_E_INVALID, "aslr_policy_covariance: all five outputs are NULL: nothing to compute");
   if (!sigma0 && !noise_var)
     return fail(ASLR_E_INVALID, "aslr_policy_covariance: sigma0 and noise_var are both NULL: nothing to propagate");
-  if (!has_covariance_kernel(p->nx, p->nu)) // (before the calcDiff sweep: a refusal writes nothing)
-    return fail(ASLR_E_INVALID, "aslr_policy_covariance: no covariance kernel for records of (nx = %d, nu = %d)", p->nx, p->nu);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
   const KArgs &k = p->k;
@@ -1203,7 +1216,7 @@ int aslr_policy_covariance(aslr_problem_t *p, const double *sigma0, const double
   a.sigma0 = sigma0; a.noise_var = noise_var;
   a.x_var = x_var; a.u_var = u_var; a.cov_final = cov_final; a.cov = cov; a.cost_increase = cost_increase;
   a.B = k.B; a.T = k.T;
-  return launch_covariance(p->nx, p->nu, a, st);
+  return p->ks->covariance(a, st);
 }
 
 int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var, const double *motor_inertia_var,
@@ -1219,22 +1232,12 @@ int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var
     return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: a stiffness argument on a VSA model, which takes its stiffness from u");
   if ((x_var || u_var) && !stiffness_var && !motor_inertia_var)
     return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: x_var or u_var with stiffness_var and motor_inertia_var both NULL: no variance to propagate");
-  if (!has_plant_sens_kernel(p->nx, p->nu)) // (before the calcDiff sweep: a refusal writes nothing)
-    return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: no kernel for records of (nx = %d, nu = %d)", p->nx, p->nu);
   // the stiffness columns are computed when an output of theirs, or their variance in x_var / u_var, is asked for
   const bool stiff = dx_dstiffness || dxT_dstiffness || dcost_dstiffness || (stiffness_var && (x_var || u_var));
   if (int rc = model_refusals("aslr_policy_plant_sensitivity", p, true, stiff)) return rc;
-  const int nj = p->nj;
-  const aslr_model_t *M = p->desc.models;
   PlantSensArgs a;
   memset(&a, 0, sizeof a);
-  for (int i = 0; i < p->desc.nmodels; ++i) {
-    a.dt[i] = M[i].dt;
-    for (int j = 0; j < nj; ++j) {
-      a.K[i][j] = sea ? M[i].K[j * nj + j] : 0.0;
-      a.Binv[i][j] = 1.0 / M[i].B[j * nj + j];
-    }
-  }
+  fill_sweep_plant(p, &a.plant);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
   const KArgs &k = p->k;
@@ -1244,7 +1247,7 @@ int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var
   a.dx_k = dx_dstiffness; a.dx_b = dx_dmotor_inertia; a.dxT_k = dxT_dstiffness; a.dxT_b = dxT_dmotor_inertia;
   a.dcost_k = dcost_dstiffness; a.dcost_b = dcost_dmotor_inertia; a.x_var = x_var; a.u_var = u_var;
   a.B = k.B; a.T = k.T; a.stiff = stiff;
-  return launch_plant_sens(p->nx, p->nu, a, st);
+  return p->ks->plant_sens(a, st);
 }
 
 // aslr_policy_rollout, aslr_policy_rollout_all (include/aslr_to_amd_policy_all.h) and aslr_policy_rollout_noise
@@ -1291,8 +1294,6 @@ int policy_rollout(const char *fn, bool arms, aslr_problem_t *p, int n_samples, 
     return fail(ASLR_E_INVALID, "%s: all five outputs are NULL: nothing to compute", fn);
   if (p->nj != 2 && !arms)
     return fail(ASLR_E_INVALID, "%s: the roll-out kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle (the 7-joint team form is not built); aslr_policy_rollout_all serves every size", fn, p->nj);
-  if (p->nj != 2 && p->nj != 7)
-    return fail(ASLR_E_INVALID, "%s: no roll-out kernel for this %d-joint handle", fn, p->nj);
   if (int rc = draw ? noise_refusals(fn, p, n_samples, sample0, trajectory0, *draw) : plant_arg_refusals(fn, p, plant_stiffness, plant_motor_inertia)) return rc;
   const bool table = p->ks->traj_params;
   PolicyArgs own;
@@ -1302,14 +1303,14 @@ int policy_rollout(const char *fn, bool arms, aslr_problem_t *p, int n_samples, 
   a.cost = cost; a.failed_knot = failed_knot; a.x_final = x_final; a.xs_closed = xs_closed; a.us_closed = us_closed;
   a.S = n_samples; a.clamp = clamp != 0;
   a.table = table; a.diagonal = table || plant_stiffness || plant_motor_inertia;
-  if (!draw) return (p->nj == 2 ? launch_policy_rollout : launch_policy_rollout_team)(p->nj, p->dam, p->k, p->limits, a, static_cast<hipStream_t>(stream));
+  if (!draw) return p->ks->policy_rollout(p->k, p->limits, a, static_cast<hipStream_t>(stream));
   draw->diagonal = table || draw->stiffness_rel_std || draw->motor_inertia_rel_std;
   draw->key.sample0 = (uint32_t)sample0; draw->key.trajectory0 = (uint32_t)trajectory0;
   for (int j = 0; j < p->nj; ++j) { // (read by the kernel only where noise_refusals found one nominal)
     draw->knom[j] = p->desc.models[0].K[j * p->nj + j];
     draw->bnom[j] = p->desc.models[0].B[j * p->nj + j];
   }
-  return (p->nj == 2 ? launch_policy_rollout_noise : launch_policy_rollout_noise_team)(p->nj, p->dam, p->k, p->limits, *draw, static_cast<hipStream_t>(stream));
+  return p->ks->policy_rollout_noise(p->k, p->limits, *draw, static_cast<hipStream_t>(stream));
 }
 } // namespace
 
@@ -1489,8 +1490,6 @@ int mpc_run_plant(const char *fn, bool arms, aslr_problem_t *p, const aslr_solve
   if (hold < 1 || hold > T) return fail(ASLR_E_INVALID, "%s: hold = %d must lie in [1, T = %d]", fn, hold, T);
   if (p->nj != 2 && !arms)
     return fail(ASLR_E_INVALID, "%s: the plant kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle; aslr_mpc_run_plant_all serves every size", fn, p->nj);
-  if (p->nj != 2 && p->nj != 7)
-    return fail(ASLR_E_INVALID, "%s: no plant kernel for this %d-joint handle", fn, p->nj);
   if (int rc = plant_arg_refusals(fn, p, plant_stiffness, plant_motor_inertia)) return rc;
   const long long N = (long long)mpc->n_steps * hold;
   const int32_t row0 = p->k.ref_row0;
@@ -1517,7 +1516,7 @@ int mpc_run_plant(const char *fn, bool arms, aslr_problem_t *p, const aslr_solve
     pa.closed_cost = closed_cost; pa.failed_knot = failed_knot;
     pa.hold = hold; pa.k0 = (int32_t)k0; pa.first = s == 0; pa.clamp = clamp != 0;
     pa.table = table; pa.diagonal = table || plant_stiffness || plant_motor_inertia;
-    if (int rc = (p->nj == 2 ? launch_mpc_plant : launch_mpc_plant_team)(p->nj, p->dam, ks, p->limits, pa, st)) return rc;
+    if (int rc = p->ks->mpc_plant(ks, p->limits, pa, st)) return rc;
     MpcHoldDev m;
     m.nx = p->nx; m.nu = p->nu; m.h = hold;
     m.xplus = mpc->x_closed + (k0 + hold) * B * nx; // (the plant kernel left x+ in the row behind its last record)

@@ -35,14 +35,15 @@ __global__ void __launch_bounds__(64) adjoint_kernel(AdjointArgs a) {
   const bool motor = j >= NJ && j < 2 * NJ; // lane nj + jj: the parameter terms of joint jj
   const int jj = motor ? j - NJ : 0;
 
-  // 1 / K_jj and 1 / B_jj of this lane's joint, per action model (one value for all of them with a table)
+  // 1 / K_jj and 1 / B_jj of this lane's joint, per action model (one value for all of them with a table).  As the model choice in
+  // the loop, written out here and in plant_sens_kernel: through a helper both kernels came out changed (profiles/ext_rows/)
   double rk[ASLR_MAX_MODELS], bi[ASLR_MAX_MODELS];
   double tk = 0.0, tv = 0.0;
   if (a.traj_params) { tk = a.traj_params[(size_t)jj * B + b]; tv = a.traj_params[(size_t)(NJ + jj) * B + b]; }
   ASLR_UNROLL for (int m = 0; m < ASLR_MAX_MODELS; ++m) {
-    double k = a.K[m][0], v = a.Binv[m][0];
+    double k = a.plant.K[m][0], v = a.plant.Binv[m][0];
     ASLR_UNROLL for (int c = 1; c < NJ; ++c)
-      if (jj == c) { k = a.K[m][c]; v = a.Binv[m][c]; }
+      if (jj == c) { k = a.plant.K[m][c]; v = a.plant.Binv[m][c]; }
     if (a.traj_params) { k = tk; v = tv; }
     rk[m] = k != 0.0 ? 1.0 / k : 0.0;
     bi[m] = v;
@@ -70,9 +71,9 @@ __global__ void __launch_bounds__(64) adjoint_kernel(AdjointArgs a) {
     ASLR_UNROLL for (int i = 0; i < NX; ++i) g = fma(cur.col[i], __shfl(lam, i, TEAM), g);
     const double lam_v = __shfl(lam, 3 * NJ + jj, TEAM); // lambda_{t+1}[3nj + jj]
     const int mi = ((const int32_t __attribute__((address_space(4))) *)(a.node_model))[t];
-    double dt = a.dt[0], rkm = rk[0], bim = bi[0];
+    double dt = a.plant.dt[0], rkm = rk[0], bim = bi[0];
     ASLR_UNROLL for (int m = 1; m < ASLR_MAX_MODELS; ++m)
-      if (mi == m) { dt = a.dt[m]; rkm = rk[m]; bim = bi[m]; }
+      if (mi == m) { dt = a.plant.dt[m]; rkm = rk[m]; bim = bi[m]; }
     const double delta = cur.ql - cur.qm, D = cur.vmn - cur.vm;
     acc_k += -(delta * rkm) * (g - lam);
     acc_b += -bim * (dt * D * lam + D * lam_v);
@@ -88,17 +89,9 @@ __global__ void __launch_bounds__(64) adjoint_kernel(AdjointArgs a) {
   }
 }
 
-// the four record shapes in use: (8, 2) 2-joint SEA / pendulum, (8, 4) 2-joint VSA, (28, 7) 7-joint SEA, (28, 14) 7-joint VSA
-int launch_adjoint(int nx, int nu, const AdjointArgs &a, hipStream_t st) {
-  const auto go = [&](auto kernel, int team) {
-    const int tpw = 64 / team;
-    hipLaunchKernelGGL(kernel, dim3((a.B + tpw - 1) / tpw), dim3(64), 0, st, a);
-  };
-  if (nx == 8 && nu == 2) go(adjoint_kernel<8, 2>, 8);
-  else if (nx == 8 && nu == 4) go(adjoint_kernel<8, 4>, 8);
-  else if (nx == 28 && nu == 7) go(adjoint_kernel<28, 7>, 32);
-  else if (nx == 28 && nu == 14) go(adjoint_kernel<28, 14>, 32);
-  else return fail(ASLR_E_INVALID, "aslr_cost_sensitivity: no adjoint kernel for records of (nx = %d, nu = %d)", nx, nu);
+template <int NJ, int DAM>
+int launch_adjoint(const AdjointArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL((adjoint_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -155,6 +155,8 @@ struct SizeTraits {
   static constexpr bool boxddp_only = big_vsa;
   static constexpr int cost_tag = big_vsa ? 14 : NJ;      // instantiation tag of sum_cost_kernel / select_kernel
   static constexpr bool reg_column = !big_vsa;            // backward: the register-column kernel (ASLR_BWD_HS > 0) is built
+  // adjoint / covariance / tangent sweeps: one wave per block, a team of 8 (nx = 8) or 32 (nx = 28) lanes per trajectory
+  static constexpr int sweep_blocks(int B) { return NJ == 2 ? (B + 7) / 8 : (B + 1) / 2; }
 };
 
 // a run-time bool as a template argument: f(std::true_type) or f(std::false_type)
@@ -184,9 +186,16 @@ template <int NJ, int DAM, bool TP = false> int launch_forward(const KArgs &k, c
 // hs: ASLR_BWD_HS (0: the size's default decomposition); mfma: ASLR_BLK_MFMA (block kernel of nx = 28 only)
 template <int NJ, int DAM, bool TP = false> int launch_backward(const KArgs &k, int hs, bool mfma, const SolverDev &sd, const ModelLimits &lim, hipStream_t st);
 
-// Adjoint sweep (aslr_cost_sensitivity, aslr_adjoint.inc.hpp): what adjoint_kernel reads and writes, by value.  The kernel
-// depends on the record shape (nx, nu) alone, and one template serves handles with and without a parameter table
-// (traj_params == nullptr: K and 1 / B of the node's model, below), so it has no row in the table of kernel sets.
+// dt and the diagonals of K and 1 / B per action model, as the adjoint and the tangent sweep read them: the last member of
+// both argument blocks (as a base struct it would come first and move every kernel-argument offset)
+struct SweepPlant {
+  double dt[ASLR_MAX_MODELS];
+  double K[ASLR_MAX_MODELS][ASLR_MAX_NJ], Binv[ASLR_MAX_MODELS][ASLR_MAX_NJ]; // K = 0: no stiffness term (VSA)
+};
+
+// Adjoint sweep (aslr_cost_sensitivity, aslr_adjoint.inc.hpp): what adjoint_kernel reads and writes, by value.  One template
+// serves handles with and without a parameter table (traj_params == nullptr: K and 1 / B of the node's model, `plant`),
+// so the TP rows of the table of kernel sets share the launcher with the plain rows.
 struct AdjointArgs {
   const double *deriv, *xs, *xnext;
   const int32_t *node_model;
@@ -194,25 +203,22 @@ struct AdjointArgs {
   double *d_stiffness, *d_motor_inertia, *d_x0; // [nj][B], [nj][B], [nx][B]; each nullable
   double *costate;                              // [T+1][B][nx]; nullable
   int32_t B, T;
-  double dt[ASLR_MAX_MODELS];
-  double K[ASLR_MAX_MODELS][ASLR_MAX_NJ], Binv[ASLR_MAX_MODELS][ASLR_MAX_NJ]; // diagonals; K = 0: no stiffness term (VSA)
+  SweepPlant plant;
 };
-int launch_adjoint(int nx, int nu, const AdjointArgs &a, hipStream_t st);
+template <int NJ, int DAM> int launch_adjoint(const AdjointArgs &a, hipStream_t st);
 
 // Closed-loop covariance sweep (aslr_policy_covariance, aslr_covariance.inc.hpp): what covariance_kernel reads and writes, by
-// value.  Like the adjoint kernel it depends on the record shape (nx, nu) alone and has no row in the table of kernel sets.
+// value.  It reads no model constant: one launcher per size, shared by its two rows.
 struct CovarianceArgs {
   const double *deriv, *kgain;
   const double *sigma0, *noise_var;                         // [B][nx][nx], [T][B][nx]; each nullable (zero)
   double *x_var, *u_var, *cov_final, *cov, *cost_increase; // [T+1][B][nx], [T][B][nu], [B][nx][nx], [T+1][B][nx][nx], [B]; each nullable
   int32_t B, T;
 };
-bool has_covariance_kernel(int nx, int nu);
-int launch_covariance(int nx, int nu, const CovarianceArgs &a, hipStream_t st);
+template <int NJ, int DAM> int launch_covariance(const CovarianceArgs &a, hipStream_t st);
 
 // Tangent sweep (aslr_policy_plant_sensitivity, aslr_plant_sens.inc.hpp): what plant_sens_kernel reads and writes, by value.
-// The parameters of a trajectory are taken as AdjointArgs has them; like the adjoint kernel it depends on the record shape
-// alone and has no row in the table of kernel sets.
+// The parameters of a trajectory are taken as AdjointArgs has them, and the rows share the launcher in the same way.
 struct PlantSensArgs {
   const double *deriv, *kgain, *xs, *xnext;
   const int32_t *node_model;
@@ -223,16 +229,14 @@ struct PlantSensArgs {
   double *dcost_k, *dcost_b;                       // [nj][B]
   double *x_var, *u_var;                           // [T+1][B][nx], [T][B][nu]
   int32_t B, T;
-  int32_t stiff; // the stiffness columns are computed (some stiffness quantity is asked for)
-  double dt[ASLR_MAX_MODELS];
-  double K[ASLR_MAX_MODELS][ASLR_MAX_NJ], Binv[ASLR_MAX_MODELS][ASLR_MAX_NJ]; // diagonals
+  int32_t stiff; // the stiffness columns are computed (some stiffness quantity is asked for; never on a VSA size)
+  SweepPlant plant;
 };
-bool has_plant_sens_kernel(int nx, int nu);
-int launch_plant_sens(int nx, int nu, const PlantSensArgs &a, hipStream_t st);
+template <int NJ, int DAM> int launch_plant_sens(const PlantSensArgs &a, hipStream_t st);
 
 // Closed-loop policy roll-outs (aslr_policy_rollout, aslr_policy.inc.hpp): the caller's arrays, by value, beside the KArgs and
 // ModelLimits of the handle.  One template serves handles with and without a parameter table (`table`), as the adjoint
-// kernel does, so it has no row in the table of kernel sets either.
+// kernel does, and the rows share its launcher likewise.
 struct PolicyArgs {
   const double *plant_stiffness, *plant_motor_inertia; // [nj][S][B], each nullable
   const double *dx0, *disturbance;                     // [S][B][nx], [S][T][B][nx], each nullable
@@ -243,9 +247,6 @@ struct PolicyArgs {
   int32_t table;    // a parameter table is set: K, 1 / B and the control box of a trajectory are its row
   int32_t diagonal; // a plant array or a table is in use (every model's K and B is diagonal then): diagonals through ModelRegs::set_traj
 };
-int launch_policy_rollout(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st);
-// the nx = 28 sizes of the same roll-out (aslr_policy_rollout_all, aslr_policy_team.inc.hpp): 8-lane teams, the same arguments
-int launch_policy_rollout_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st);
 
 // The same roll-outs with the perturbations drawn inside the kernel (aslr_policy_rollout_noise, aslr_policy_noise.hpp): the
 // input pointers of the PolicyArgs part are NULL, the sigma arrays stand in their place.  The same kernel templates, with this
@@ -259,12 +260,13 @@ struct PolicyNoiseArgs : PolicyArgs {
   NoiseKey key;
   double knom[ASLR_MAX_NJ], bnom[ASLR_MAX_NJ]; // the diagonals of K and B the models share: the nominal while no table is set
 };
-int launch_policy_rollout_noise(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyNoiseArgs &pa, hipStream_t st);
-int launch_policy_rollout_noise_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyNoiseArgs &pa, hipStream_t st);
+// PA: PolicyArgs or PolicyNoiseArgs, two entries of a row.  Two names for two bodies in two headers: a sample per lane (nx = 8,
+// aslr_policy.inc.hpp) and 8-lane teams (nx = 28, aslr_policy_team.inc.hpp); a row takes the one SizeTraits::team_rollout names
+template <int NJ, int DAM, class PA> int launch_policy_rollout(const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st);
+template <int NJ, int DAM, class PA> int launch_policy_rollout_team(const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st);
 
 // The plant phase of one control step of aslr_mpc_run_plant (aslr_mpc_plant.inc.hpp): the caller's arrays, by value, beside
-// the KArgs and ModelLimits of the handle; `table` and `diagonal` as in PolicyArgs.  Like the policy kernel it has no row in
-// the table of kernel sets.
+// the KArgs and ModelLimits of the handle; `table` and `diagonal` as in PolicyArgs.
 struct MpcPlantArgs {
   const double *plant_stiffness, *plant_motor_inertia; // [nj][B], each nullable
   const double *disturbance;                           // [hold][B][nx] of this step, nullable
@@ -275,13 +277,13 @@ struct MpcPlantArgs {
   int32_t first, clamp;                                // first: step 0 of the run
   int32_t table, diagonal;
 };
-int launch_mpc_plant(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
-// the nx = 28 sizes of the same plant phase (aslr_mpc_run_plant_all, aslr_mpc_plant_team.inc.hpp): 8-lane teams, the same arguments
-int launch_mpc_plant_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
+// per-lane (nx = 8, aslr_mpc_plant.inc.hpp) and team (nx = 28, aslr_mpc_plant_team.inc.hpp) forms, as the roll-out's
+template <int NJ, int DAM> int launch_mpc_plant(const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
+template <int NJ, int DAM> int launch_mpc_plant_team(const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st);
 
 // One outer step of aslr_design_descent (aslr_design.hip): what design_step_kernel reads and writes, by value.  The workspace
 // pointers are the handle's; everything else is the caller's (include/aslr_to_amd_design.h).  Like the adjoint kernel it
-// depends on no model size at compile time and has no row in the table of kernel sets.
+// depends on no model size at compile time: one launcher, no entry in the table of kernel sets.
 struct DesignStepArgs {
   double *xs, *us, *gaps, *vxxf, *kff;     // XS / US are copied to or from the best plan; the others are zeroed
   const double *traj_f;                    // TF_COST: the cost of the finalized candidate
@@ -312,6 +314,12 @@ struct KernelSet {
   decltype(&launch_quasi_static<2, 0>) quasi_static;
   decltype(&launch_forward<2, 0>) forward;
   decltype(&launch_backward<2, 0>) backward;
+  decltype(&launch_adjoint<2, 0>) adjoint; // the extension calls: the TP rows share these with the plain rows
+  decltype(&launch_covariance<2, 0>) covariance;
+  decltype(&launch_plant_sens<2, 0>) plant_sens;
+  decltype(&launch_policy_rollout<2, 0, PolicyArgs>) policy_rollout;
+  decltype(&launch_policy_rollout<2, 0, PolicyNoiseArgs>) policy_rollout_noise;
+  decltype(&launch_mpc_plant<2, 0>) mpc_plant;
 };
 
 #ifdef ASLR_BWD_PROFILE

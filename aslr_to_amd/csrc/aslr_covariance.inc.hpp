@@ -202,19 +202,9 @@ __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
 
 #undef ASLR_COV_LOOP
 
-// the four record shapes in use: (8, 2) 2-joint SEA / pendulum, (8, 4) 2-joint VSA, (28, 7) 7-joint SEA, (28, 14) 7-joint VSA
-bool has_covariance_kernel(int nx, int nu) { return (nx == 8 && (nu == 2 || nu == 4)) || (nx == 28 && (nu == 7 || nu == 14)); }
-
-int launch_covariance(int nx, int nu, const CovarianceArgs &a, hipStream_t st) {
-  const auto go = [&](auto kernel, int team) {
-    const int tpw = 64 / team;
-    hipLaunchKernelGGL(kernel, dim3((a.B + tpw - 1) / tpw), dim3(64), 0, st, a);
-  };
-  if (nx == 8 && nu == 2) go(covariance_kernel<8, 2>, 8);
-  else if (nx == 8 && nu == 4) go(covariance_kernel<8, 4>, 8);
-  else if (nx == 28 && nu == 7) go(covariance_kernel<28, 7>, 32);
-  else if (nx == 28 && nu == 14) go(covariance_kernel<28, 14>, 32);
-  else return fail(ASLR_E_INVALID, "aslr_policy_covariance: no covariance kernel for records of (nx = %d, nu = %d)", nx, nu);
+template <int NJ, int DAM>
+int launch_covariance(const CovarianceArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL((covariance_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -147,16 +147,12 @@ __global__ void __launch_bounds__(64) mpc_plant_kernel(KArgs a, ModelLimits lim,
 }
 
 // the nx = 8 sizes, as policy_rollout_kernel
-int launch_mpc_plant(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st) {
+template <int NJ, int DAM>
+int launch_mpc_plant(const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st) {
   const dim3 grid((k.B + 63) / 64), block(64);
-  const auto go = [&](auto NJc, auto DAMc) {
-    with_planar<decltype(NJc)::value>(k, [&](auto P) {
-      hipLaunchKernelGGL((mpc_plant_kernel<decltype(NJc)::value, decltype(DAMc)::value, decltype(P)::value>), grid, block, 0, st, k, lim, pa);
-    });
-  };
-  if (nj == 2 && dam == ASLR_DAM_SEA) go(std::integral_constant<int, 2>{}, std::integral_constant<int, ASLR_DAM_SEA>{});
-  else if (nj == 2 && dam == ASLR_DAM_VSA) go(std::integral_constant<int, 2>{}, std::integral_constant<int, ASLR_DAM_VSA>{});
-  else return fail(ASLR_E_INVALID, "aslr_mpc_run_plant: no plant kernel for nj = %d", nj);
+  with_planar<NJ>(k, [&](auto P) {
+    hipLaunchKernelGGL((mpc_plant_kernel<NJ, DAM, decltype(P)::value>), grid, block, 0, st, k, lim, pa);
+  });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

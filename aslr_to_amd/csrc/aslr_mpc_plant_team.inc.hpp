@@ -214,11 +214,10 @@ __global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits
 }
 
 // the nx = 28 sizes: one block = one wave = 8 teams = 8 trajectories
-int launch_mpc_plant_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st) {
+template <int NJ, int DAM>
+int launch_mpc_plant_team(const KArgs &k, const ModelLimits &lim, const MpcPlantArgs &pa, hipStream_t st) {
   const dim3 grid((k.B + 7) / 8), block(64);
-  if (nj == 7 && dam == ASLR_DAM_SEA) hipLaunchKernelGGL((mpc_plant_team_kernel<7, ASLR_DAM_SEA>), grid, block, 0, st, k, lim, pa);
-  else if (nj == 7 && dam == ASLR_DAM_VSA) hipLaunchKernelGGL((mpc_plant_team_kernel<7, ASLR_DAM_VSA>), grid, block, 0, st, k, lim, pa);
-  else return fail(ASLR_E_INVALID, "aslr_mpc_run_plant_all: no team plant kernel for nj = %d", nj);
+  hipLaunchKernelGGL((mpc_plant_team_kernel<NJ, DAM>), grid, block, 0, st, k, lim, pa);
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -70,9 +70,9 @@ __global__ void __launch_bounds__(64) plant_sens_kernel(PlantSensArgs a) {
   double tk = 0.0, tv = 0.0;
   if (a.traj_params) { tk = a.traj_params[(size_t)jj * B + b]; tv = a.traj_params[(size_t)(NJ + jj) * B + b]; }
   ASLR_UNROLL for (int m = 0; m < ASLR_MAX_MODELS; ++m) {
-    double k = a.K[m][0], v = a.Binv[m][0];
+    double k = a.plant.K[m][0], v = a.plant.Binv[m][0];
     ASLR_UNROLL for (int c = 1; c < NJ; ++c)
-      if (jj == c) { k = a.K[m][c]; v = a.Binv[m][c]; }
+      if (jj == c) { k = a.plant.K[m][c]; v = a.plant.Binv[m][c]; }
     if (a.traj_params) { k = tk; v = tv; }
     rk[m] = k != 0.0 ? 1.0 / k : 0.0;
     bi[m] = v;
@@ -144,9 +144,9 @@ __global__ void __launch_bounds__(64) plant_sens_kernel(PlantSensArgs a) {
     double *bf = tm + (t & 1) * BUF;
     store(s, t);
     const int mi = ((const int32_t __attribute__((address_space(4))) *)(a.node_model))[t];
-    double dt = a.dt[0], rkm = rk[0], bim = bi[0];
+    double dt = a.plant.dt[0], rkm = rk[0], bim = bi[0];
     ASLR_UNROLL for (int m = 1; m < ASLR_MAX_MODELS; ++m)
-      if (mi == m) { dt = a.dt[m]; rkm = rk[m]; bim = bi[m]; }
+      if (mi == m) { dt = a.plant.dt[m]; rkm = rk[m]; bim = bi[m]; }
     ASLR_UNROLL for (int m = 0; m < KP; ++m) {
       const int idx = jr + m * TEAM;
       if (idx < NK) bf[oK + idx] = cur.kp[m];
@@ -227,21 +227,14 @@ __global__ void __launch_bounds__(64) plant_sens_kernel(PlantSensArgs a) {
 
 #undef ASLR_PS_LOOP
 
-// the four record shapes in use: (8, 2) 2-joint SEA / pendulum, (8, 4) 2-joint VSA, (28, 7) 7-joint SEA, (28, 14) 7-joint VSA
-bool has_plant_sens_kernel(int nx, int nu) { return (nx == 8 && (nu == 2 || nu == 4)) || (nx == 28 && (nu == 7 || nu == 14)); }
-
-// a.stiff: the stiffness columns are wanted (never on a VSA shape, whose stiffness is a control)
-int launch_plant_sens(int nx, int nu, const PlantSensArgs &a, hipStream_t st) {
-  const auto go = [&](auto kernel, int team) {
-    const int tpw = 64 / team;
-    hipLaunchKernelGGL(kernel, dim3((a.B + tpw - 1) / tpw), dim3(64), 0, st, a);
+// a.stiff: the stiffness columns are wanted.  The STIFF kernels are built for the SEA sizes alone: a VSA model takes its
+// stiffness from u, and aslr_policy_plant_sensitivity refuses every stiffness argument on one, so a.stiff is 0 there
+template <int NJ, int DAM>
+int launch_plant_sens(const PlantSensArgs &a, hipStream_t st) {
+  const auto go = [&](auto STIFF) {
+    hipLaunchKernelGGL((plant_sens_kernel<4 * NJ, ModelDims<NJ, DAM>::nu, decltype(STIFF)::value>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
   };
-  if (nx == 8 && nu == 2) { if (a.stiff) go(plant_sens_kernel<8, 2, true>, 8); else go(plant_sens_kernel<8, 2, false>, 8); }
-  else if (nx == 8 && nu == 4 && !a.stiff) go(plant_sens_kernel<8, 4, false>, 8);
-  else if (nx == 28 && nu == 7) { if (a.stiff) go(plant_sens_kernel<28, 7, true>, 32); else go(plant_sens_kernel<28, 7, false>, 32); }
-  else if (nx == 28 && nu == 14 && !a.stiff) go(plant_sens_kernel<28, 14, false>, 32);
-  else return fail(ASLR_E_INVALID, "aslr_policy_plant_sensitivity: no kernel for records of (nx = %d, nu = %d)%s", nx, nu,
-                   a.stiff ? " with stiffness columns" : "");
+  if constexpr (DAM == ASLR_DAM_SEA) with_bool(a.stiff != 0, go); else go(std::false_type{});
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

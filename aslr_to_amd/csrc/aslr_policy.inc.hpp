@@ -270,18 +270,13 @@ __global__ void __launch_bounds__(64) policy_rollout_kernel(KArgs a, ModelLimits
 }
 
 // the nx = 8 sizes; the 7-joint team form is policy_rollout_team_kernel (aslr_policy_team.inc.hpp, aslr_policy_rollout_all).
-// One launcher body for both argument types: fn is the entry point a refusal names.
-template <class PA>
-int launch_policy_rollout_as(const char *fn, int nj, int dam, const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st) {
+// One launcher body for both argument types.
+template <int NJ, int DAM, class PA>
+int launch_policy_rollout(const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st) {
   const dim3 grid((k.B + 3) / 4, (pa.S + 15) / 16), block(64);
-  const auto go = [&](auto NJc, auto DAMc) {
-    with_planar<decltype(NJc)::value>(k, [&](auto P) {
-      hipLaunchKernelGGL((policy_rollout_kernel<decltype(NJc)::value, decltype(DAMc)::value, decltype(P)::value, PA>), grid, block, 0, st, k, lim, pa);
-    });
-  };
-  if (nj == 2 && dam == ASLR_DAM_SEA) go(std::integral_constant<int, 2>{}, std::integral_constant<int, ASLR_DAM_SEA>{});
-  else if (nj == 2 && dam == ASLR_DAM_VSA) go(std::integral_constant<int, 2>{}, std::integral_constant<int, ASLR_DAM_VSA>{});
-  else return fail(ASLR_E_INVALID, "%s: no policy roll-out kernel for nj = %d", fn, nj);
+  with_planar<NJ>(k, [&](auto P) {
+    hipLaunchKernelGGL((policy_rollout_kernel<NJ, DAM, decltype(P)::value, PA>), grid, block, 0, st, k, lim, pa);
+  });
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -3,7 +3,6 @@
 #include "aslr_policy_team.inc.hpp"
 
 namespace aslr {
-int launch_policy_rollout_noise_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyNoiseArgs &pa, hipStream_t st) {
-  return launch_policy_rollout_team_as("aslr_policy_rollout_noise", nj, dam, k, lim, pa, st);
-}
+template decltype(launch_policy_rollout_team<7, ASLR_DAM_SEA, PolicyNoiseArgs>) launch_policy_rollout_team<7, ASLR_DAM_SEA, PolicyNoiseArgs>;
+template decltype(launch_policy_rollout_team<7, ASLR_DAM_VSA, PolicyNoiseArgs>) launch_policy_rollout_team<7, ASLR_DAM_VSA, PolicyNoiseArgs>;
 } // namespace aslr

@@ -2,7 +2,6 @@
 #include "aslr_policy_team.inc.hpp"
 
 namespace aslr {
-int launch_policy_rollout_team(int nj, int dam, const KArgs &k, const ModelLimits &lim, const PolicyArgs &pa, hipStream_t st) {
-  return launch_policy_rollout_team_as("aslr_policy_rollout_all", nj, dam, k, lim, pa, st);
-}
+template decltype(launch_policy_rollout_team<7, ASLR_DAM_SEA, PolicyArgs>) launch_policy_rollout_team<7, ASLR_DAM_SEA, PolicyArgs>;
+template decltype(launch_policy_rollout_team<7, ASLR_DAM_VSA, PolicyArgs>) launch_policy_rollout_team<7, ASLR_DAM_VSA, PolicyArgs>;
 } // namespace aslr

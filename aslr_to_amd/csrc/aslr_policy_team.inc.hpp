@@ -238,13 +238,11 @@ __global__ void __launch_bounds__(128) policy_rollout_team_kernel(KArgs a, Model
 }
 
 // the nx = 28 sizes: grid (trajectories, groups of 16 samples), one block = 2 waves of 8 teams.  One launcher body for both
-// argument types: fn is the entry point a refusal names.
-template <class PA>
-int launch_policy_rollout_team_as(const char *fn, int nj, int dam, const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st) {
+// argument types.
+template <int NJ, int DAM, class PA>
+int launch_policy_rollout_team(const KArgs &k, const ModelLimits &lim, const PA &pa, hipStream_t st) {
   const dim3 grid(k.B, (pa.S + 15) / 16), block(128);
-  if (nj == 7 && dam == ASLR_DAM_SEA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_SEA, PA>), grid, block, 0, st, k, lim, pa);
-  else if (nj == 7 && dam == ASLR_DAM_VSA) hipLaunchKernelGGL((policy_rollout_team_kernel<7, ASLR_DAM_VSA, PA>), grid, block, 0, st, k, lim, pa);
-  else return fail(ASLR_E_INVALID, "%s: no team roll-out kernel for nj = %d", fn, nj);
+  hipLaunchKernelGGL((policy_rollout_team_kernel<NJ, DAM, PA>), grid, block, 0, st, k, lim, pa);
   HIP_TRY(hipGetLastError());
   return ASLR_OK;
 }

@@ -7,8 +7,9 @@ launch (the bounds cases of aslr_design_descent after its two small read-backs),
 here is ever written through.
 
 Refusals no test reaches, because create refuses first or only a failing device call produces them:
-  "... no roll-out kernel for this %d-joint handle", "... no plant kernel for this %d-joint handle", "... no kernel for records
-  of (nx, nu)" and "... no per-trajectory-parameter kernels for (nj, dam)": aslr_problem_create admits 2 and 7 joints only;
+  "... no per-trajectory-parameter kernels for (nj, dam)": aslr_problem_create admits only the sizes that have a row in the
+  table of kernel sets, and every row has its TP row (the extension calls take their kernels from the handle's row and
+  refuse no size of their own);
   "... motor inertia entry B[j] of model i is 0" and "... motor inertia entry [b][j] of the initial design is not positive":
   create refuses a singular B, aslr_set_trajectory_params a non-positive one;
   "... %d of %d problems finished within the iteration bound" and "... putting the handle's x0 / frame_ref back failed": behind
