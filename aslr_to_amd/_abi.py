@@ -113,6 +113,16 @@ class Design(C.Structure):
                 ("grad", C.c_void_p)]
 
 
+class Identify(C.Structure):
+    """aslr_identify_t (include/aslr_to_amd_identify.h): a plant identification (aslr_plant_identify); device pointers, rows
+    [np][B]."""
+    _fields_ = [("n_steps", _i), ("fit_stiffness", _i), ("fit_motor_inertia", _i), ("_pad0", _i), ("mu0", _d), ("mu_min", _d),
+                ("mu_max", _d), ("grow", _d), ("shrink", _d), ("max_rel", _d), ("min_curv", _d), ("weights", C.c_void_p),
+                ("lo", C.c_void_p), ("hi", C.c_void_p), ("theta", C.c_void_p), ("sse", C.c_void_p), ("grad", C.c_void_p),
+                ("information", C.c_void_p), ("mu", C.c_void_p), ("identifiable", C.c_void_p), ("n_accepted", C.c_void_p),
+                ("hist_theta", C.c_void_p), ("hist_sse", C.c_void_p), ("hist_decision", C.c_void_p), ("work", C.c_void_p)]
+
+
 class Region(C.Structure):
     _fields_ = [("offset", C.c_int64), ("bytes", C.c_int64)]
 
@@ -213,6 +223,9 @@ MPC_PLANT_ALL_SYMBOLS = ["aslr_mpc_run_plant_all"]
 # what include/aslr_to_amd_policy_noise.h declares: a tenth extension header, in a list of its own for the same reason
 POLICY_NOISE_SYMBOLS = ["aslr_policy_rollout_noise"]
 
+# what include/aslr_to_amd_identify.h declares: an eleventh extension header, in a list of its own for the same reason
+IDENTIFY_SYMBOLS = ["aslr_plant_identify"]
+
 
 def load_library():
     """Load the HIP C-ABI library; raise loudly when it is absent (no fallback exists)."""
@@ -309,6 +322,8 @@ def load_library():
     lib.aslr_policy_plant_sensitivity.argtypes = [vp] * 12
     lib.aslr_design_descent.restype = C.c_int
     lib.aslr_design_descent.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Design), vp]
+    lib.aslr_plant_identify.restype = C.c_int
+    lib.aslr_plant_identify.argtypes = [vp, C.POINTER(Identify), vp]
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

@@ -224,6 +224,37 @@ class ShootingProblem(object):
             e.set_candidate(xs, us)
         return e.cost_sensitivity()
 
+    def identify_plant(self, xs, us, n_steps=10, weights=None, stiffness_bounds=None, motor_inertia_bounds=None, mu0=1e-3,
+                       grow=10.0, shrink=0.1, max_rel=0.5, min_curv=1e-12, keep_history=False):
+        """Fit every trajectory's own spring stiffness and motor inertia to a recorded run (Engine.plant_identify;
+        aslr_plant_identify): xs [B, T+1, nx] the recorded states, us [B, T, nu] the applied controls (put into the engine
+        as cost_sensitivity(xs, us) puts them).  n_steps Levenberg-Marquardt steps on the weighted one-step prediction
+        error sum_t |xs_{t+1} - f(xs_t, us_t; K, B)|^2_w, every trajectory on its own, starting from the parameters the
+        problem holds.  stiffness_bounds / motor_inertia_bounds: (lo, hi), each [B, nj], [nj] or a scalar; a field whose bounds
+        are None is not fitted (no stiffness_bounds for a VSA model).  -> engine.IdentifyResult; the problem's parameter
+        table is left on the fit.  This shard's trajectories only."""
+        e = self.engine
+        lo, hi = self.rows
+
+        def shard(v, width):  # whole-batch rows -> this rank's
+            return v[lo:hi] if v is not None and np.ndim(v) == width and len(v) == self.batch_total else v
+
+        def shard2(bounds):
+            if bounds is None or len(bounds) != 2:
+                return bounds
+            return tuple(shard(v, 2) for v in bounds)
+
+        e.set_candidate(xs, us)
+        r = e.plant_identify(n_steps, shard(weights, 2), shard2(stiffness_bounds), shard2(motor_inertia_bounds), mu0=mu0, grow=grow,
+                             shrink=shrink, max_rel=max_rel, min_curv=min_curv, keep_history=keep_history)
+        # the problem's own record of the table follows the engine's (a later engine of this problem starts from it)
+        low = self._lowered
+        old = low.traj_params or {}
+        low.traj_params = lower_traj_params(low.desc, low.nj, low.nu, low.nu_user, low.dam,
+                                            None if r.stiffness is None else r.stiffness.cpu().numpy(),
+                                            r.motor_inertia.cpu().numpy(), old.get("u_lb"), old.get("u_ub"))
+        return r
+
     def policy_rollout(self, xs, us, K, n_samples, plant_stiffness=None, plant_motor_inertia=None, dx0=None,
                        disturbance=None, clamp=False, keep_trajectories=False):
         """Closed-loop roll-outs of the policy u_t = us_t - K_t (x_t - xs_t) on n_samples perturbed plants per trajectory

@@ -18,6 +18,7 @@
 #include "../../include/aslr_to_amd_policy_noise.h"
 #include "../../include/aslr_to_amd_mpc_plant_all.h"
 #include "../../include/aslr_to_amd_design.h"
+#include "../../include/aslr_to_amd_identify.h"
 
 using namespace aslr;
 
@@ -643,9 +644,10 @@ template <int NJ, int DAM, bool TP = false>
 constexpr KernelSet kernel_set() {
   constexpr KernelSet ks = {NJ, DAM, TP, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM, TP>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
                             launch_quasi_static<NJ, DAM, TP>, launch_forward<NJ, DAM, TP>, launch_backward<NJ, DAM, TP>, launch_adjoint<NJ, DAM>, launch_covariance<NJ, DAM>,
-                            launch_plant_sens<NJ, DAM>, policy_launcher<NJ, DAM, PolicyArgs>(), policy_launcher<NJ, DAM, PolicyNoiseArgs>(), mpc_plant_launcher<NJ, DAM>()};
+                            launch_plant_sens<NJ, DAM>, policy_launcher<NJ, DAM, PolicyArgs>(), policy_launcher<NJ, DAM, PolicyNoiseArgs>(), mpc_plant_launcher<NJ, DAM>(),
+                            launch_identify_normal<NJ, DAM>, launch_identify_step<NJ, DAM>};
   static_assert(ks.calc && ks.dam_eval && ks.dam_residuals && ks.frame_placement && ks.quasi_static && ks.forward && ks.backward && ks.adjoint && ks.covariance &&
-                ks.plant_sens && ks.policy_rollout && ks.policy_rollout_noise && ks.mpc_plant, "a row of kKernelSets lacks a launcher");
+                ks.plant_sens && ks.policy_rollout && ks.policy_rollout_noise && ks.mpc_plant && ks.identify_normal && ks.identify_step, "a row of kKernelSets lacks a launcher");
   return ks;
 }
 constexpr KernelSet kKernelSets[] = {
@@ -1546,6 +1548,84 @@ int aslr_mpc_run_plant_all(aslr_problem_t *p, const aslr_solver_params_t *sp, co
 // never polls, aslr_finalize, the two sweeps of aslr_cost_sensitivity and design_step_kernel (aslr_design.hip).
 namespace {
 
+// What aslr_design_descent and aslr_plant_identify share around their loops.  Both start from the handle's parameter table (or
+// the models' constants, lowered as aslr_set_trajectory_params lowers them with no field given), check device-resident bounds
+// against it before anything is enqueued, put the table in place, run steps that rewrite it on the device and let the host
+// copies follow it.  fn: the entry point a refusal names; what: its noun for theta ("design", "parameters").
+struct TableRun {
+  const char *fn, *what;
+  aslr_problem *p;
+  hipStream_t st;
+  std::vector<double> rows, bdiag; // the table [2 nj + 2 nu][B] and diag B [nj][B] the run starts from
+  bool had_table = false;
+  const KernelSet *tp_set = nullptr;
+
+  int start() {
+    const int B = p->desc.B;
+    had_table = p->ks->traj_params;
+    tp_set = find_kernel_set(p->nj, p->dam, true);
+    if (!tp_set) return fail(ASLR_E_INVALID, "%s: no per-trajectory-parameter kernels for (nj=%d, dam=%d)", fn, p->nj, p->dam);
+    if (had_table) { rows = p->tp_host; bdiag = p->tp_b_host; return ASLR_OK; }
+    const aslr_traj_params_t none{nullptr, nullptr, nullptr, nullptr};
+    if (int rc = build_param_rows(fn, p, &none, B, &rows)) return rc;
+    bdiag = motor_inertia_rows(p, &none, B);
+    return ASLR_OK;
+  }
+  // the stiffness rows (check_k) and the motor inertias (check_b) the run starts from are positive
+  int positive(bool check_k, bool check_b) const {
+    const int B = p->desc.B, nj = p->nj;
+    for (int j = 0; j < nj; ++j)
+      for (int b = 0; b < B; ++b) {
+        if (check_k && !(rows[(size_t)j * B + b] > 0.0)) return fail(ASLR_E_INVALID, "%s: stiffness entry [%d][%d] of the initial %s is not positive", fn, b, j, what);
+        if (check_b && !(bdiag[(size_t)j * B + b] > 0.0)) return fail(ASLR_E_INVALID, "%s: motor inertia entry [%d][%d] of the initial %s is not positive", fn, b, j, what);
+      }
+    return ASLR_OK;
+  }
+  // entries [r0, r1) of the device arrays lo, hi (laid out like theta0, [.][B]) read back -- the one wait before anything
+  // else is enqueued -- and checked: 0 < lo <= theta0 <= hi, finite
+  int bounds(const double *lo_dev, const double *hi_dev, const std::vector<double> &theta0, size_t r0, size_t r1) const {
+    const int B = p->desc.B;
+    std::vector<double> lo(theta0.size()), hi(theta0.size());
+    hipError_t e = hipMemcpyAsync(lo.data() + r0, lo_dev + r0, sizeof(double) * (r1 - r0), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hi.data() + r0, hi_dev + r0, sizeof(double) * (r1 - r0), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(ASLR_E_HIP, "%s: reading the bounds back -> %s", fn, hipGetErrorString(e));
+    for (size_t i = r0; i < r1; ++i) {
+      const int r = (int)(i / B), b = (int)(i % B);
+      if (!(lo[i] > 0.0 && lo[i] <= hi[i] && std::isfinite(hi[i]))) return fail(ASLR_E_INVALID, "%s: bounds [%d][%d] are (%g, %g): 0 < lo <= hi must hold, finite", fn, b, r, lo[i], hi[i]);
+      if (!(lo[i] <= theta0[i] && theta0[i] <= hi[i])) return fail(ASLR_E_INVALID, "%s: entry [%d][%d] of the initial %s, %g, lies outside its bounds [%g, %g]", fn, b, r, what, theta0[i], lo[i], hi[i]);
+    }
+    return ASLR_OK;
+  }
+  int copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) const {
+    const hipError_t ce = hipMemcpyAsync(dst, src, bytes, kind, st);
+    return ce == hipSuccess ? ASLR_OK : fail(ASLR_E_HIP, "%s: hipMemcpyAsync -> %s", fn, hipGetErrorString(ce));
+  }
+  // the table in place (when the handle had none) and the handle on the kernels that read it.  Staged from `rows`, which
+  // lives as long as this object: finish() synchronises before the caller lets go of it
+  int install() {
+    if (!had_table) {
+      if (int rc = copy(region(p, ASLR_R_TRAJ_PARAMS), rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice)) return rc;
+      p->tp_host = rows; p->tp_b_host = bdiag;
+      p->ks = tp_set;
+    }
+    p->const_written = false;
+    return ASLR_OK;
+  }
+  // rc: what the enqueued steps returned.  The table holds the accepted theta now: the host copies follow it (bdiag_dev: its
+  // motor inertias [nj][B] on the device, or nullptr: they did not move), then the call's one wait after the bounds check
+  // (also after a failed launch)
+  int finish(int rc, const double *bdiag_dev) {
+    if (!rc) rc = copy(p->tp_host.data(), region(p, ASLR_R_TRAJ_PARAMS), sizeof(double) * p->tp_host.size(), hipMemcpyDeviceToHost);
+    if (!rc && bdiag_dev) rc = copy(p->tp_b_host.data(), bdiag_dev, sizeof(double) * p->tp_b_host.size(), hipMemcpyDeviceToHost);
+    const hipError_t e = hipStreamSynchronize(st);
+    p->const_written = false; // the record chunks in place belong to the last candidate
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(ASLR_E_HIP, "%s: hipStreamSynchronize -> %s", fn, hipGetErrorString(e));
+    return ASLR_OK;
+  }
+};
+
 // design_step_kernel's argument block for step s of the run d describes on handle p
 DesignStepArgs design_step_args(aslr_problem *p, const aslr_design_t *d, int s, bool last) {
   const size_t B = p->desc.B, rows = 2 * (size_t)p->nj;
@@ -1593,53 +1673,21 @@ int aslr_design_descent(aslr_problem_t *p, const aslr_solver_params_t *sp, const
   if (p->k.iter_log) return fail(ASLR_E_INVALID, "%s: an iteration log is set (every step would overwrite it): clear it with aslr_set_iteration_log(p, NULL, 0)", fn);
   if (int rc = solver_unsupported(fn, p, sp->solver)) return rc;
   const int B = p->desc.B, nj = p->nj;
-  const bool sea = p->dam == ASLR_DAM_SEA, had_table = p->ks->traj_params;
+  const bool sea = p->dam == ASLR_DAM_SEA;
   if (int rc = model_refusals(fn, p, false, false)) return rc;
-  const KernelSet *tp_set = find_kernel_set(nj, p->dam, true);
-  if (!tp_set) return fail(ASLR_E_INVALID, "%s: no per-trajectory-parameter kernels for (nj=%d, dam=%d)", fn, nj, p->dam);
-  // ---- the initial design: the handle's table, or the models' constants lowered as aslr_set_trajectory_params lowers them ----
-  std::vector<double> rows, bdiag;
-  if (had_table) { rows = p->tp_host; bdiag = p->tp_b_host; }
-  else {
-    const aslr_traj_params_t none{nullptr, nullptr, nullptr, nullptr};
-    if (int rc = build_param_rows(fn, p, &none, B, &rows)) return rc;
-    bdiag = motor_inertia_rows(p, &none, B);
-  }
+  // ---- the initial design, and the bounds of the optimised fields checked against it ----
+  TableRun run{fn, "design", p, static_cast<hipStream_t>(stream)};
+  if (int rc = run.start()) return rc;
   const size_t half = (size_t)nj * B;
   std::vector<double> theta0(2 * half);
-  for (size_t i = 0; i < half; ++i) { theta0[i] = sea ? rows[i] : 0.0; theta0[half + i] = bdiag[i]; }
-  for (int j = 0; j < nj; ++j)
-    for (int b = 0; b < B; ++b) {
-      if (sea && !(theta0[(size_t)j * B + b] > 0.0)) return fail(ASLR_E_INVALID, "%s: stiffness entry [%d][%d] of the initial design is not positive", fn, b, j);
-      if (!(theta0[half + (size_t)j * B + b] > 0.0)) return fail(ASLR_E_INVALID, "%s: motor inertia entry [%d][%d] of the initial design is not positive", fn, b, j);
-    }
-  // ---- the bounds of the optimised fields, read back to be checked (before anything else is enqueued) ----
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  std::vector<double> lo(2 * half), hi(2 * half);
-  const size_t r0 = opt_k ? 0 : half, r1 = opt_b ? 2 * half : half;
-  HIP_TRY(hipMemcpyAsync(lo.data() + r0, d->lo + r0, sizeof(double) * (r1 - r0), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(hi.data() + r0, d->hi + r0, sizeof(double) * (r1 - r0), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  for (size_t i = r0; i < r1; ++i) {
-    const int r = (int)(i / B), b = (int)(i % B);
-    if (!(lo[i] > 0.0 && lo[i] <= hi[i] && std::isfinite(hi[i]))) return fail(ASLR_E_INVALID, "%s: bounds [%d][%d] are (%g, %g): 0 < lo <= hi must hold, finite", fn, b, r, lo[i], hi[i]);
-    if (!(lo[i] <= theta0[i] && theta0[i] <= hi[i])) return fail(ASLR_E_INVALID, "%s: entry [%d][%d] of the initial design, %g, lies outside its bounds [%g, %g]", fn, b, r, theta0[i], lo[i], hi[i]);
-  }
-  // ---- in place: the table (when the handle had none), theta_0.  The copies are staged from `rows` and `theta0`, which
-  // live until this function returns, and every return below follows a synchronisation of the stream ----
-  const auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) -> int { // (HIP_TRY would name the lambda)
-    const hipError_t ce = hipMemcpyAsync(dst, src, bytes, kind, st);
-    return ce == hipSuccess ? ASLR_OK : fail(ASLR_E_HIP, "%s: hipMemcpyAsync -> %s", fn, hipGetErrorString(ce));
-  };
+  for (size_t i = 0; i < half; ++i) { theta0[i] = sea ? run.rows[i] : 0.0; theta0[half + i] = run.bdiag[i]; }
+  if (int rc = run.positive(sea, true)) return rc;
+  if (int rc = run.bounds(d->lo, d->hi, theta0, opt_k ? 0 : half, opt_b ? 2 * half : half)) return rc;
+  // ---- in place: the table (when the handle had none), theta_0 (staged from `theta0`, which outlives run.finish) ----
+  hipStream_t st = run.st;
   const auto enqueue = [&]() -> int {
-    if (!had_table)
-      if (int rc = copy(region(p, ASLR_R_TRAJ_PARAMS), rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice)) return rc;
-    if (int rc = copy(d->theta_best, theta0.data(), sizeof(double) * theta0.size(), hipMemcpyHostToDevice)) return rc;
-    if (!had_table) {
-      p->tp_host = rows; p->tp_b_host = bdiag;
-      p->ks = tp_set;
-    }
-    p->const_written = false;
+    if (int rc = run.install()) return rc;
+    if (int rc = run.copy(d->theta_best, theta0.data(), sizeof(double) * theta0.size(), hipMemcpyHostToDevice)) return rc;
     aslr_solver_params_t sps = *sp;
     for (int s = 0; s < d->n_steps; ++s) {
       if (s > 0) sps.is_feasible = 0; // the plan was made under other parameters
@@ -1649,16 +1697,9 @@ int aslr_design_descent(aslr_problem_t *p, const aslr_solver_params_t *sp, const
       if (int rc = design_gradient(p, d, st)) return rc;
       if (int rc = launch_design_step(design_step_args(p, d, s, s == d->n_steps - 1), st)) return rc;
     }
-    // the table holds theta_acc now: the host copies follow it
-    if (int rc = copy(p->tp_host.data(), region(p, ASLR_R_TRAJ_PARAMS), sizeof(double) * p->tp_host.size(), hipMemcpyDeviceToHost)) return rc;
-    return copy(p->tp_b_host.data(), d->theta_best + half, sizeof(double) * half, hipMemcpyDeviceToHost);
+    return ASLR_OK;
   };
-  const int rc = enqueue();
-  const hipError_t e = hipStreamSynchronize(st); // the call's one wait after the bounds check (also after a failed launch)
-  p->const_written = false; // the record chunks in place belong to the last candidate
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(ASLR_E_HIP, "%s: hipStreamSynchronize -> %s", fn, hipGetErrorString(e));
-  return ASLR_OK;
+  return run.finish(enqueue(), d->theta_best + half);
 }
 
 // One launch of design_step_kernel on the handle's state, for the kernel-level test (tests/test_gpu_design.py): no header
@@ -1669,6 +1710,118 @@ int aslr_debug_design_step(aslr_problem_t *p, const aslr_design_t *d, int32_t s,
   DesignStepArgs a = design_step_args(p, &one, 0, last != 0);
   a.s = s;
   return launch_design_step(a, static_cast<hipStream_t>(stream));
+}
+
+// aslr_plant_identify (include/aslr_to_amd_identify.h): per outer step the calcDiff sweep at the
+// recorded (XS, US) under the candidate in the table, identify_normal_kernel and identify_step_kernel (aslr_identify.inc.hpp).
+namespace {
+
+int identify_np(const aslr_problem *p, const aslr_identify_t *d) { return ((d->fit_stiffness != 0) + (d->fit_motor_inertia != 0)) * p->nj; }
+
+// the normal equations of what XS / US / XNEXT / DERIV hold, into the work buffer of d; sweep: after the calcDiff sweep at
+// (XS, US) under the candidate in the table
+int identify_normal(aslr_problem *p, const aslr_identify_t *d, bool sweep, hipStream_t st) {
+  const size_t B = p->desc.B;
+  const int np = identify_np(p, d);
+  if (sweep) {
+    // the model-only record chunks depend on the table, which the step kernel has just rewritten
+    p->const_written = false;
+    if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
+  }
+  const KArgs &k = p->k;
+  IdentifyNormalArgs a;
+  memset(&a, 0, sizeof a);
+  a.deriv = k.deriv; a.xs = k.xs; a.xnext = k.xnext; a.node_model = k.node_model;
+  a.weights = d->weights;
+  a.sse = d->work + (size_t)np * B; a.grad = a.sse + B; a.information = a.grad + (size_t)np * B;
+  a.B = k.B; a.T = k.T;
+  a.stiff = d->fit_stiffness != 0; a.np_out = np;
+  for (int i = 0; i < p->desc.nmodels; ++i) a.dt[i] = p->desc.models[i].dt;
+  return p->ks->identify_normal(a, st);
+}
+
+// identify_step_kernel's argument block for step s of the run d describes on handle p
+IdentifyStepArgs identify_step_args(aslr_problem *p, const aslr_identify_t *d, int s, bool last) {
+  const size_t B = p->desc.B;
+  const int np = identify_np(p, d);
+  IdentifyStepArgs a;
+  memset(&a, 0, sizeof a);
+  a.traj_params = reinterpret_cast<double *>(region(p, ASLR_R_TRAJ_PARAMS));
+  a.lo = d->lo; a.hi = d->hi;
+  a.theta_try = d->work; a.sse_try = d->work + (size_t)np * B; a.g_try = a.sse_try + B; a.h_try = a.g_try + (size_t)np * B;
+  a.theta = d->theta; a.sse = d->sse; a.grad = d->grad; a.information = d->information; a.mu = d->mu;
+  a.identifiable = d->identifiable; a.n_accepted = d->n_accepted;
+  a.hist_theta = d->hist_theta ? d->hist_theta + (size_t)s * np * B : nullptr;
+  a.hist_sse = d->hist_sse ? d->hist_sse + (size_t)s * B : nullptr;
+  a.hist_decision = d->hist_decision ? d->hist_decision + (size_t)s * B : nullptr;
+  a.B = p->k.B; a.nj = p->nj; a.np = np;
+  a.row0 = d->fit_stiffness ? 0 : p->nj;
+  a.s = s; a.last = last;
+  a.mu0 = d->mu0; a.mu_min = d->mu_min; a.mu_max = d->mu_max; a.grow = d->grow; a.shrink = d->shrink;
+  a.max_rel = d->max_rel; a.min_curv = d->min_curv;
+  return a;
+}
+
+} // namespace
+
+int aslr_plant_identify(aslr_problem_t *p, const aslr_identify_t *d, void *stream) {
+  const char *fn = "aslr_plant_identify";
+  if (!p || !d) return fail(ASLR_E_INVALID, "%s: NULL argument: %s", fn, !p ? "the problem handle p" : "d");
+  if (d->n_steps < 1) return fail(ASLR_E_INVALID, "%s: n_steps = %d must be >= 1", fn, d->n_steps);
+  const bool fit_k = d->fit_stiffness != 0, fit_b = d->fit_motor_inertia != 0;
+  if (!fit_k && !fit_b) return fail(ASLR_E_INVALID, "%s: neither fit_stiffness nor fit_motor_inertia is set: nothing to fit", fn);
+  if (fit_k && p->dam != ASLR_DAM_SEA) return fail(ASLR_E_INVALID, "%s: fit_stiffness on a VSA model, which takes its stiffness from u", fn);
+  if (int rc = model_refusals(fn, p, false, false)) return rc;
+  if (!(d->mu_min > 0.0 && d->mu_min <= d->mu_max && std::isfinite(d->mu_max)))
+    return fail(ASLR_E_INVALID, "%s: mu_min = %g, mu_max = %g: 0 < mu_min <= mu_max must hold, finite", fn, d->mu_min, d->mu_max);
+  if (!(d->mu0 >= d->mu_min && d->mu0 <= d->mu_max)) return fail(ASLR_E_INVALID, "%s: mu0 = %g must lie in [mu_min, mu_max] = [%g, %g]", fn, d->mu0, d->mu_min, d->mu_max);
+  if (!(d->grow > 1.0) || !std::isfinite(d->grow)) return fail(ASLR_E_INVALID, "%s: grow = %g must be finite and > 1", fn, d->grow);
+  if (!(d->shrink > 0.0 && d->shrink < 1.0)) return fail(ASLR_E_INVALID, "%s: shrink = %g must lie in (0, 1)", fn, d->shrink);
+  if (!(d->max_rel > 0.0 && d->max_rel < 1.0)) return fail(ASLR_E_INVALID, "%s: max_rel = %g must lie in (0, 1)", fn, d->max_rel);
+  if (!(d->min_curv >= 0.0 && d->min_curv < 1.0)) return fail(ASLR_E_INVALID, "%s: min_curv = %g must lie in [0, 1)", fn, d->min_curv);
+  if (!d->lo || !d->hi || !d->theta || !d->sse || !d->grad || !d->information || !d->mu || !d->identifiable || !d->n_accepted || !d->work)
+    return fail(ASLR_E_INVALID, "%s: lo, hi, theta, sse, grad, information, mu, identifiable, n_accepted and work must be given", fn);
+  const int B = p->desc.B, nj = p->nj, np = identify_np(p, d);
+  // ---- the initial parameters (the fitted fields of them must be positive), and the bounds checked against them ----
+  TableRun run{fn, "parameters", p, static_cast<hipStream_t>(stream)};
+  if (int rc = run.start()) return rc;
+  const size_t half = (size_t)nj * B, n = (size_t)np * B, b0 = fit_k ? half : 0; // b0: where the motor-inertia entries start
+  std::vector<double> theta0(n);
+  for (size_t i = 0; i < half; ++i) {
+    if (fit_k) theta0[i] = run.rows[i];
+    if (fit_b) theta0[b0 + i] = run.bdiag[i];
+  }
+  if (int rc = run.positive(fit_k, fit_b)) return rc;
+  if (int rc = run.bounds(d->lo, d->hi, theta0, 0, n)) return rc;
+  // ---- in place: the table (when the handle had none), theta_0 as the accepted set and as the first candidate (staged from
+  // `theta0`, which outlives run.finish) ----
+  const auto enqueue = [&]() -> int {
+    if (int rc = run.install()) return rc;
+    if (int rc = run.copy(d->theta, theta0.data(), sizeof(double) * n, hipMemcpyHostToDevice)) return rc;
+    if (int rc = run.copy(d->work, theta0.data(), sizeof(double) * n, hipMemcpyHostToDevice)) return rc;
+    for (int s = 0; s < d->n_steps; ++s) {
+      if (int rc = identify_normal(p, d, true, run.st)) return rc;
+      if (int rc = p->ks->identify_step(identify_step_args(p, d, s, s == d->n_steps - 1), run.st)) return rc;
+    }
+    return ASLR_OK;
+  };
+  return run.finish(enqueue(), fit_b ? d->theta + b0 : nullptr);
+}
+
+// One launch of identify_step_kernel on the caller's buffers, for the kernel-level test (tests/test_gpu_identify.py): no
+// header declares it and nothing is checked beyond the pointers -- the caller has put every buffer of d in place (the
+// history pointers are taken as those of THIS step).
+int aslr_debug_identify_step(aslr_problem_t *p, const aslr_identify_t *d, int32_t s, int32_t last, void *stream) {
+  if (!p || !d) return fail(ASLR_E_INVALID, "aslr_debug_identify_step: NULL argument");
+  IdentifyStepArgs a = identify_step_args(p, d, 0, last != 0);
+  a.s = s;
+  return p->ks->identify_step(a, static_cast<hipStream_t>(stream));
+}
+
+// ... and one launch of identify_normal_kernel on what the handle holds (no sweep before it), into d->work
+int aslr_debug_identify_normal(aslr_problem_t *p, const aslr_identify_t *d, void *stream) {
+  if (!p || !d || !d->work) return fail(ASLR_E_INVALID, "aslr_debug_identify_normal: NULL argument");
+  return identify_normal(p, d, false, static_cast<hipStream_t>(stream));
 }
 
 int aslr_solve_pool(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_pool_t *pool, int32_t refill_every,

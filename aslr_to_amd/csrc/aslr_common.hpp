@@ -302,6 +302,38 @@ struct DesignStepArgs {
 };
 int launch_design_step(const DesignStepArgs &a, hipStream_t st);
 
+// aslr_plant_identify (aslr_identify.inc.hpp; include/aslr_to_amd_identify.h): what identify_normal_kernel reads and writes, by
+// value.  It reads no K and no B (the columns of Jz are the parameter derivatives times the parameter): dt alone, per model.
+struct IdentifyNormalArgs {
+  const double *deriv, *xs, *xnext;
+  const int32_t *node_model;
+  const double *weights;            // [nx][B], nullable (ones)
+  double *sse, *grad, *information; // [B], [np][B], [np (np+1)/2][B] of the candidate
+  int32_t B, T;
+  int32_t stiff;  // the stiffness columns are computed (never on a VSA size)
+  int32_t np_out; // entries stored: all np of the kernel, or nj where the stiffness alone is fitted (the K block)
+  double dt[ASLR_MAX_MODELS];
+};
+template <int NJ, int DAM> int launch_identify_normal(const IdentifyNormalArgs &a, hipStream_t st);
+
+// ... and identify_step_kernel: the decision on the candidate, the accepted set, the damped solve, the next candidate into
+// the trajectory's column of TRAJ_PARAMS.  Everything but the table is the caller's.
+struct IdentifyStepArgs {
+  double *traj_params;                              // region TRAJ_PARAMS
+  const double *lo, *hi;                            // [np][B]
+  double *theta_try;                                // [np][B]: the candidate evaluated; takes the next one
+  const double *sse_try, *g_try, *h_try;            // [B], [np][B], [nh][B]: what the normal kernel made of it
+  double *theta, *sse, *grad, *information, *mu;    // the accepted set and the damping (mu < 0: frozen)
+  int32_t *identifiable, *n_accepted;               // [np][B], [B]
+  double *hist_theta, *hist_sse;                    // [np][B], [B] of this step, nullable
+  int32_t *hist_decision;                           // [B] of this step, nullable
+  int32_t B, nj, np;
+  int32_t row0;                                     // table row of parameter 0: 0 (stiffness fitted) or nj (motor inertia alone)
+  int32_t s, last;
+  double mu0, mu_min, mu_max, grow, shrink, max_rel, min_curv;
+};
+template <int NJ, int DAM> int launch_identify_step(const IdentifyStepArgs &a, hipStream_t st);
+
 // the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
 struct KernelSet {
   int nj, dam;
@@ -320,6 +352,8 @@ struct KernelSet {
   decltype(&launch_policy_rollout<2, 0, PolicyArgs>) policy_rollout;
   decltype(&launch_policy_rollout<2, 0, PolicyNoiseArgs>) policy_rollout_noise;
   decltype(&launch_mpc_plant<2, 0>) mpc_plant;
+  decltype(&launch_identify_normal<2, 0>) identify_normal;
+  decltype(&launch_identify_step<2, 0>) identify_step;
 };
 
 #ifdef ASLR_BWD_PROFILE

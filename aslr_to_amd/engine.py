@@ -81,6 +81,18 @@ class DesignResult(object):
         self.__dict__.update(fields)
 
 
+class IdentifyResult(object):
+    """What Engine.plant_identify returns: batch-major device tensors -- stiffness [B, nj] (None for a VSA model) and
+    motor_inertia [B, nj] (the fit where the field was fitted, the table's value otherwise), theta [B, np] (the fitted entries,
+    stiffness first), sse [B], n_accepted [B] (int32), grad [B, np], information [B, np, np] (the Gauss-Newton matrix H in
+    z = log theta, unpacked and symmetric), identifiable [B, np] (bool), mu [B] and, when the history is kept, theta_history
+    [B, n_steps, np], sse_history [B, n_steps], decision_history [B, n_steps] (int32: 1 accepted, 0 rejected, -1 not
+    evaluable)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
 class Engine(object):
     """ShootingProblem shard resident in HBM.  Region layouts: include/aslr_to_amd.h."""
 
@@ -772,6 +784,93 @@ class Engine(object):
                         motor_inertia_history=th[:, nj:].permute(2, 0, 1))
         return DesignResult(stiffness=None if vsa else theta[:nj].t(), motor_inertia=theta[nj:].t(), cost=cost,
                             xs=xb.permute(1, 0, 2), us=self.cut_u(ub.permute(1, 0, 2)), **hist)
+
+    def plant_identify(self, n_steps, weights=None, stiffness_bounds=None, motor_inertia_bounds=None, mu0=1e-3, mu_min=1e-12,
+                       mu_max=1e12, grow=10.0, shrink=0.1, max_rel=0.5, min_curv=1e-12, keep_history=False):
+        """Fit every trajectory's own spring stiffness and motor inertia to the recorded run in XS / US on the device
+        (aslr_plant_identify, include/aslr_to_amd_identify.h): n_steps Levenberg-Marquardt steps on the one-step prediction
+        error, one ABI call, no host round trip per step.  weights: [B, nx], [nx] or None (ones).  stiffness_bounds,
+        motor_inertia_bounds: (lo, hi), each [B, nj], [nj] or a scalar; a field whose bounds are None is not fitted.  The
+        initial parameters are the parameter table if one is set, the models' constants otherwise.  -> IdentifyResult; the
+        parameter table is left on the fit, XS / US are not written."""
+        torch = _torch()
+        B, nx, nj = self.B, self.nx, self.nx // 4
+        n = int(n_steps)
+        m = max(n, 0)
+        fit_k, fit_b = stiffness_bounds is not None, motor_inertia_bounds is not None
+        npar = (int(fit_k) + int(fit_b)) * nj
+        nh = npar * (npar + 1) // 2
+
+        def rows(bounds, name):
+            """(lo, hi) -> two [nj, B] tensors"""
+            if len(bounds) != 2:
+                raise ValueError("%s must be a pair (lo, hi)" % name)
+            out = []
+            for v in bounds:
+                t = self._f64(v)
+                if t.dim() == 0:
+                    t = t.expand(nj)
+                if t.dim() == 1:
+                    t = t.unsqueeze(0).expand(B, -1)
+                if tuple(t.shape) != (B, nj):
+                    raise ValueError("%s entries must have shape [B=%d, nj=%d], [nj] or be scalars, not %s"
+                                     % (name, B, nj, list(t.shape)))
+                out.append(t.t())
+            return out
+
+        with torch.cuda.device(self.device):
+            los, his = [], []
+            for on, bounds, name in ((fit_k, stiffness_bounds, "stiffness_bounds"), (fit_b, motor_inertia_bounds, "motor_inertia_bounds")):
+                if on:
+                    l, h = rows(bounds, name)
+                    los.append(l)
+                    his.append(h)
+            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
+            f64, i32 = torch.float64, torch.int32
+            lo = torch.cat(los).contiguous() if los else new(f64, 1)
+            hi = torch.cat(his).contiguous() if his else new(f64, 1)
+            w = None
+            if weights is not None:
+                w = self._f64(weights)
+                if w.dim() == 1:
+                    w = w.unsqueeze(0).expand(B, -1)
+                if tuple(w.shape) != (B, nx):
+                    raise ValueError("weights must have shape [B=%d, nx=%d] or [nx], not %s" % (B, nx, list(w.shape)))
+                w = w.t().contiguous()
+            r = max(npar, 1)
+            theta, sse, grad, info, mu = new(f64, r, B), new(f64, B), new(f64, r, B), new(f64, max(nh, 1), B), new(f64, B)
+            ident, nacc = new(i32, r, B), new(i32, B)
+            work = new(f64, 2 * r + 1 + max(nh, 1), B)
+            ht = new(f64, m, r, B) if keep_history else None
+            hs = new(f64, m, B) if keep_history else None
+            hd = new(i32, m, B) if keep_history else None
+        d = _abi.Identify()
+        d.n_steps, d.fit_stiffness, d.fit_motor_inertia = n, int(fit_k), int(fit_b)
+        d.mu0, d.mu_min, d.mu_max, d.grow, d.shrink = float(mu0), float(mu_min), float(mu_max), float(grow), float(shrink)
+        d.max_rel, d.min_curv = float(max_rel), float(min_curv)
+        d.weights, d.lo, d.hi = _ptr(w), _ptr(lo), _ptr(hi)
+        d.theta, d.sse, d.grad, d.information, d.mu = _ptr(theta), _ptr(sse), _ptr(grad), _ptr(info), _ptr(mu)
+        d.identifiable, d.n_accepted, d.work = _ptr(ident), _ptr(nacc), _ptr(work)
+        d.hist_theta, d.hist_sse, d.hist_decision = _ptr(ht), _ptr(hs), _ptr(hd)
+        self._call("aslr_plant_identify", C.byref(d), self._stream())
+        torch.cuda.synchronize(self.device)  # (the scratch tensors die on return)
+        # the fitted fields from theta, the others from the table (reciprocal motor rows)
+        reg = _abi.Region()
+        _abi.check(self.lib.aslr_problem_region(self.handle, _abi.R_TRAJ_PARAMS, C.byref(reg)), "aslr_problem_region")
+        table = self.ws[reg.offset:reg.offset + reg.bytes].view(f64).view(2 * nj + 2 * self.nu, B)
+        vsa = self.low.dam == _abi.DAM_VSA
+        k0 = nj if fit_k else 0
+        stiffness = None if vsa else (theta[:nj] if fit_k else table[:nj]).t().clone()
+        motor = (theta[k0:k0 + nj].t() if fit_b else (1.0 / table[nj:2 * nj]).t()).clone()
+        full = new(f64, B, npar, npar)
+        pi, qi = (torch.as_tensor(v, device=self.device) for v in np.tril_indices(npar))
+        full[:, pi, qi] = info[:nh].t()
+        full[:, qi, pi] = info[:nh].t()
+        hist = {}
+        if keep_history:
+            hist = dict(theta_history=ht.permute(2, 0, 1), sse_history=hs.t(), decision_history=hd.t())
+        return IdentifyResult(stiffness=stiffness, motor_inertia=motor, theta=theta.t(), sse=sse, n_accepted=nacc, grad=grad.t(),
+                              information=full, identifiable=ident.t() != 0, mu=mu, **hist)
 
     def traj_f(self, row):
         return self.region(_abi.R_TRAJ_F)[row]
