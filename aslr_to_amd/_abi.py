@@ -180,51 +180,73 @@ def lib_path():
     return os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", LIB_NAME)
 
 
-# every symbol include/aslr_to_amd.h declares
-EXPORTED_SYMBOLS = [
-    "aslr_abi_version", "aslr_sizeof", "aslr_record_len", "aslr_solver_params_default",
-    "aslr_workspace_bytes", "aslr_problem_create", "aslr_problem_destroy", "aslr_problem_region",
-    "aslr_calc", "aslr_calc_diff", "aslr_backward_pass", "aslr_forward_pass", "aslr_solve",
-    "aslr_iterate", "aslr_iterate_timed", "aslr_finalize", "aslr_count_active", "aslr_dam_eval", "aslr_quasi_static", "aslr_last_error",
-    "aslr_dam_residuals", "aslr_residual_len", "aslr_frame_placement", "aslr_set_iteration_log",
-    "aslr_iterate_n", "aslr_set_subshards", "aslr_solve_pool", "aslr_set_trajectory_params",
-    "aslr_mpc_run", "aslr_set_reference_path", "aslr_reference_row",
-]
+_vp, _i64, _sp = C.c_void_p, C.c_int64, C.POINTER(SolverParams)
+_rollout = [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]
+_mpc_plant = [_vp, _sp, C.POINTER(Mpc), C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp]
 
-# what include/aslr_to_amd_sens.h declares: an extension exported from the same library, kept apart from the base set so
-# that the base header, its symbol list and ABI_VERSION stay what existing bindings check against
-EXTENSION_SYMBOLS = ["aslr_cost_sensitivity"]
+# header under include/ -> {function it declares: (restype, argtypes)}, in the order of the symbol lists below; argtypes
+# None: left unset (a function without parameters).  The base header comes first; every extension is exported from the same
+# library under a header of its own, so that the base header, its symbol list and ABI_VERSION stay what existing bindings
+# check against.  (The aslr_debug_* exports are in no header and not bound here.)
+PROTOTYPES = {
+    "aslr_to_amd.h": {
+        "aslr_abi_version": (C.c_int, None),
+        "aslr_sizeof": (_i64, [C.c_int]),
+        "aslr_record_len": (_i, [_i, _i]),
+        "aslr_solver_params_default": (None, [_sp, _i]),
+        "aslr_workspace_bytes": (_i64, [C.POINTER(ProblemDesc)]),
+        "aslr_problem_create": (C.c_int, [C.POINTER(ProblemDesc), _vp, _i64, _vp, C.POINTER(_vp)]),
+        "aslr_problem_destroy": (C.c_int, [_vp]),
+        "aslr_problem_region": (C.c_int, [_vp, _i, C.POINTER(Region)]),
+        "aslr_calc": (C.c_int, [_vp, _vp]),
+        "aslr_calc_diff": (C.c_int, [_vp, _vp]),
+        "aslr_backward_pass": (C.c_int, [_vp, _sp, _vp]),
+        "aslr_forward_pass": (C.c_int, [_vp, _sp, _vp]),
+        "aslr_solve": (C.c_int, [_vp, _sp, _i, _vp, C.POINTER(_i)]),
+        "aslr_iterate": (C.c_int, [_vp, _sp, _i, _vp]),
+        "aslr_iterate_timed": (C.c_int, [_vp, _sp, _i, _vp, C.POINTER(C.c_float)]),
+        "aslr_finalize": (C.c_int, [_vp, _vp]),
+        "aslr_count_active": (C.c_int, [_vp, _vp, C.POINTER(_i)]),
+        "aslr_dam_eval": (C.c_int, [_vp, _i, _i] + [_vp] * 12),
+        "aslr_quasi_static": (C.c_int, [_vp, _i, _d, _vp, _vp]),
+        "aslr_last_error": (C.c_char_p, None),
+        "aslr_dam_residuals": (C.c_int, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+        "aslr_residual_len": (_i, [C.POINTER(Model), _i]),
+        "aslr_frame_placement": (C.c_int, [_vp, _i, C.POINTER(_d), C.POINTER(_d), _i, _vp, _i64, _vp, _vp]),
+        "aslr_set_iteration_log": (C.c_int, [_vp, _vp, _i]),
+        "aslr_iterate_n": (C.c_int, [_vp, _sp, _i, _i, _vp]),
+        "aslr_set_subshards": (C.c_int, [_vp, _i]),
+        "aslr_solve_pool": (C.c_int, [_vp, _sp, C.POINTER(Pool), _i, _i, _vp, C.POINTER(_i)]),
+        "aslr_set_trajectory_params": (C.c_int, [_vp, C.POINTER(TrajParams), _vp]),
+        "aslr_mpc_run": (C.c_int, [_vp, _sp, C.POINTER(Mpc), _vp]),
+        "aslr_set_reference_path": (C.c_int, [_vp, _vp, _i, _i, _vp]),
+        "aslr_reference_row": (C.c_int, [_vp, C.POINTER(_i)]),
+    },
+    "aslr_to_amd_sens.h": {"aslr_cost_sensitivity": (C.c_int, [_vp] * 6)},
+    "aslr_to_amd_policy.h": {"aslr_policy_rollout": (C.c_int, _rollout)},
+    "aslr_to_amd_mpc_plant.h": {"aslr_mpc_run_plant": (C.c_int, _mpc_plant)},
+    "aslr_to_amd_pool_params.h": {
+        "aslr_solve_pool_params": (C.c_int, [_vp, _sp, C.POINTER(Pool), C.POINTER(PoolParams), _i, _i, _vp, C.POINTER(_i)])},
+    "aslr_to_amd_cov.h": {"aslr_policy_covariance": (C.c_int, [_vp] * 9)},
+    "aslr_to_amd_plant_sens.h": {"aslr_policy_plant_sensitivity": (C.c_int, [_vp] * 12)},
+    "aslr_to_amd_design.h": {"aslr_design_descent": (C.c_int, [_vp, _sp, C.POINTER(Design), _vp])},
+    "aslr_to_amd_policy_all.h": {"aslr_policy_rollout_all": (C.c_int, _rollout)},
+    "aslr_to_amd_mpc_plant_all.h": {"aslr_mpc_run_plant_all": (C.c_int, _mpc_plant)},
+    "aslr_to_amd_policy_noise.h": {
+        "aslr_policy_rollout_noise": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_int] + [_vp] * 10)},
+    "aslr_to_amd_identify.h": {"aslr_plant_identify": (C.c_int, [_vp, C.POINTER(Identify), _vp])},
+}
 
-# what include/aslr_to_amd_policy.h declares: a second extension header, in a list of its own so that EXTENSION_SYMBOLS
-# keeps equalling what aslr_to_amd_sens.h declares
-POLICY_SYMBOLS = ["aslr_policy_rollout"]
-
-# what include/aslr_to_amd_mpc_plant.h declares: a third extension header, in a list of its own for the same reason
-MPC_PLANT_SYMBOLS = ["aslr_mpc_run_plant"]
-
-# what include/aslr_to_amd_pool_params.h declares: a fourth extension header, in a list of its own for the same reason
-POOL_PARAMS_SYMBOLS = ["aslr_solve_pool_params"]
-
-# what include/aslr_to_amd_cov.h declares: a fifth extension header, in a list of its own for the same reason
-COV_SYMBOLS = ["aslr_policy_covariance"]
-
-# what include/aslr_to_amd_plant_sens.h declares: a sixth extension header, in a list of its own for the same reason
-PLANT_SENS_SYMBOLS = ["aslr_policy_plant_sensitivity"]
-
-# what include/aslr_to_amd_design.h declares: a seventh extension header, in a list of its own for the same reason
-DESIGN_SYMBOLS = ["aslr_design_descent"]
-
-# what include/aslr_to_amd_policy_all.h declares: an eighth extension header, in a list of its own for the same reason
-POLICY_ALL_SYMBOLS = ["aslr_policy_rollout_all"]
-
-# what include/aslr_to_amd_mpc_plant_all.h declares: a ninth extension header, in a list of its own for the same reason
-MPC_PLANT_ALL_SYMBOLS = ["aslr_mpc_run_plant_all"]
-
-# what include/aslr_to_amd_policy_noise.h declares: a tenth extension header, in a list of its own for the same reason
-POLICY_NOISE_SYMBOLS = ["aslr_policy_rollout_noise"]
-
-# what include/aslr_to_amd_identify.h declares: an eleventh extension header, in a list of its own for the same reason
-IDENTIFY_SYMBOLS = ["aslr_plant_identify"]
+# header -> the module attribute that lists what it declares (EXPORTED_SYMBOLS: the base header's)
+SYMBOL_LISTS = {
+    "aslr_to_amd.h": "EXPORTED_SYMBOLS", "aslr_to_amd_sens.h": "EXTENSION_SYMBOLS", "aslr_to_amd_policy.h": "POLICY_SYMBOLS",
+    "aslr_to_amd_mpc_plant.h": "MPC_PLANT_SYMBOLS", "aslr_to_amd_pool_params.h": "POOL_PARAMS_SYMBOLS",
+    "aslr_to_amd_cov.h": "COV_SYMBOLS", "aslr_to_amd_plant_sens.h": "PLANT_SENS_SYMBOLS",
+    "aslr_to_amd_design.h": "DESIGN_SYMBOLS", "aslr_to_amd_policy_all.h": "POLICY_ALL_SYMBOLS",
+    "aslr_to_amd_mpc_plant_all.h": "MPC_PLANT_ALL_SYMBOLS", "aslr_to_amd_policy_noise.h": "POLICY_NOISE_SYMBOLS",
+    "aslr_to_amd_identify.h": "IDENTIFY_SYMBOLS",
+}
+globals().update((attr, list(PROTOTYPES[header])) for header, attr in SYMBOL_LISTS.items())
 
 
 def load_library():
@@ -242,88 +264,12 @@ def load_library():
     # device pointers of torch tensors would belong to a different runtime than our kernel launches
     import torch  # noqa: F401
     lib = C.CDLL(path)
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    lib.aslr_abi_version.restype = C.c_int
-    lib.aslr_sizeof.restype = i64
-    lib.aslr_sizeof.argtypes = [C.c_int]
-    lib.aslr_record_len.restype = i32
-    lib.aslr_record_len.argtypes = [i32, i32]
-    lib.aslr_solver_params_default.restype = None
-    lib.aslr_solver_params_default.argtypes = [C.POINTER(SolverParams), i32]
-    lib.aslr_workspace_bytes.restype = i64
-    lib.aslr_workspace_bytes.argtypes = [C.POINTER(ProblemDesc)]
-    lib.aslr_problem_create.restype = C.c_int
-    lib.aslr_problem_create.argtypes = [C.POINTER(ProblemDesc), vp, i64, vp, C.POINTER(vp)]
-    lib.aslr_problem_destroy.restype = C.c_int
-    lib.aslr_problem_destroy.argtypes = [vp]
-    lib.aslr_problem_region.restype = C.c_int
-    lib.aslr_problem_region.argtypes = [vp, i32, C.POINTER(Region)]
-    for name in ("aslr_calc", "aslr_calc_diff", "aslr_finalize"):
-        f = getattr(lib, name)
-        f.restype = C.c_int
-        f.argtypes = [vp, vp]
-    for name in ("aslr_backward_pass", "aslr_forward_pass"):
-        f = getattr(lib, name)
-        f.restype = C.c_int
-        f.argtypes = [vp, C.POINTER(SolverParams), vp]
-    lib.aslr_solve.restype = C.c_int
-    lib.aslr_solve.argtypes = [vp, C.POINTER(SolverParams), i32, vp, C.POINTER(i32)]
-    lib.aslr_iterate.restype = C.c_int
-    lib.aslr_iterate.argtypes = [vp, C.POINTER(SolverParams), i32, vp]
-    lib.aslr_iterate_timed.restype = C.c_int
-    lib.aslr_iterate_timed.argtypes = [vp, C.POINTER(SolverParams), i32, vp, C.POINTER(C.c_float)]
-    lib.aslr_count_active.restype = C.c_int
-    lib.aslr_count_active.argtypes = [vp, vp, C.POINTER(i32)]
-    lib.aslr_dam_eval.restype = C.c_int
-    lib.aslr_dam_eval.argtypes = [vp, i32, i32] + [vp] * 11 + [vp]
-    lib.aslr_quasi_static.restype = C.c_int
-    lib.aslr_quasi_static.argtypes = [vp, i32, C.c_double, vp, vp]
-    lib.aslr_last_error.restype = C.c_char_p
-    lib.aslr_dam_residuals.restype = C.c_int
-    lib.aslr_dam_residuals.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-    lib.aslr_residual_len.restype = i32
-    lib.aslr_residual_len.argtypes = [C.POINTER(Model), i32]
-    lib.aslr_frame_placement.restype = C.c_int
-    lib.aslr_frame_placement.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, vp, i64, vp, vp]
-    lib.aslr_iterate_n.restype = C.c_int
-    lib.aslr_iterate_n.argtypes = [vp, C.POINTER(SolverParams), i32, i32, vp]
-    lib.aslr_solve_pool.restype = C.c_int
-    lib.aslr_solve_pool.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Pool), i32, i32, vp, C.POINTER(i32)]
-    lib.aslr_set_subshards.restype = C.c_int
-    lib.aslr_set_subshards.argtypes = [vp, i32]
-    lib.aslr_set_trajectory_params.restype = C.c_int
-    lib.aslr_set_trajectory_params.argtypes = [vp, C.POINTER(TrajParams), vp]
-    lib.aslr_mpc_run.restype = C.c_int
-    lib.aslr_mpc_run.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), vp]
-    lib.aslr_set_reference_path.restype = C.c_int
-    lib.aslr_set_reference_path.argtypes = [vp, vp, i32, i32, vp]
-    lib.aslr_reference_row.restype = C.c_int
-    lib.aslr_reference_row.argtypes = [vp, C.POINTER(i32)]
-    lib.aslr_set_iteration_log.restype = C.c_int
-    lib.aslr_set_iteration_log.argtypes = [vp, vp, i32]
-    lib.aslr_cost_sensitivity.restype = C.c_int
-    lib.aslr_cost_sensitivity.argtypes = [vp, vp, vp, vp, vp, vp]
-    lib.aslr_policy_rollout.restype = C.c_int
-    lib.aslr_policy_rollout.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.aslr_policy_rollout_all.restype = C.c_int
-    lib.aslr_policy_rollout_all.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
-    lib.aslr_policy_rollout_noise.restype = C.c_int
-    lib.aslr_policy_rollout_noise.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp, C.c_int] + [vp] * 10
-    lib.aslr_mpc_run_plant.restype = C.c_int
-    lib.aslr_mpc_run_plant.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
-    lib.aslr_mpc_run_plant_all.restype = C.c_int
-    lib.aslr_mpc_run_plant_all.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Mpc), C.c_int, vp, vp, C.c_int, vp, vp, vp]
-    lib.aslr_solve_pool_params.restype = C.c_int
-    lib.aslr_solve_pool_params.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Pool), C.POINTER(PoolParams), i32, i32, vp,
-                                           C.POINTER(i32)]
-    lib.aslr_policy_covariance.restype = C.c_int
-    lib.aslr_policy_covariance.argtypes = [vp] * 9
-    lib.aslr_policy_plant_sensitivity.restype = C.c_int
-    lib.aslr_policy_plant_sensitivity.argtypes = [vp] * 12
-    lib.aslr_design_descent.restype = C.c_int
-    lib.aslr_design_descent.argtypes = [vp, C.POINTER(SolverParams), C.POINTER(Design), vp]
-    lib.aslr_plant_identify.restype = C.c_int
-    lib.aslr_plant_identify.argtypes = [vp, C.POINTER(Identify), vp]
+    for functions in PROTOTYPES.values():
+        for name, (restype, argtypes) in functions.items():
+            f = getattr(lib, name)
+            f.restype = restype
+            if argtypes is not None:
+                f.argtypes = argtypes
     if lib.aslr_abi_version() != ABI_VERSION:
         raise ImportError("aslr_to_amd: ABI version mismatch between %s and the Python layer" % path)
     for which, st in enumerate((Chain, Cost, Model, ProblemDesc, SolverParams, Region, Pool, TrajParams, Mpc)):

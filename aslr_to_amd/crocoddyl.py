@@ -162,18 +162,34 @@ class ShootingProblem(object):
             return self._engine.reference_row
         return 0 if self._lowered.ref_path is None else self._lowered.ref_path[1]
 
+    def _shard(self, v, ndim=None, pair=False):
+        """This rank's rows of v where v is a whole-batch array: one of `ndim` dimensions with a row per trajectory (ndim
+        None: any array).  Anything else, and None, passes through for the engine to judge.  pair: v is (lo, hi), and
+        each entry is cut."""
+        if pair:
+            return v if v is None or len(v) != 2 else tuple(self._shard(e, ndim) for e in v)
+        whole = v is not None and (ndim is None or (np.ndim(v) == ndim and len(v) == self.batch_total))
+        return v[self.rows[0]:self.rows[1]] if whole else v
+
     def _shard_params(self, stiffness, motor_inertia, u_lb, u_ub):
         """rows of this rank out of whole-batch parameter arrays"""
-        lo, hi = self.rows
         out = {}
         for name, v in (("stiffness", stiffness), ("motor_inertia", motor_inertia), ("u_lb", u_lb), ("u_ub", u_ub)):
             if v is not None:
                 v = np.array(v, dtype=np.float64, ndmin=2)
                 if v.shape[0] != self.batch_total:
                     raise ValueError("%s needs one row per trajectory (%d), got %d" % (name, self.batch_total, v.shape[0]))
-                v = v[lo:hi]
-            out[name] = v
+            out[name] = self._shard(v)
         return out
+
+    def _follow_table(self, r):
+        """the problem's own record of the parameter table follows the engine's, which a design descent or an identification
+        left on r.stiffness / r.motor_inertia (a later engine of this problem starts from it)"""
+        low = self._lowered
+        old = low.traj_params or {}
+        low.traj_params = lower_traj_params(low.desc, low.nj, low.nu, low.nu_user, low.dam,
+                                            None if r.stiffness is None else r.stiffness.cpu().numpy(),
+                                            r.motor_inertia.cpu().numpy(), old.get("u_lb"), old.get("u_ub"))
 
     def set_trajectory_params(self, stiffness=None, motor_inertia=None, u_lb=None, u_ub=None):
         """Replace the per-trajectory parameter table between solves (whole-batch arrays, as in the constructor; all
@@ -234,25 +250,11 @@ class ShootingProblem(object):
         are None is not fitted (no stiffness_bounds for a VSA model).  -> engine.IdentifyResult; the problem's parameter
         table is left on the fit.  This shard's trajectories only."""
         e = self.engine
-        lo, hi = self.rows
-
-        def shard(v, width):  # whole-batch rows -> this rank's
-            return v[lo:hi] if v is not None and np.ndim(v) == width and len(v) == self.batch_total else v
-
-        def shard2(bounds):
-            if bounds is None or len(bounds) != 2:
-                return bounds
-            return tuple(shard(v, 2) for v in bounds)
-
         e.set_candidate(xs, us)
-        r = e.plant_identify(n_steps, shard(weights, 2), shard2(stiffness_bounds), shard2(motor_inertia_bounds), mu0=mu0, grow=grow,
-                             shrink=shrink, max_rel=max_rel, min_curv=min_curv, keep_history=keep_history)
-        # the problem's own record of the table follows the engine's (a later engine of this problem starts from it)
-        low = self._lowered
-        old = low.traj_params or {}
-        low.traj_params = lower_traj_params(low.desc, low.nj, low.nu, low.nu_user, low.dam,
-                                            None if r.stiffness is None else r.stiffness.cpu().numpy(),
-                                            r.motor_inertia.cpu().numpy(), old.get("u_lb"), old.get("u_ub"))
+        r = e.plant_identify(n_steps, self._shard(weights, 2), self._shard(stiffness_bounds, 2, pair=True),
+                             self._shard(motor_inertia_bounds, 2, pair=True), mu0=mu0, grow=grow, shrink=shrink, max_rel=max_rel,
+                             min_curv=min_curv, keep_history=keep_history)
+        self._follow_table(r)
         return r
 
     def policy_rollout(self, xs, us, K, n_samples, plant_stiffness=None, plant_motor_inertia=None, dx0=None,
@@ -603,23 +605,11 @@ class SolverDDP(object):
         sp.maxiter = int(maxiter)
         sp.is_feasible = 0
         sp.reg_init = float("nan")
-        lo, hi = p.rows
-
-        def shard(bounds):  # whole-batch [B, nj] entries -> this rank's rows
-            if bounds is None or len(bounds) != 2:
-                return bounds
-            return tuple(v[lo:hi] if np.ndim(v) == 2 and len(v) == p.batch_total else v for v in bounds)
-
         e.set_candidate(init_xs, init_us)
         e.enable_iteration_log(0)
-        r = e.design_descent(sp, n_steps, sp.maxiter, iters_per_step, shard(stiffness_bounds), shard(motor_inertia_bounds),
-                             eta0, grow, shrink, c1, max_rel, keep_history)
-        # the problem's own record of the table follows the engine's (a later engine of this problem starts from it)
-        low = p.lowered
-        old = low.traj_params or {}
-        low.traj_params = lower_traj_params(low.desc, low.nj, low.nu, low.nu_user, low.dam,
-                                            None if r.stiffness is None else r.stiffness.cpu().numpy(),
-                                            r.motor_inertia.cpu().numpy(), old.get("u_lb"), old.get("u_ub"))
+        r = e.design_descent(sp, n_steps, sp.maxiter, iters_per_step, p._shard(stiffness_bounds, 2, pair=True),
+                             p._shard(motor_inertia_bounds, 2, pair=True), eta0, grow, shrink, c1, max_rel, keep_history)
+        p._follow_table(r)
         return r
 
     def cost_sensitivity(self):

@@ -23,74 +23,60 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
-class MpcResult(object):
+class _Result(object):
+    """What an Engine call returns: its fields as attributes."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+class MpcResult(_Result):
     """What Engine.mpc_run returns: batch-major device tensors, views of the time-major arrays the kernels wrote --
     xs_closed [B, n+1, nx], us_closed [B, n, nu_user], and per step's solve iters, status (int32), cost, stop, x_reg,
     step [B, n]; reference_row (int): the row of the reference path knot 0 reads after the run (0 without a path).
     Engine.mpc_run_plant returns the same with N = n * hold applied knots in xs_closed [B, N+1, nx] and us_closed
     [B, N, nu_user], plus closed_cost [B] (None when not asked for), failed_knot [B] (int32; -1: none) and hold."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class SensitivityResult(object):
+class SensitivityResult(_Result):
     """What Engine.cost_sensitivity returns: batch-major device tensors -- stiffness [B, nj] (dJ/dK_j; None for a VSA model,
     whose stiffness is a control), motor_inertia [B, nj] (dJ/dB_j), x0 [B, nx] (dJ/dx0) and costate [B, T+1, nx]."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class PolicyRolloutResult(object):
+class PolicyRolloutResult(_Result):
     """What Engine.policy_rollout returns: batch-major device tensors -- cost [B, S] (NaN for a failed sample),
     failed_knot [B, S] (int32; -1: none), x_final [B, S, nx] and, when kept, xs [B, S, T+1, nx] and us [B, S, T, nu] (the
     models' own nu: padded controls are cut); xs and us are None otherwise."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class PolicyCovarianceResult(object):
+class PolicyCovarianceResult(_Result):
     """What Engine.policy_covariance returns: batch-major device tensors -- x_var [B, T+1, nx] (diagonal of Sigma_t), u_var
     [B, T, nu] (diagonal of K Sigma K^T; the models' own nu: padded controls are cut), cov_final [B, nx, nx] (Sigma_T),
     cost_increase [B] and, when kept, cov [B, T+1, nx, nx] (every Sigma_t); cov is None otherwise."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class PlantSensitivityResult(object):
+class PlantSensitivityResult(_Result):
     """What Engine.policy_plant_sensitivity returns: batch-major device tensors -- dx_final_dstiffness,
     dx_final_dmotor_inertia [B, nx, nj] (dx_T/dK_j, dx_T/dB_j), dcost_dstiffness, dcost_dmotor_inertia [B, nj], x_var
     [B, T+1, nx] and u_var [B, T, nu] (the models' own nu; both None when no variance was given) and, when kept,
     dxs_dstiffness, dxs_dmotor_inertia [B, T+1, nx, nj] (None otherwise).  The stiffness fields are None for a VSA model."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class DesignResult(object):
+class DesignResult(_Result):
     """What Engine.design_descent returns: batch-major device tensors -- stiffness [B, nj] (the accepted diag K; None for a
     VSA model), motor_inertia [B, nj] (the accepted diag B), cost [B], xs [B, T+1, nx], us [B, T, nu] (the models' own nu) and,
     when the history is kept, cost_history, eta_history, predicted_history [B, n_steps], accepted_history [B, n_steps]
     (int32: 1 accepted, 0 rejected, -1 not evaluable), stiffness_history (None for VSA) and motor_inertia_history
     [B, n_steps, nj]: the candidate evaluated in every step."""
 
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
-
-class IdentifyResult(object):
+class IdentifyResult(_Result):
     """What Engine.plant_identify returns: batch-major device tensors -- stiffness [B, nj] (None for a VSA model) and
     motor_inertia [B, nj] (the fit where the field was fitted, the table's value otherwise), theta [B, np] (the fitted entries,
     stiffness first), sse [B], n_accepted [B] (int32), grad [B, np], information [B, np, np] (the Gauss-Newton matrix H in
     z = log theta, unpacked and symmetric), identifiable [B, np] (bool), mu [B] and, when the history is kept, theta_history
     [B, n_steps, np], sse_history [B, n_steps], decision_history [B, n_steps] (int32: 1 accepted, 0 rejected, -1 not
     evaluable)."""
-
-    def __init__(self, **fields):
-        self.__dict__.update(fields)
 
 
 class Engine(object):
@@ -110,7 +96,10 @@ class Engine(object):
         if nbytes <= 0:
             raise _abi.AslrError("invalid problem description (aslr_workspace_bytes = %d)" % nbytes)
         with torch.cuda.device(self.device):
-            self.ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
+            # zeroed, not empty: the library zeroes the regions a solve expects zeroed, but XS / US and the scratch are
+            # whatever the allocator's block held, and a call on a handle whose candidate was never set would read that
+            # (the fill is on the stream aslr_problem_create uploads on, so it is ordered before it)
+            self.ws = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
             off = (-self.ws.data_ptr()) % 256
             self.ws = self.ws[off:off + nbytes]
             self.handle = C.c_void_p()
@@ -181,14 +170,60 @@ class Engine(object):
                                device=self.device)
 
     def _dev(self, v, shape, perm, name, message=None):
-        """_f64(v), checked against the batch-major `shape`, permuted to the library's layout and made contiguous.
-        message: the ValueError text, where a caller has its own."""
+        """_f64(v), checked against the batch-major `shape`, permuted to the library's layout (perm None: as it is) and
+        made contiguous.  message: the ValueError text, where a caller has its own."""
         if v is None:
             return None
         t = self._f64(v)
         if tuple(t.shape) != shape:
             raise ValueError(message or "%s must have shape %s, not %s" % (name, list(shape), list(t.shape)))
-        return t.permute(*perm).contiguous()
+        return (t if perm is None else t.permute(*perm)).contiguous()
+
+    def _bcast(self, v, shape, short, perm, message, nonneg=None, say_given=False):
+        """_dev for a value that may come in a shorter form.  short: the accepted forms, each the tuple of the axes of
+        `shape` it carries (() is a scalar); the other axes are broadcast.  message: the ValueError text of a wrong shape,
+        {} in it the shape refused -- as far as it was broadcast, or as it was given (say_given).  nonneg: the ValueError
+        text of a negative entry, where the caller refuses one."""
+        if v is None:
+            return None
+        t = self._f64(v)
+        said = list(t.shape)
+        for axes in short:
+            if t.dim() == len(axes):
+                seen = [t.shape[axes.index(a)] if a in axes else 1 for a in range(len(shape))]
+                t = t.reshape(seen).expand([-1 if a in axes else n for a, n in enumerate(shape)])
+                break
+        t = self._dev(t, shape, perm, None, message.format(list(t.shape) if not say_given else said))
+        if nonneg and bool((t < 0).any()):
+            raise ValueError(nonneg)
+        return t
+
+    def _bounds(self, fields, ones):
+        """fields: (bounds, name) of the stiffness and of the motor inertia, bounds None or (lo, hi), each [B, nj], [nj] or a
+        scalar -> lo, hi: the rows [nj, B] of the fields stacked.  A field whose bounds are None is rows of ones (never
+        read) with `ones`, left out otherwise; (None, None) when that leaves nothing."""
+        torch = _torch()
+        B, nj = self.B, self.nx // 4
+        los, his = [], []
+        for bounds, name in fields:
+            if bounds is None:
+                if ones:
+                    los.append(torch.ones((nj, B), dtype=torch.float64, device=self.device))
+                    his.append(los[-1])
+                continue
+            if len(bounds) != 2:
+                raise ValueError("%s must be a pair (lo, hi)" % name)
+            lo, hi = (self._bcast(v, (B, nj), ((), (1,)), (1, 0), "%s entries must have shape [B=%d, nj=%d], [nj] or be scalars, "
+                                  "not {}" % (name, B, nj)) for v in bounds)
+            los.append(lo)
+            his.append(hi)
+        return (torch.cat(los), torch.cat(his)) if los else (None, None)
+
+    def _zeros(self, *shape, dtype=None):
+        """a zeroed tensor on this engine's device, float64 unless dtype says otherwise"""
+        torch = _torch()
+        with torch.cuda.device(self.device):
+            return torch.zeros(shape, dtype=dtype or torch.float64, device=self.device)
 
     def _call(self, name, *args):
         """One C-ABI call with this engine's device current (the ABI launches on the thread's current device, on a
@@ -248,6 +283,10 @@ class Engine(object):
         self._views[rid] = v
         return v
 
+    def _traj_table(self):
+        """the per-trajectory parameter table in R_TRAJ_PARAMS as the kernels read it: [2 nj + 2 nu, B] doubles (a view)"""
+        return self.region(_abi.R_TRAJ_PARAMS).view(_torch().float64).view(2 * (self.nx // 4) + 2 * self.nu, self.B)
+
     # batch-major views ([B, T, ...]) of the time-major storage
     @property
     def xs(self):
@@ -287,29 +326,20 @@ class Engine(object):
     def set_candidate(self, xs=None, us=None):
         """xs: [B, T+1, nx] / [T+1, nx] / list of arrays; us likewise.  None -> zeros
         (crocoddyl setCandidate with empty lists: state.zero() and zero controls)."""
-        torch = _torch()
         X, U = self.region(_abi.R_XS), self.region(_abi.R_US)
-        if xs is None or (hasattr(xs, "__len__") and len(xs) == 0):
-            X.zero_()
-        else:
-            x = torch.as_tensor(np.asarray(xs, dtype=np.float64) if not torch.is_tensor(xs) else xs,
-                                dtype=torch.float64, device=self.device)
-            if x.dim() == 2:
-                x = x.unsqueeze(0).expand(self.B, -1, -1)
-            if tuple(x.shape) != (self.B, self.T + 1, self.nx):
-                raise ValueError("xs must have shape [B=%d, T+1=%d, nx=%d]" % (self.B, self.T + 1, self.nx))
-            X.copy_(x.permute(1, 0, 2))
-        if us is None or (hasattr(us, "__len__") and len(us) == 0):
-            U.zero_()
-        else:
-            u = torch.as_tensor(np.asarray(us, dtype=np.float64) if not torch.is_tensor(us) else us,
-                                dtype=torch.float64, device=self.device)
-            if u.dim() == 2:
-                u = u.unsqueeze(0).expand(self.B, -1, -1)
-            u = self.pad_u(u)
-            if tuple(u.shape) != (self.B, self.T, self.nu):
-                raise ValueError("us must have shape [B=%d, T=%d, nu=%d]" % (self.B, self.T, self.nu))
-            U.copy_(u.permute(1, 0, 2))
+        for v, dst, text in ((xs, X, "xs must have shape [B=%d, T+1=%d, nx=%d]"), (us, U, "us must have shape [B=%d, T=%d, nu=%d]")):
+            if v is None or (hasattr(v, "__len__") and len(v) == 0):
+                dst.zero_()
+                continue
+            t = self._f64(v)
+            if t.dim() == 2:
+                t = t.unsqueeze(0).expand(self.B, -1, -1)
+            if dst is U:
+                t = self.pad_u(t)
+            knots, B, width = dst.shape
+            if tuple(t.shape) != (B, knots, width):
+                raise ValueError(text % (B, knots, width))
+            dst.copy_(t.permute(1, 0, 2))
 
     # ---- the hot path ----
     def calc(self):
@@ -367,12 +397,9 @@ class Engine(object):
         stiffness, motor inertia and initial state, by one calcDiff sweep and one adjoint sweep (aslr_cost_sensitivity,
         include/aslr_to_amd_sens.h).  -> SensitivityResult.  Exact where the candidate has no gaps; at a converged
         solution also the gradient of the optimal cost; with gaps the gradient of the linearisation about (xs, us)."""
-        torch = _torch()
-        nj = self.nx // 4
+        nj, zeros = self.nx // 4, self._zeros
         vsa = self.low.dam == _abi.DAM_VSA
-        with torch.cuda.device(self.device):
-            new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
-            dk, db, dx0, lam = (None if vsa else new(nj, self.B)), new(nj, self.B), new(self.nx, self.B), new(self.T + 1, self.B, self.nx)
+        dk, db, dx0, lam = (None if vsa else zeros(nj, self.B)), zeros(nj, self.B), zeros(self.nx, self.B), zeros(self.T + 1, self.B, self.nx)
         self._call("aslr_cost_sensitivity", _ptr(dk), _ptr(db), _ptr(dx0), _ptr(lam), self._stream())
         return SensitivityResult(stiffness=None if dk is None else dk.t(), motor_inertia=db.t(), x0=dx0.t(),
                                  costate=lam.permute(1, 0, 2))
@@ -387,8 +414,7 @@ class Engine(object):
         knot).  clamp: clamp the control to the knot's box.  -> PolicyRolloutResult.  Writes nothing into the workspace.
         Before any backward sweep K = 0 and the roll-out is open loop; a non-positive plant inertia is not checked (it
         lives on the device) and shows up in failed_knot."""
-        torch = _torch()
-        S, B, T, nx, nu, nj = int(n_samples), self.B, self.T, self.nx, self.nu, self.nx // 4
+        S, B, T, nx, nj = int(n_samples), self.B, self.T, self.nx, self.nx // 4
         if S > 0:  # (S <= 0: the library refuses by name)
             pk = self._dev(plant_stiffness, (B, S, nj), (2, 1, 0), "plant_stiffness")
             pb = self._dev(plant_motor_inertia, (B, S, nj), (2, 1, 0), "plant_motor_inertia")
@@ -396,27 +422,29 @@ class Engine(object):
             w = self._dev(disturbance, (B, S, T, nx), (1, 2, 0, 3), "disturbance")
         else:
             pk = pb = d0 = w = None
-        n = max(S, 0)
-        with torch.cuda.device(self.device):
-            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
-            cost, failed, xf = new(torch.float64, n, B), new(torch.int32, n, B), new(torch.float64, n, B, nx)
-            xs = new(torch.float64, n, T + 1, B, nx) if keep_trajectories else None
-            us = new(torch.float64, n, T, B, nu) if keep_trajectories else None
+        out = self._rollout_outputs(max(S, 0), keep_trajectories)
         # (2 joints: the entry point that has always served them; every other size: the one that serves all sizes)
-        self._call("aslr_policy_rollout" if nj == 2 else "aslr_policy_rollout_all", S, _ptr(pk), _ptr(pb), _ptr(d0), _ptr(w), 1 if clamp else 0, _ptr(cost), _ptr(failed),
-                   _ptr(xf), _ptr(xs), _ptr(us), self._stream())
+        self._call("aslr_policy_rollout" if nj == 2 else "aslr_policy_rollout_all", S, _ptr(pk), _ptr(pb), _ptr(d0), _ptr(w),
+                   1 if clamp else 0, *[_ptr(t) for t in out], self._stream())
+        return self._rollout_result(*out)
+
+    def _rollout_outputs(self, n, keep_trajectories):
+        """the zeroed outputs of a roll-out of n samples as the library writes them: cost, failed_knot [n, B], x_final
+        [n, B, nx] and, when kept, xs [n, T+1, B, nx] and us [n, T, B, nu] (None otherwise)"""
+        B, T, nx, zeros = self.B, self.T, self.nx, self._zeros
+        return (zeros(n, B), zeros(n, B, dtype=_torch().int32), zeros(n, B, nx),
+                zeros(n, T + 1, B, nx) if keep_trajectories else None, zeros(n, T, B, self.nu) if keep_trajectories else None)
+
+    def _rollout_result(self, cost, failed, xf, xs, us):
+        """the batch-major PolicyRolloutResult of what _rollout_outputs made, once the library has written it"""
         return PolicyRolloutResult(cost=cost.t(), failed_knot=failed.t(), x_final=xf.permute(1, 0, 2),
                                    xs=None if xs is None else xs.permute(2, 0, 1, 3),
                                    us=None if us is None else self.cut_u(us.permute(2, 0, 1, 3)))
 
     def _sigma(self, v, n, name):
         """a sigma of policy_rollout_noise: None, a scalar, [n] or [B, n] -> None or a contiguous [B, n] device tensor"""
-        if v is None:
-            return None
-        t = self._f64(v)
-        if t.dim() > 2 or (t.dim() >= 1 and t.shape[-1] != n) or (t.dim() == 2 and t.shape[0] != self.B):
-            raise ValueError("%s must be a scalar or have shape [%d] or [%d, %d], not %s" % (name, n, self.B, n, list(t.shape)))
-        return t.expand(self.B, n).contiguous()
+        return self._bcast(v, (self.B, n), ((), (1,)), None, "%s must be a scalar or have shape [%d] or [%d, %d], not {}"
+                           % (name, n, self.B, n), say_given=True)
 
     def policy_rollout_noise(self, n_samples, seed, noise_std=None, dx0_std=None, stiffness_rel_std=None,
                              motor_inertia_rel_std=None, clamp=False, keep_trajectories=False, keep_draws=False, sample0=0,
@@ -429,27 +457,19 @@ class Engine(object):
         [0, 2^64).  -> PolicyRolloutResult; with keep_draws it also has `draws`, a dict of batch-major tensors
         plant_stiffness, plant_motor_inertia [B, S, nj], dx0 [B, S, nx], disturbance [B, S, T, nx] (None for an absent
         source): the very arguments policy_rollout accepts.  Writes nothing into the workspace."""
-        torch = _torch()
-        S, B, T, nx, nu, nj = int(n_samples), self.B, self.T, self.nx, self.nu, self.nx // 4
+        S, B, T, nx, nj = int(n_samples), self.B, self.T, self.nx, self.nx // 4
         seed = int(seed)
         if not 0 <= seed < 2 ** 64:
             raise ValueError("seed must lie in [0, 2^64), not %d" % seed)
         sw, s0 = self._sigma(noise_std, nx, "noise_std"), self._sigma(dx0_std, nx, "dx0_std")
         sk, sb = self._sigma(stiffness_rel_std, nj, "stiffness_rel_std"), self._sigma(motor_inertia_rel_std, nj, "motor_inertia_rel_std")
         n = max(S, 0)  # (S <= 0: the library refuses by name)
-        with torch.cuda.device(self.device):
-            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
-            cost, failed, xf = new(torch.float64, n, B), new(torch.int32, n, B), new(torch.float64, n, B, nx)
-            xs = new(torch.float64, n, T + 1, B, nx) if keep_trajectories else None
-            us = new(torch.float64, n, T, B, nu) if keep_trajectories else None
-            kept = lambda sigma, *shape: new(torch.float64, *shape) if keep_draws and sigma is not None else None
-            dk, db, d0, dw = kept(sk, nj, n, B), kept(sb, nj, n, B), kept(s0, n, B, nx), kept(sw, n, T, B, nx)
+        out = self._rollout_outputs(n, keep_trajectories)
+        kept = lambda sigma, *shape: self._zeros(*shape) if keep_draws and sigma is not None else None
+        dk, db, d0, dw = kept(sk, nj, n, B), kept(sb, nj, n, B), kept(s0, n, B, nx), kept(sw, n, T, B, nx)
         self._call("aslr_policy_rollout_noise", S, int(sample0), int(trajectory0), C.c_uint64(seed), _ptr(sw), _ptr(s0), _ptr(sk),
-                   _ptr(sb), 1 if clamp else 0, _ptr(cost), _ptr(failed), _ptr(xf), _ptr(xs), _ptr(us), _ptr(dk), _ptr(db),
-                   _ptr(d0), _ptr(dw), self._stream())
-        r = PolicyRolloutResult(cost=cost.t(), failed_knot=failed.t(), x_final=xf.permute(1, 0, 2),
-                                xs=None if xs is None else xs.permute(2, 0, 1, 3),
-                                us=None if us is None else self.cut_u(us.permute(2, 0, 1, 3)))
+                   _ptr(sb), 1 if clamp else 0, *[_ptr(t) for t in out], _ptr(dk), _ptr(db), _ptr(d0), _ptr(dw), self._stream())
+        r = self._rollout_result(*out)
         if keep_draws:
             back = lambda t, *perm: None if t is None else t.permute(*perm)
             r.draws = dict(plant_stiffness=back(dk, 2, 1, 0), plant_motor_inertia=back(db, 2, 1, 0), dx0=back(d0, 1, 0, 2),
@@ -466,31 +486,19 @@ class Engine(object):
         torch = _torch()
         B, T, nx, nu = self.B, self.T, self.nx, self.nu
         with torch.cuda.device(self.device):
-            s0, w = self._f64(sigma0), self._f64(noise_var)
+            s0 = self._bcast(sigma0, (B, nx, nx), ((1, 2),), None,
+                             "sigma0 must have shape [B=%d, nx=%d, nx] or [nx, nx], not {}" % (B, nx))
             if s0 is not None:
-                if s0.dim() == 2:
-                    s0 = s0.unsqueeze(0).expand(B, -1, -1)
-                if tuple(s0.shape) != (B, nx, nx):
-                    raise ValueError("sigma0 must have shape [B=%d, nx=%d, nx] or [nx, nx], not %s" % (B, nx, list(s0.shape)))
                 if not torch.equal(s0, s0.transpose(1, 2)):
                     raise ValueError("sigma0 must be symmetric")
                 if bool((torch.diagonal(s0, dim1=1, dim2=2) < 0).any()):
                     raise ValueError("sigma0 has a negative variance on its diagonal")
-                s0 = s0.contiguous()
-            if w is not None:
-                if w.dim() == 1:
-                    w = w.unsqueeze(0).expand(B, -1)
-                if w.dim() == 2:
-                    w = w.unsqueeze(1).expand(-1, T, -1)
-                if tuple(w.shape) != (B, T, nx):
-                    raise ValueError("noise_var must have shape [B=%d, T=%d, nx=%d], [B, nx] or [nx], not %s"
-                                     % (B, T, nx, list(w.shape)))
-                if bool((w < 0).any()):
-                    raise ValueError("noise_var has a negative variance")
-                w = w.permute(1, 0, 2).contiguous()
-            new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
-            xv, uv, cf, ci = new(T + 1, B, nx), new(T, B, nu), new(B, nx, nx), new(B)
-            cov = new(T + 1, B, nx, nx) if keep_cov else None
+            w = self._bcast(noise_var, (B, T, nx), ((2,), (0, 2)), (1, 0, 2),
+                            "noise_var must have shape [B=%d, T=%d, nx=%d], [B, nx] or [nx], not {}" % (B, T, nx),
+                            nonneg="noise_var has a negative variance")
+        zeros = self._zeros
+        xv, uv, cf, ci = zeros(T + 1, B, nx), zeros(T, B, nu), zeros(B, nx, nx), zeros(B)
+        cov = zeros(T + 1, B, nx, nx) if keep_cov else None
         self._call("aslr_policy_covariance", _ptr(s0), _ptr(w), _ptr(xv), _ptr(uv), _ptr(cf), _ptr(cov), _ptr(ci), self._stream())
         torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
         return PolicyCovarianceResult(x_var=xv.permute(1, 0, 2), u_var=self.cut_u(uv.permute(1, 0, 2)), cov_final=cf,
@@ -511,24 +519,15 @@ class Engine(object):
             raise ValueError("stiffness_var on a VSA model, which takes its stiffness from u")
 
         def var(v, name):
-            if v is None:
-                return None
-            v = self._f64(v)
-            if v.dim() == 1:
-                v = v.unsqueeze(0).expand(B, -1)
-            if tuple(v.shape) != (B, nj):
-                raise ValueError("%s must have shape [B=%d, nj=%d] or [nj], not %s" % (name, B, nj, list(v.shape)))
-            if bool((v < 0).any()):
-                raise ValueError("%s has a negative variance" % name)
-            return v.t().contiguous()
+            return self._bcast(v, (B, nj), ((1,),), (1, 0), "%s must have shape [B=%d, nj=%d] or [nj], not {}" % (name, B, nj),
+                               nonneg="%s has a negative variance" % name)
 
-        with torch.cuda.device(self.device):
-            vk, vb = var(stiffness_var, "stiffness_var"), var(motor_inertia_var, "motor_inertia_var")
-            new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=self.device)
-            both = lambda *shape: (None if vsa else new(*shape), new(*shape))
-            (fk, fb), (ck, cb) = both(B, nx, nj), both(nj, B)
-            tk, tb = both(T + 1, B, nx, nj) if keep_trajectories else (None, None)
-            xv, uv = (new(T + 1, B, nx), new(T, B, nu)) if (vk is not None or vb is not None) else (None, None)
+        vk, vb = var(stiffness_var, "stiffness_var"), var(motor_inertia_var, "motor_inertia_var")
+        zeros = self._zeros
+        both = lambda *shape: (None if vsa else zeros(*shape), zeros(*shape))
+        (fk, fb), (ck, cb) = both(B, nx, nj), both(nj, B)
+        tk, tb = both(T + 1, B, nx, nj) if keep_trajectories else (None, None)
+        xv, uv = (zeros(T + 1, B, nx), zeros(T, B, nu)) if (vk is not None or vb is not None) else (None, None)
         self._call("aslr_policy_plant_sensitivity", _ptr(vk), _ptr(vb), _ptr(tk), _ptr(tb), _ptr(fk), _ptr(fb), _ptr(ck), _ptr(cb),
                    _ptr(xv), _ptr(uv), self._stream())
         torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
@@ -601,24 +600,13 @@ class Engine(object):
         aslr_solve_pool as before; otherwise the result also holds params, the lowered table [2 nj + 2 nu, P] on the device."""
         torch = _torch()
         with torch.cuda.device(self.device):
-            x0 = torch.as_tensor(x0s, dtype=torch.float64, device=self.device).contiguous()
+            x0 = self._f64(x0s)
             P = x0.shape[0]
-            if tuple(x0.shape) != (P, self.nx):
-                raise ValueError("x0s must have shape [P, nx=%d]" % self.nx)
-            fr = None
-            if frame_refs is not None:
-                fr = torch.as_tensor(frame_refs, dtype=torch.float64, device=self.device).contiguous()
-                if tuple(fr.shape) != (P, 12):
-                    raise ValueError("frame_refs must have shape [P, 12]")
-            xi = ui = None
-            if xs_init is not None:
-                xi = torch.as_tensor(xs_init, dtype=torch.float64, device=self.device).contiguous()
-                if tuple(xi.shape) != (P, self.T + 1, self.nx):
-                    raise ValueError("xs_init must have shape [P, T+1, nx]")
-            if us_init is not None:
-                ui = self.pad_u(torch.as_tensor(us_init, dtype=torch.float64, device=self.device)).contiguous()
-                if tuple(ui.shape) != (P, self.T, self.nu):
-                    raise ValueError("us_init must have shape [P, T, nu]")
+            x0 = self._dev(x0, (P, self.nx), None, "x0s", "x0s must have shape [P, nx=%d]" % self.nx)
+            fr = self._dev(frame_refs, (P, 12), None, "frame_refs", "frame_refs must have shape [P, 12]")
+            xi = self._dev(xs_init, (P, self.T + 1, self.nx), None, "xs_init", "xs_init must have shape [P, T+1, nx]")
+            ui = self._dev(None if us_init is None else self.pad_u(self._f64(us_init)), (P, self.T, self.nu), None, "us_init",
+                           "us_init must have shape [P, T, nu]")
             xs = torch.empty((P, self.T + 1, self.nx), dtype=torch.float64, device=self.device)
             us = torch.empty((P, self.T, self.nu), dtype=torch.float64, device=self.device)
             sf = torch.zeros((P, 4), dtype=torch.float64, device=self.device)
@@ -674,13 +662,9 @@ class Engine(object):
     def _mpc_block(self, n, N, first_maxiter, iters_per_step, dist):
         """The aslr_mpc_t of a run of n control steps that apply N knots in all, and the four zeroed time-major buffers it
         points to (x_closed, u_closed, stat_f, stat_i); dist: the time-major disturbance, or None."""
-        torch = _torch()
-        m = max(n, 0)
-        with torch.cuda.device(self.device):
-            xc = torch.zeros((N + 1, self.B, self.nx), dtype=torch.float64, device=self.device)
-            uc = torch.zeros((N, self.B, self.nu), dtype=torch.float64, device=self.device)
-            sf = torch.zeros((m, 4, self.B), dtype=torch.float64, device=self.device)
-            si = torch.zeros((m, 2, self.B), dtype=torch.int32, device=self.device)
+        m, zeros = max(n, 0), self._zeros
+        xc, uc = zeros(N + 1, self.B, self.nx), zeros(N, self.B, self.nu)
+        sf, si = zeros(m, 4, self.B), zeros(m, 2, self.B, dtype=_torch().int32)
         mpc = _abi.Mpc()
         mpc.n_steps, mpc.first_maxiter, mpc.iters_per_step = n, int(first_maxiter), int(iters_per_step)
         mpc.disturbance = dist.data_ptr() if dist is not None else None
@@ -713,7 +697,7 @@ class Engine(object):
             pk = self._dev(plant_stiffness, (self.B, nj), (1, 0), "plant_stiffness")
             pb = self._dev(plant_motor_inertia, (self.B, nj), (1, 0), "plant_motor_inertia")
             dist = self._dev(disturbance, (self.B, N, self.nx), (1, 0, 2), "disturbance")
-            cc = torch.zeros((self.B,), dtype=torch.float64, device=self.device) if closed_cost else None
+            cc = self._zeros(self.B) if closed_cost else None
             fk = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
         mpc, bufs = self._mpc_block(n, N, first_maxiter, iters_per_step, dist)
         # (2 joints: the entry point that has always served them; every other size: the one that serves all sizes)
@@ -736,36 +720,13 @@ class Engine(object):
         n = int(n_steps)
         m = max(n, 0)
 
-        def rows(bounds, name):
-            """(lo, hi) -> two [nj, B] tensors (ones where the field is not optimised: never read)"""
-            if bounds is None:
-                return [torch.ones((nj, B), dtype=torch.float64, device=self.device)] * 2
-            if len(bounds) != 2:
-                raise ValueError("%s must be a pair (lo, hi)" % name)
-            out = []
-            for v in bounds:
-                t = torch.as_tensor(np.asarray(v, dtype=np.float64) if not torch.is_tensor(v) else v, dtype=torch.float64,
-                                    device=self.device)
-                if t.dim() == 0:
-                    t = t.expand(nj)
-                if t.dim() == 1:
-                    t = t.unsqueeze(0).expand(B, -1)
-                if tuple(t.shape) != (B, nj):
-                    raise ValueError("%s entries must have shape [B=%d, nj=%d], [nj] or be scalars, not %s"
-                                     % (name, B, nj, list(t.shape)))
-                out.append(t.t())
-            return out
-
-        with torch.cuda.device(self.device):
-            (klo, khi), (blo, bhi) = rows(stiffness_bounds, "stiffness_bounds"), rows(motor_inertia_bounds, "motor_inertia_bounds")
-            lo, hi = torch.cat([klo, blo]).contiguous(), torch.cat([khi, bhi]).contiguous()
-            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
-            f64 = torch.float64
-            theta, cost, xb, ub = new(f64, 2 * nj, B), new(f64, B), new(f64, T + 1, B, nx), new(f64, T, B, nu)
-            gacc, eta, grad = new(f64, 2 * nj, B), new(f64, B), new(f64, 2 * nj, B)
-            hf = new(f64, m, 3, B) if keep_history else None
-            hi_ = new(torch.int32, m, B) if keep_history else None
-            th = new(f64, m, 2 * nj, B) if keep_history else None
+        lo, hi = self._bounds(((stiffness_bounds, "stiffness_bounds"), (motor_inertia_bounds, "motor_inertia_bounds")), ones=True)
+        zeros = self._zeros
+        theta, cost, xb, ub = zeros(2 * nj, B), zeros(B), zeros(T + 1, B, nx), zeros(T, B, nu)
+        gacc, eta, grad = zeros(2 * nj, B), zeros(B), zeros(2 * nj, B)
+        hf = zeros(m, 3, B) if keep_history else None
+        hi_ = zeros(m, B, dtype=torch.int32) if keep_history else None
+        th = zeros(m, 2 * nj, B) if keep_history else None
         d = _abi.Design()
         d.n_steps, d.first_maxiter, d.iters_per_step = n, int(first_maxiter), int(iters_per_step)
         d.opt_stiffness, d.opt_motor_inertia = int(stiffness_bounds is not None), int(motor_inertia_bounds is not None)
@@ -801,49 +762,18 @@ class Engine(object):
         npar = (int(fit_k) + int(fit_b)) * nj
         nh = npar * (npar + 1) // 2
 
-        def rows(bounds, name):
-            """(lo, hi) -> two [nj, B] tensors"""
-            if len(bounds) != 2:
-                raise ValueError("%s must be a pair (lo, hi)" % name)
-            out = []
-            for v in bounds:
-                t = self._f64(v)
-                if t.dim() == 0:
-                    t = t.expand(nj)
-                if t.dim() == 1:
-                    t = t.unsqueeze(0).expand(B, -1)
-                if tuple(t.shape) != (B, nj):
-                    raise ValueError("%s entries must have shape [B=%d, nj=%d], [nj] or be scalars, not %s"
-                                     % (name, B, nj, list(t.shape)))
-                out.append(t.t())
-            return out
-
-        with torch.cuda.device(self.device):
-            los, his = [], []
-            for on, bounds, name in ((fit_k, stiffness_bounds, "stiffness_bounds"), (fit_b, motor_inertia_bounds, "motor_inertia_bounds")):
-                if on:
-                    l, h = rows(bounds, name)
-                    los.append(l)
-                    his.append(h)
-            new = lambda dt, *shape: torch.zeros(shape, dtype=dt, device=self.device)
-            f64, i32 = torch.float64, torch.int32
-            lo = torch.cat(los).contiguous() if los else new(f64, 1)
-            hi = torch.cat(his).contiguous() if his else new(f64, 1)
-            w = None
-            if weights is not None:
-                w = self._f64(weights)
-                if w.dim() == 1:
-                    w = w.unsqueeze(0).expand(B, -1)
-                if tuple(w.shape) != (B, nx):
-                    raise ValueError("weights must have shape [B=%d, nx=%d] or [nx], not %s" % (B, nx, list(w.shape)))
-                w = w.t().contiguous()
-            r = max(npar, 1)
-            theta, sse, grad, info, mu = new(f64, r, B), new(f64, B), new(f64, r, B), new(f64, max(nh, 1), B), new(f64, B)
-            ident, nacc = new(i32, r, B), new(i32, B)
-            work = new(f64, 2 * r + 1 + max(nh, 1), B)
-            ht = new(f64, m, r, B) if keep_history else None
-            hs = new(f64, m, B) if keep_history else None
-            hd = new(i32, m, B) if keep_history else None
+        zeros, i32 = self._zeros, torch.int32
+        lo, hi = self._bounds(((stiffness_bounds, "stiffness_bounds"), (motor_inertia_bounds, "motor_inertia_bounds")), ones=False)
+        if lo is None:
+            lo, hi = zeros(1), zeros(1)
+        w = self._bcast(weights, (B, nx), ((1,),), (1, 0), "weights must have shape [B=%d, nx=%d] or [nx], not {}" % (B, nx))
+        r = max(npar, 1)
+        theta, sse, grad, info, mu = zeros(r, B), zeros(B), zeros(r, B), zeros(max(nh, 1), B), zeros(B)
+        ident, nacc = zeros(r, B, dtype=i32), zeros(B, dtype=i32)
+        work = zeros(2 * r + 1 + max(nh, 1), B)
+        ht = zeros(m, r, B) if keep_history else None
+        hs = zeros(m, B) if keep_history else None
+        hd = zeros(m, B, dtype=i32) if keep_history else None
         d = _abi.Identify()
         d.n_steps, d.fit_stiffness, d.fit_motor_inertia = n, int(fit_k), int(fit_b)
         d.mu0, d.mu_min, d.mu_max, d.grow, d.shrink = float(mu0), float(mu_min), float(mu_max), float(grow), float(shrink)
@@ -855,14 +785,12 @@ class Engine(object):
         self._call("aslr_plant_identify", C.byref(d), self._stream())
         torch.cuda.synchronize(self.device)  # (the scratch tensors die on return)
         # the fitted fields from theta, the others from the table (reciprocal motor rows)
-        reg = _abi.Region()
-        _abi.check(self.lib.aslr_problem_region(self.handle, _abi.R_TRAJ_PARAMS, C.byref(reg)), "aslr_problem_region")
-        table = self.ws[reg.offset:reg.offset + reg.bytes].view(f64).view(2 * nj + 2 * self.nu, B)
+        table = self._traj_table()
         vsa = self.low.dam == _abi.DAM_VSA
         k0 = nj if fit_k else 0
         stiffness = None if vsa else (theta[:nj] if fit_k else table[:nj]).t().clone()
         motor = (theta[k0:k0 + nj].t() if fit_b else (1.0 / table[nj:2 * nj]).t()).clone()
-        full = new(f64, B, npar, npar)
+        full = zeros(B, npar, npar)
         pi, qi = (torch.as_tensor(v, device=self.device) for v in np.tril_indices(npar))
         full[:, pi, qi] = info[:nh].t()
         full[:, qi, pi] = info[:nh].t()

@@ -3,9 +3,6 @@ the reference of tests/_covariance.py pinned on the oracle alone -- against the 
 finite differences and by sampling, and against the vector form of its own recursion -- and the conditioning of the inputs
 the GPU cases use (tests/test_gpu_covariance.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,32 +10,6 @@ import pytest
 import _covariance as cv
 import _policy as pol
 from aslr_to_amd import _abi, scenarios
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-OTHER_HEADERS = ("aslr_to_amd.h", "aslr_to_amd_sens.h", "aslr_to_amd_policy.h", "aslr_to_amd_mpc_plant.h", "aslr_to_amd_pool_params.h")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_covariance_header_is_bound_and_exported():
-    """every aslr_ function include/aslr_to_amd_cov.h declares is in _abi.COV_SYMBOLS and defined in the library; no other
-    header and no other symbol list knows it"""
-    declared = _declared("aslr_to_amd_cov.h")
-    assert declared and declared == set(_abi.COV_SYMBOLS)
-    for other in (_abi.EXPORTED_SYMBOLS, _abi.EXTENSION_SYMBOLS, _abi.POLICY_SYMBOLS, _abi.MPC_PLANT_SYMBOLS, _abi.POOL_PARAMS_SYMBOLS):
-        assert not declared & set(other)
-    for header in OTHER_HEADERS:
-        assert not declared & _declared(header), header
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared <= defined, declared - defined
-    lib = _abi.load_library()
-    for name in declared:
-        assert getattr(lib, name).argtypes is not None
 
 
 def test_a_null_handle_is_refused_by_name():

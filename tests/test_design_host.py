@@ -2,47 +2,12 @@
 tests/_design.py in a loop on the CPU oracle alone -- the properties a descent must have, and the conditioning of the cases
 the GPU tests reuse (tests/test_gpu_design.py): every case accepts and rejects, no Armijo decision within rounding."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import _design as D
 from aslr_to_amd import _abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-OTHER_HEADERS = ("aslr_to_amd.h", "aslr_to_amd_sens.h", "aslr_to_amd_policy.h", "aslr_to_amd_mpc_plant.h",
-                 "aslr_to_amd_pool_params.h", "aslr_to_amd_cov.h", "aslr_to_amd_plant_sens.h")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_design_header_is_bound_and_exported():
-    """include/aslr_to_amd_design.h declares exactly _abi.DESIGN_SYMBOLS, which the library defines; no other header and no
-    other symbol list knows the name; the base header's list, ABI version 5 and aslr_sizeof(9) == -1 are untouched; the
-    ctypes mirror of aslr_design_t has the size of 6 int32, 5 doubles and 12 pointers"""
-    declared = _declared("aslr_to_amd_design.h")
-    assert _abi.DESIGN_SYMBOLS == ["aslr_design_descent"] and declared == set(_abi.DESIGN_SYMBOLS)
-    for other in (_abi.EXPORTED_SYMBOLS, _abi.EXTENSION_SYMBOLS, _abi.POLICY_SYMBOLS, _abi.MPC_PLANT_SYMBOLS,
-                  _abi.POOL_PARAMS_SYMBOLS, _abi.COV_SYMBOLS, _abi.PLANT_SENS_SYMBOLS):
-        assert not declared & set(other)
-    for header in OTHER_HEADERS:
-        assert not declared & _declared(header), header
-    assert _declared("aslr_to_amd.h") == set(_abi.EXPORTED_SYMBOLS)
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared <= defined, declared - defined
-    lib = _abi.load_library()
-    assert len(lib.aslr_design_descent.argtypes) == 4
-    assert _abi.ABI_VERSION == 5 and lib.aslr_abi_version() == 5
-    assert lib.aslr_sizeof(9) == -1
-    assert C.sizeof(_abi.Design) == 6 * 4 + 5 * 8 + 12 * C.sizeof(C.c_void_p)
 
 
 def test_a_null_handle_is_refused_by_name():

@@ -2,47 +2,12 @@
 the kernel against the definition of tests/_identify.py, and the reference loop on the oracle alone -- the conditions on the
 cases the GPU tests reuse (tests/test_gpu_identify.py), a joint held still, recovery of the true plant, noisy data."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import _identify as I
 from aslr_to_amd import _abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_identify_header_is_bound_and_exported():
-    """include/aslr_to_amd_identify.h declares exactly _abi.IDENTIFY_SYMBOLS, which the library defines; no other header and no
-    other symbol list knows the name; ABI version 5 and aslr_sizeof(9) == -1 are untouched; the ctypes mirror of
-    aslr_identify_t has the size of 4 int32, 7 doubles and 14 pointers; the debug exports are declared in no header"""
-    declared = _declared("aslr_to_amd_identify.h")
-    assert _abi.IDENTIFY_SYMBOLS == ["aslr_plant_identify"] and declared == set(_abi.IDENTIFY_SYMBOLS)
-    for other in (_abi.EXPORTED_SYMBOLS, _abi.EXTENSION_SYMBOLS, _abi.POLICY_SYMBOLS, _abi.MPC_PLANT_SYMBOLS, _abi.POOL_PARAMS_SYMBOLS,
-                  _abi.COV_SYMBOLS, _abi.PLANT_SENS_SYMBOLS, _abi.DESIGN_SYMBOLS, _abi.POLICY_ALL_SYMBOLS, _abi.MPC_PLANT_ALL_SYMBOLS,
-                  _abi.POLICY_NOISE_SYMBOLS):
-        assert not declared & set(other)
-    for header in os.listdir(INCLUDE):
-        if header != "aslr_to_amd_identify.h":
-            assert not {"aslr_plant_identify", "aslr_debug_identify_step", "aslr_debug_identify_normal"} & _declared(header), header
-    assert _declared("aslr_to_amd.h") == set(_abi.EXPORTED_SYMBOLS)
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared | {"aslr_debug_identify_step", "aslr_debug_identify_normal"} <= defined
-    lib = _abi.load_library()
-    assert len(lib.aslr_plant_identify.argtypes) == 3
-    assert _abi.ABI_VERSION == 5 and lib.aslr_abi_version() == 5
-    assert lib.aslr_sizeof(9) == -1
-    assert C.sizeof(_abi.Identify) == 4 * 4 + 7 * 8 + 14 * C.sizeof(C.c_void_p)
 
 
 def test_a_null_handle_is_refused_by_name():

@@ -2,9 +2,6 @@
 of the extension header, the helpers of tests/_mpc_plant.py pinned on the oracle alone, and the conditioning of the rows the
 GPU test of the whole loop uses (tests/test_gpu_mpc_plant.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,31 +10,6 @@ import _mpc_plant as mp
 import _policy as pol
 import test_mpc_host as H
 from aslr_to_amd import _abi, scenarios
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_mpc_plant_header_is_bound_and_exported():
-    """every aslr_ function include/aslr_to_amd_mpc_plant.h declares is in _abi.MPC_PLANT_SYMBOLS and defined in the library;
-    the other three headers and their symbol lists do not know it"""
-    declared = _declared("aslr_to_amd_mpc_plant.h")
-    assert declared and declared == set(_abi.MPC_PLANT_SYMBOLS)
-    for other in (_abi.EXPORTED_SYMBOLS, _abi.EXTENSION_SYMBOLS, _abi.POLICY_SYMBOLS):
-        assert not declared & set(other)
-    for header in ("aslr_to_amd.h", "aslr_to_amd_sens.h", "aslr_to_amd_policy.h"):
-        assert not declared & _declared(header), header
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared <= defined, declared - defined
-    lib = _abi.load_library()
-    for name in declared:
-        assert getattr(lib, name).argtypes is not None
 
 
 def test_a_null_handle_is_refused_by_name():

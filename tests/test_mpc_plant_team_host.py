@@ -3,9 +3,6 @@ include/aslr_to_amd_mpc_plant_all.h) on a CPU: the contract of the extension hea
 rows and one-step cases the GPU tests use (tests/_mpc_plant_team.py, tests/test_gpu_mpc_plant_team.py) on the oracle alone,
 with the reference of tests/_mpc_plant.py as it stands."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,42 +12,6 @@ import _mpc_plant_team as mt
 import _policy as pol
 import test_mpc_host as H
 from aslr_to_amd import _abi, scenarios
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-HEADER = "aslr_to_amd_mpc_plant_all.h"
-OTHER_LISTS = ("EXPORTED_SYMBOLS", "EXTENSION_SYMBOLS", "POLICY_SYMBOLS", "MPC_PLANT_SYMBOLS", "POOL_PARAMS_SYMBOLS",
-               "COV_SYMBOLS", "PLANT_SENS_SYMBOLS", "DESIGN_SYMBOLS", "POLICY_ALL_SYMBOLS")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_header_is_bound_and_exported():
-    """include/aslr_to_amd_mpc_plant_all.h declares exactly _abi.MPC_PLANT_ALL_SYMBOLS, which the library defines; no other
-    header and no other symbol list knows the name; aslr_to_amd_mpc_plant.h still declares exactly MPC_PLANT_SYMBOLS, the
-    base header's list, ABI version 5 and aslr_sizeof(9) == -1 are untouched; the binding takes the 10 arguments of
-    aslr_mpc_run_plant"""
-    declared = _declared(HEADER)
-    assert _abi.MPC_PLANT_ALL_SYMBOLS == ["aslr_mpc_run_plant_all"] and declared == set(_abi.MPC_PLANT_ALL_SYMBOLS)
-    for name in OTHER_LISTS:
-        assert not declared & set(getattr(_abi, name)), name
-    others = sorted(h for h in os.listdir(INCLUDE) if h.endswith(".h") and h != HEADER)
-    assert "aslr_to_amd.h" in others and "aslr_to_amd_mpc_plant.h" in others
-    for header in others:
-        assert not declared & _declared(header), header
-    assert _declared("aslr_to_amd.h") == set(_abi.EXPORTED_SYMBOLS)
-    assert _declared("aslr_to_amd_mpc_plant.h") == set(_abi.MPC_PLANT_SYMBOLS)
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared <= defined, declared - defined
-    lib = _abi.load_library()
-    assert len(lib.aslr_mpc_run_plant_all.argtypes) == 10
-    assert list(lib.aslr_mpc_run_plant_all.argtypes) == list(lib.aslr_mpc_run_plant.argtypes)
-    assert _abi.ABI_VERSION == 5 and lib.aslr_abi_version() == 5
-    assert lib.aslr_sizeof(9) == -1
 
 
 def test_a_null_handle_is_refused_by_name():

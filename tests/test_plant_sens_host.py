@@ -3,9 +3,6 @@ the extension header, the reference of tests/_plant_sens.py pinned on the oracle
 nonlinear closed loop of tests/_policy.py on perturbed plants, and against the adjoint reference of tests/_sensitivity.py
 where the loop is open -- and the conditioning of the inputs the GPU cases use (tests/test_gpu_plant_sens.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,35 +12,6 @@ import _plant_sens as ps
 import _policy as pol
 import _sensitivity as sens
 from aslr_to_amd import _abi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-OTHER_HEADERS = ("aslr_to_amd.h", "aslr_to_amd_sens.h", "aslr_to_amd_policy.h", "aslr_to_amd_mpc_plant.h",
-                 "aslr_to_amd_pool_params.h", "aslr_to_amd_cov.h")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_plant_sensitivity_header_is_bound_and_exported():
-    """every aslr_ function include/aslr_to_amd_plant_sens.h declares is in _abi.PLANT_SENS_SYMBOLS and defined in the
-    library; no other header and no other symbol list knows it; the ABI version is still 5"""
-    declared = _declared("aslr_to_amd_plant_sens.h")
-    assert declared == {"aslr_policy_plant_sensitivity"} and declared == set(_abi.PLANT_SENS_SYMBOLS)
-    for other in (_abi.EXPORTED_SYMBOLS, _abi.EXTENSION_SYMBOLS, _abi.POLICY_SYMBOLS, _abi.MPC_PLANT_SYMBOLS,
-                  _abi.POOL_PARAMS_SYMBOLS, _abi.COV_SYMBOLS):
-        assert not declared & set(other)
-    for header in OTHER_HEADERS:
-        assert not declared & _declared(header), header
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared <= defined, declared - defined
-    lib = _abi.load_library()
-    for name in declared:
-        assert len(getattr(lib, name).argtypes) == 12
-    assert _abi.ABI_VERSION == 5 and lib.aslr_abi_version() == 5
 
 
 def test_a_null_handle_is_refused_by_name():

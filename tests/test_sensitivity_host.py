@@ -6,9 +6,6 @@ Finite-difference error is not rounding error and has no a-priori bound, so the 
 tests were fixed by the procedure of their docstrings: the disagreement measured over a few relative steps on the oracle
 alone, the step where it is smallest, ten times that value.  Disagreement: max |a - b| / (1 + |b|) (_sensitivity.relerr)."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,8 +14,6 @@ import _sensitivity as sens
 import _traj_oracle
 from aslr_to_amd import _abi, scenarios
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SENS_HEADER = os.path.join(ROOT, "include", "aslr_to_amd_sens.h")
 
 # scenario -> (relative step, disagreement measured at it); the bound is ten times the measured value
 ROLLOUT_FD = {"two_dof_sea": (1e-5, 8.2e-8), "talos_arm_sea": (1e-4, 8.2e-8)}
@@ -67,26 +62,6 @@ def test_at_an_optimum_the_adjoint_gradient_is_the_gradient_of_the_optimal_cost(
         err = sens.relerr(want[k], fd[k])
         print("d%s: disagreement %.2e at step %.0e (bound %.1e)" % (k, err, sens.OPT_FD[0], 10 * sens.OPT_FD[1]))
         assert err < 10 * sens.OPT_FD[1], (k, err)
-
-
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    return set(re.findall(r"\b(aslr_[a-z0-9_]+)\s*\(", src))
-
-
-def test_the_extension_header_is_bound_and_exported():
-    """every aslr_ function include/aslr_to_amd_sens.h declares is in _abi.EXTENSION_SYMBOLS and defined in the library;
-    the base header and its symbol list do not know it"""
-    declared = _declared(SENS_HEADER)
-    assert declared and declared == set(_abi.EXTENSION_SYMBOLS)
-    assert not declared & set(_abi.EXPORTED_SYMBOLS)
-    assert not declared & _declared(os.path.join(ROOT, "include", "aslr_to_amd.h"))
-    nm = subprocess.run(["nm", "-D", "--defined-only", _abi.lib_path()], capture_output=True, text=True, check=True).stdout
-    defined = {l.split()[-1] for l in nm.splitlines() if l.split()[-2:-1] == ["T"]}
-    assert declared <= defined, declared - defined
-    lib = _abi.load_library()
-    for name in declared:
-        assert getattr(lib, name).argtypes is not None
 
 
 def test_a_null_handle_is_refused_by_name():
