@@ -74,8 +74,14 @@ ASLR_DEV void wait_vmcnt() {
 ASLR_DEV void wait_lgkmcnt0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
 // sin/cos for joint angles: Cody-Waite reduction by pi/2 (33 + 53 bits of pi/2, exact for
-// |x| < ~1e5) and the fdlibm kernel polynomials; < 1 ulp there.  Larger arguments take the library
-// path.  (ocml's sincos carries the full Payne-Hanek reduction inline: ~6x the instructions.)
+// |x| < ~1e5) and the fdlibm kernel polynomials.  Larger arguments take the library path.
+// (ocml's sincos carries the full Payne-Hanek reduction inline: ~6x the instructions.)
+// Accuracy below 1e5, measured on a host replica of this arithmetic (with and without FMA contraction) against
+// sinl / cosl at 14 million random arguments and 640 000 arguments at and next to every multiple of pi/2 and every
+// tie of rint: absolute error at most 1.20e-16 (1.73 ulp at generic arguments, so NOT below 1 ulp).  Next to a
+// multiple of pi/2, where the result is tiny, the absolute error is at most 6.5e-22 but the error in ulps is
+// unbounded (up to 4e9): the tail of the reduced argument is dropped.  tests/test_gpu_angle_range.py holds a single
+// sine / cosine to 2^-52 absolute on the device.
 ASLR_DEV void sincos_fast(double x, double *sn, double *cs) {
   if (!(fabs(x) < 1.0e5)) { sincos(x, sn, cs); return; }
   const double fn = rint(x * 6.36619772367581382433e-01);

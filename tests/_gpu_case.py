@@ -65,9 +65,10 @@ def random_candidate(low, seed):
     return xs, us
 
 
-def backward_inputs(oracle, low, seed, clip=None):
-    """-> xs, us, deriv, gaps.  clip = (lb, ub): the controls are clipped to the box before the oracle makes the records."""
-    xs, us = random_candidate(low, seed)
+def backward_inputs(oracle, low, seed, clip=None, candidate=None):
+    """-> xs, us, deriv, gaps.  clip = (lb, ub): the controls are clipped to the box before the oracle makes the records.
+    candidate = (xs, us): that candidate in place of random_candidate(low, seed); the gaps are drawn from the seed as ever."""
+    xs, us = random_candidate(low, seed) if candidate is None else candidate
     if clip is not None:
         us = np.clip(us, *clip)
     _, _, deriv = oracle.calc_diff(low, xs, us)
@@ -75,11 +76,11 @@ def backward_inputs(oracle, low, seed, clip=None):
     return xs, us, deriv, gaps
 
 
-def forward_inputs(oracle, low, sp, seed, fddp, feasible=None, full=False):
+def forward_inputs(oracle, low, sp, seed, fddp, feasible=None, full=False, candidate=None):
     """-> xs, us, K, k, gaps (full: also the oracle's backward pass the gains come from, with its unscaled Vxx).  fddp: the
     backward pass runs infeasible, so that its value function carries the gap terms; feasible: one flag per trajectory
-    instead."""
-    xs, us, deriv, gaps = backward_inputs(oracle, low, seed)
+    instead; candidate = (xs, us): as in backward_inputs."""
+    xs, us, deriv, gaps = backward_inputs(oracle, low, seed, candidate=candidate)
     if feasible is None:
         feasible = 0 if fddp else 1
     ref_b = oracle.backward_pass(low, sp, deriv, gaps, us, 1e-3, feasible)
