@@ -149,29 +149,36 @@ __global__ void __launch_bounds__(64) pool_refill_kernel(KArgs a, PoolDev pl, do
   }
 }
 
-// aslr_mpc_run: what lies between two solves of a receding-horizon run, for one trajectory per 64-thread block -- record the
-// step, take the plant's next state (XNEXT[0], evaluated by a one-knot calc launch just before) plus the disturbance, move
-// the plan one knot down, zero the gaps and gains as the refill above does for a fresh problem.
+// aslr_mpc_run, aslr_mpc_run_plant[_all]: what lies between two solves of a receding-horizon run, for one trajectory per
+// 64-thread block -- the step's statistics, the plant's next state x+, the plan moved `h` knots down, the gaps and gains
+// zeroed as the refill above does for a fresh problem.  Where the plant phase was a plant kernel's (mpc_plant_kernel,
+// mpc_plant_team_kernel: h knots applied and recorded there), x+ is the row it left behind its last record, `xplus`.  Where it
+// was a one-knot calc launch (xplus == nullptr, h = 1), the step is recorded here and x+ is XNEXT[0] plus the disturbance.
 struct MpcDev {
-  int32_t nx, nu;
+  int32_t nx, nu, h;
+  const double *xplus;          // [B][nx], or nullptr: the four below are read
   const double *dist;           // [B][nx] of this step, or nullptr
   double *x_rec, *u_rec;        // x_closed[s], u_closed[s]
-  double *x_last;               // x_closed[n_steps] in the last step, nullptr before
+  double *x_last;               // x_closed[n_steps] in the last step, nullptr before (and with xplus: the plant kernel wrote it)
   double *stat_f;               // [4][B] of this step
   int32_t *stat_i;              // [2][B]
 };
-// rows [0, n) of trajectory b's column of a [rows][B][w] array take the row above them.  A lane owns entry e = t w + i of
-// the column (a wave reads 64 / w whole rows, each w consecutive doubles); kStage chunks of 64 entries are loaded before any
-// of them is stored, with a barrier in between: a store of this round overwrites only rows this round or an earlier one has
-// read (this round reads entries below e0 + 64 kStage + w, the next one reads from e0 + 64 kStage + w on)
+// rows [0, n) of trajectory b's column of a [rows][B][w] array take row min(t + h, last), where last >= n is the row the
+// clamped tail repeats (T of xs with n = T, T - 1 of us with n = T - 1); h = 1, last = n is the plain shift by one row.  A
+// lane owns entry e = t w + i of the column (a wave reads 64 / w whole rows, each w consecutive doubles) and reads entry
+// e + h w, or its image in row `last` once t + h passes it; kStage chunks of 64 entries are loaded before any of them is
+// stored.  Within a round every load precedes the barrier and every store follows it.  Across rounds a store of this round
+// touches entries below e0 + 64 kStage only, and a later round reads (a) unclamped sources e' + h w with
+// e' >= e0 + 64 kStage, above everything stored so far, or (b) row `last`, which no round stores to (destinations end at row
+// n - 1 < last): the several destination rows of the tail all read that one untouched row.
 constexpr int kStage = 4;
-__device__ void shift_column(double *base, int n, int B, int b, int w, int tid) {
+__device__ void shift_column(double *base, int n, int B, int b, int w, int tid, int h, int last) {
   const int ne = n * w;
-  for (int e0 = 0; e0 < ne; e0 += 64 * kStage) { // (block-uniform trip count)
+  for (int e0 = 0; e0 < ne; e0 += 64 * kStage) { // (block-uniform trip count; none at n = 0, us at T = 1)
     double v[kStage] = {};
     ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
       const int e = e0 + 64 * k + tid, t = e / w, i = e - t * w;
-      if (e < ne) v[k] = base[((size_t)(t + 1) * B + b) * w + i];
+      if (e < ne) v[k] = base[((size_t)min(t + h, last) * B + b) * w + i];
     }
     __syncthreads();
     ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
@@ -189,82 +196,31 @@ __device__ void zero_column(double *base, int n, int B, int b, int w, int tid) {
 __global__ void __launch_bounds__(64) mpc_advance_kernel(KArgs a, MpcDev m) {
   const int b = blockIdx.x, tid = threadIdx.x, B = a.B, T = a.T, nx = m.nx, nu = m.nu;
   const size_t bx = (size_t)b * nx, bu = (size_t)b * nu; // knot 0 of trajectory b
-  // ---- record; the plant's next state (no addition without a disturbance: x + 0 is not x for x = -0) ----
+  // ---- the plant's next state: given, or record and form it (no addition without a disturbance: x + 0 is not x for x = -0) ----
   double xp = 0.0;
-  if (tid < nx) {
-    m.x_rec[bx + tid] = a.xs[bx + tid];
-    xp = a.xnext[bx + tid];
-    if (m.dist) xp += m.dist[bx + tid];
-  }
-  if (tid < nu) m.u_rec[bu + tid] = a.us[bu + tid];
-  if (tid < 4) {
-    const int row = tid == 0 ? ASLR_TF_COST : tid == 1 ? ASLR_TF_STOP : tid == 2 ? ASLR_TF_XREG : ASLR_TF_STEP;
-    m.stat_f[(size_t)tid * B + b] = a.traj_f[(size_t)row * B + b];
-  }
-  if (tid < 2) m.stat_i[(size_t)tid * B + b] = a.traj_i[(size_t)(tid == 0 ? ASLR_TI_ITER : ASLR_TI_STATUS) * B + b];
-  // ---- shift: xs[t] <- xs[t + 1] (t < T), us[t] <- us[t + 1] (t < T - 1); the last rows stay; then xs[0] <- x+ ----
-  shift_column(a.xs, T, B, b, nx, tid);
-  shift_column(a.us, T - 1, B, b, nu, tid);
-  __syncthreads(); // (knot 0 was written by the shift, possibly by other lanes)
-  if (tid < nx) {
-    a.xs[bx + tid] = xp;
-    const_cast<double *>(a.x0)[bx + tid] = xp;
-    if (m.x_last) m.x_last[bx + tid] = xp;
-  }
-  // ---- reset: the next solve starts from zeroed gaps and gains ----
-  zero_column(a.gaps, T + 1, B, b, nx, tid);
-  zero_column(a.vxxf, T + 1, B, b, nx, tid);
-  zero_column(a.kff, T, B, b, nu, tid);
-}
-
-// aslr_mpc_run_plant: the same between two solves when the plant phase was mpc_plant_kernel's -- `h` knots applied and
-// recorded there, the plant's state left in xplus ([B][nx]: the row of x_closed behind the step's last record) -- so what is
-// left here is the step's statistics, the shift by h rows and the reset.  A kernel of its own: mpc_advance_kernel and
-// shift_column stay the code aslr_mpc_run's bit-level tests pin.
-struct MpcHoldDev {
-  int32_t nx, nu, h;
-  const double *xplus;
-  double *stat_f;               // [4][B] of this step
-  int32_t *stat_i;              // [2][B]
-};
-// rows [0, n) of trajectory b's column take row min(t + h, last), where last >= n is the row the clamped tail repeats (T of
-// xs with n = T, T - 1 of us with n = T - 1).  shift_column's argument, restated for h rows: entry e = t w + i reads entry
-// e + h w, or its image in row `last` once t + h passes it.  Within a round every load precedes the barrier and every store
-// follows it.  Across rounds a store of this round touches entries below e0 + 64 kStage only, and a later round reads (a)
-// unclamped sources e' + h w with e' >= e0 + 64 kStage, above everything stored so far, or (b) row `last`, which no round
-// stores to (destinations end at row n - 1 < last): the several destination rows of the tail all read that one untouched row.
-__device__ void shift_column_hold(double *base, int n, int B, int b, int w, int tid, int h, int last) {
-  const int ne = n * w;
-  for (int e0 = 0; e0 < ne; e0 += 64 * kStage) { // (block-uniform trip count)
-    double v[kStage] = {};
-    ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
-      const int e = e0 + 64 * k + tid, t = e / w, i = e - t * w;
-      if (e < ne) v[k] = base[((size_t)min(t + h, last) * B + b) * w + i];
+  if (m.xplus) { // (block-uniform)
+    if (tid < nx) xp = m.xplus[bx + tid];
+  } else {
+    if (tid < nx) {
+      m.x_rec[bx + tid] = a.xs[bx + tid];
+      xp = a.xnext[bx + tid];
+      if (m.dist) xp += m.dist[bx + tid];
     }
-    __syncthreads();
-    ASLR_UNROLL for (int k = 0; k < kStage; ++k) {
-      const int e = e0 + 64 * k + tid, t = e / w, i = e - t * w;
-      if (e < ne) base[((size_t)t * B + b) * w + i] = v[k];
-    }
+    if (tid < nu) m.u_rec[bu + tid] = a.us[bu + tid];
   }
-}
-__global__ void __launch_bounds__(64) mpc_advance_hold_kernel(KArgs a, MpcHoldDev m) {
-  const int b = blockIdx.x, tid = threadIdx.x, B = a.B, T = a.T, nx = m.nx, nu = m.nu;
-  const size_t bx = (size_t)b * nx; // knot 0 of trajectory b
-  double xp = 0.0;
-  if (tid < nx) xp = m.xplus[bx + tid];
   if (tid < 4) {
     const int row = tid == 0 ? ASLR_TF_COST : tid == 1 ? ASLR_TF_STOP : tid == 2 ? ASLR_TF_XREG : ASLR_TF_STEP;
     m.stat_f[(size_t)tid * B + b] = a.traj_f[(size_t)row * B + b];
   }
   if (tid < 2) m.stat_i[(size_t)tid * B + b] = a.traj_i[(size_t)(tid == 0 ? ASLR_TI_ITER : ASLR_TI_STATUS) * B + b];
   // ---- shift: xs[t] <- xs[min(t + h, T)] (t < T), us[t] <- us[min(t + h, T - 1)] (t < T - 1); then xs[0] <- x+ ----
-  shift_column_hold(a.xs, T, B, b, nx, tid, m.h, T);
-  shift_column_hold(a.us, T - 1, B, b, nu, tid, m.h, T - 1);
+  shift_column(a.xs, T, B, b, nx, tid, m.h, T);
+  shift_column(a.us, T - 1, B, b, nu, tid, m.h, T - 1);
   __syncthreads(); // (knot 0 was written by the shift, possibly by other lanes)
   if (tid < nx) {
     a.xs[bx + tid] = xp;
     const_cast<double *>(a.x0)[bx + tid] = xp;
+    if (m.x_last) m.x_last[bx + tid] = xp;
   }
   // ---- reset: the next solve starts from zeroed gaps and gains ----
   zero_column(a.gaps, T + 1, B, b, nx, tid);
@@ -1451,34 +1407,61 @@ int aslr_solve(aslr_problem_t *p, const aslr_solver_params_t *sp, int32_t poll_e
   return aslr_finalize(p, stream);
 }
 
-int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, void *stream) {
-  if (int rc = mpc_refusals("aslr_mpc_run", p, sp, mpc)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t B = p->desc.B, nx = p->nx, nu = p->nu;
+// The control-step loop of aslr_mpc_run and aslr_mpc_run_plant[_all], behind the caller's own refusals.  Per step: the solve,
+// the plant phase `plant(ks, s)`, mpc_advance_kernel.  records: the phase is a plant kernel's -- it applies and records `hold`
+// knots and leaves x+ in the row of x_closed behind its last record; otherwise (hold = 1) it is a one-knot calc launch that
+// leaves XNEXT[0], and the advance kernel records the knot.  fn: the entry point a refusal names; overflow: its refusal of
+// a run whose applied knots, or the reference row after them, pass INT32_MAX (a format of one %s, fn).
+namespace {
+constexpr const char *kMpcRunOverflow = "%s: the reference row would overflow: reposition it with aslr_set_reference_path";
+constexpr const char *kMpcRunPlantOverflow = "%s: n_steps * hold, or the reference row after them, would overflow: reposition the row with aslr_set_reference_path";
+int mpc_loop(const char *fn, const char *overflow, aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, int hold,
+             bool records, hipStream_t st, const std::function<int(const KArgs &ks, int s)> &plant) {
+  const long long N = (long long)mpc->n_steps * hold;
   const int32_t row0 = p->k.ref_row0;
-  if (p->ref_path_set && row0 > INT32_MAX - mpc->n_steps - p->desc.T) return fail(ASLR_E_INVALID, "aslr_mpc_run: the reference row would overflow: reposition it with aslr_set_reference_path");
+  if (N > INT32_MAX || (p->ref_path_set && row0 > (long long)INT32_MAX - N - p->desc.T)) return fail(ASLR_E_INVALID, overflow, fn);
+  const size_t B = p->desc.B, nx = p->nx, nu = p->nu;
   for (int s = 0; s < mpc->n_steps; ++s) {
-    // with a reference path the window slides one row per control step: step s plans against rows row0 + s + t.  The
-    // offset travels by value in the argument block; nothing moves on the device
+    const size_t k0 = (size_t)s * hold; // the applied knot this step starts with
+    // with a reference path the window slides hold rows per control step: the solve of step s plans against rows
+    // row0 + k0 + t, its plant phase applies knot j against row row0 + k0 + j.  The offset travels by value in the argument
+    // block; nothing moves on the device
     KArgs ks = p->k;
-    if (p->ref_path_set) ks.ref_row0 = row0 + s;
-    KArgs plant = ks; // the plant: node 0's action model on knot 0 of every trajectory, through the handle's calc launcher
-    plant.seg_t1 = 0;
+    if (p->ref_path_set) ks.ref_row0 = row0 + (int32_t)k0;
     if (int rc = solve_unpolled(p, sp, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, ks, false, st)) return rc;
-    if (int rc = p->ks->calc(plant, false, 0, -1.0, st)) return rc;
-    MpcDev m;
-    m.nx = p->nx; m.nu = p->nu;
-    m.dist = mpc->disturbance ? mpc->disturbance + s * B * nx : nullptr;
-    m.x_rec = mpc->x_closed + s * B * nx;
-    m.u_rec = mpc->u_closed + s * B * nu;
-    m.x_last = s == mpc->n_steps - 1 ? mpc->x_closed + (s + 1) * B * nx : nullptr;
-    m.stat_f = mpc->stat_f + s * 4 * B;
-    m.stat_i = mpc->stat_i + s * 2 * B;
+    if (int rc = plant(ks, s)) return rc;
+    MpcDev m = {};
+    m.nx = p->nx; m.nu = p->nu; m.h = hold;
+    if (records) {
+      m.xplus = mpc->x_closed + (k0 + hold) * B * nx;
+    } else {
+      m.dist = mpc->disturbance ? mpc->disturbance + k0 * B * nx : nullptr;
+      m.x_rec = mpc->x_closed + k0 * B * nx;
+      m.u_rec = mpc->u_closed + k0 * B * nu;
+      m.x_last = s == mpc->n_steps - 1 ? mpc->x_closed + (k0 + hold) * B * nx : nullptr;
+    }
+    m.stat_f = mpc->stat_f + (size_t)s * 4 * B;
+    m.stat_i = mpc->stat_i + (size_t)s * 2 * B;
     hipLaunchKernelGGL(mpc_advance_kernel, dim3(p->desc.B), dim3(64), 0, st, p->k, m);
     HIP_TRY(hipGetLastError());
   }
-  if (p->ref_path_set) p->k.ref_row0 = row0 + mpc->n_steps; // (the next run, or a solve, carries on where this one ended)
+  if (p->ref_path_set) p->k.ref_row0 = row0 + (int32_t)N; // (the next run, or a solve, carries on where this one ended)
   return ASLR_OK;
+}
+// hold = 1 on the model itself: the plant is node 0's action model on knot 0 of every trajectory, through the handle's calc
+// launcher
+int mpc_run_calc(const char *fn, const char *overflow, aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, hipStream_t st) {
+  return mpc_loop(fn, overflow, p, sp, mpc, 1, false, st, [&](const KArgs &ks, int) {
+    KArgs plant = ks;
+    plant.seg_t1 = 0;
+    return p->ks->calc(plant, false, 0, -1.0, st);
+  });
+}
+} // namespace
+
+int aslr_mpc_run(aslr_problem_t *p, const aslr_solver_params_t *sp, const aslr_mpc_t *mpc, void *stream) {
+  if (int rc = mpc_refusals("aslr_mpc_run", p, sp, mpc)) return rc;
+  return mpc_run_calc("aslr_mpc_run", kMpcRunOverflow, p, sp, mpc, static_cast<hipStream_t>(stream));
 }
 
 // aslr_mpc_run_plant and aslr_mpc_run_plant_all (include/aslr_to_amd_mpc_plant_all.h): one body.  fn: the entry point a
@@ -1493,22 +1476,14 @@ int mpc_run_plant(const char *fn, bool arms, aslr_problem_t *p, const aslr_solve
   if (p->nj != 2 && !arms)
     return fail(ASLR_E_INVALID, "%s: the plant kernel is built for the nx = 8 sizes (2 joints), not for this %d-joint handle; aslr_mpc_run_plant_all serves every size", fn, p->nj);
   if (int rc = plant_arg_refusals(fn, p, plant_stiffness, plant_motor_inertia)) return rc;
-  const long long N = (long long)mpc->n_steps * hold;
-  const int32_t row0 = p->k.ref_row0;
-  if (N > INT32_MAX || (p->ref_path_set && row0 > (long long)INT32_MAX - N - T))
-    return fail(ASLR_E_INVALID, "%s: n_steps * hold, or the reference row after them, would overflow: reposition the row with aslr_set_reference_path", fn);
-  // nothing asked of the plant phase that the one-knot calc launch does not do: the launches of aslr_mpc_run
-  if (hold == 1 && !plant_stiffness && !plant_motor_inertia && !closed_cost && !failed_knot && !clamp) return aslr_mpc_run(p, sp, mpc, stream);
   hipStream_t st = static_cast<hipStream_t>(stream);
+  // nothing asked of the plant phase that the one-knot calc launch does not do: the launches of aslr_mpc_run
+  if (hold == 1 && !plant_stiffness && !plant_motor_inertia && !closed_cost && !failed_knot && !clamp)
+    return mpc_run_calc(fn, kMpcRunPlantOverflow, p, sp, mpc, st);
   const size_t B = p->desc.B, nx = p->nx, nu = p->nu;
   const bool table = p->ks->traj_params;
-  for (int s = 0; s < mpc->n_steps; ++s) {
-    const size_t k0 = (size_t)s * hold; // the applied knot this step starts with
-    // with a reference path the window slides hold rows per control step: the solve of step s plans against rows
-    // row0 + k0 + t, its plant phase applies knot j against row row0 + k0 + j (by value in the argument block, as aslr_mpc_run)
-    KArgs ks = p->k;
-    if (p->ref_path_set) ks.ref_row0 = row0 + (int32_t)k0;
-    if (int rc = solve_unpolled(p, sp, s == 0 ? mpc->first_maxiter : mpc->iters_per_step, ks, false, st)) return rc;
+  return mpc_loop(fn, kMpcRunPlantOverflow, p, sp, mpc, hold, true, st, [&](const KArgs &ks, int s) {
+    const size_t k0 = (size_t)s * hold;
     MpcPlantArgs pa;
     memset(&pa, 0, sizeof pa);
     pa.plant_stiffness = plant_stiffness; pa.plant_motor_inertia = plant_motor_inertia;
@@ -1518,17 +1493,8 @@ int mpc_run_plant(const char *fn, bool arms, aslr_problem_t *p, const aslr_solve
     pa.closed_cost = closed_cost; pa.failed_knot = failed_knot;
     pa.hold = hold; pa.k0 = (int32_t)k0; pa.first = s == 0; pa.clamp = clamp != 0;
     pa.table = table; pa.diagonal = table || plant_stiffness || plant_motor_inertia;
-    if (int rc = p->ks->mpc_plant(ks, p->limits, pa, st)) return rc;
-    MpcHoldDev m;
-    m.nx = p->nx; m.nu = p->nu; m.h = hold;
-    m.xplus = mpc->x_closed + (k0 + hold) * B * nx; // (the plant kernel left x+ in the row behind its last record)
-    m.stat_f = mpc->stat_f + (size_t)s * 4 * B;
-    m.stat_i = mpc->stat_i + (size_t)s * 2 * B;
-    hipLaunchKernelGGL(mpc_advance_hold_kernel, dim3(p->desc.B), dim3(64), 0, st, p->k, m);
-    HIP_TRY(hipGetLastError());
-  }
-  if (p->ref_path_set) p->k.ref_row0 = row0 + (int32_t)N;
-  return ASLR_OK;
+    return p->ks->mpc_plant(ks, p->limits, pa, st);
+  });
 }
 } // namespace
 

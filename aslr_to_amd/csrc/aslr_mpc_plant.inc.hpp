@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(64) mpc_plant_kernel(KArgs a, ModelLimits lim,
     else { ASLR_UNROLL for (int i = 0; i < NX; ++i) x[i] = xnext[i]; }
   }
   if (!on) return;
-  // x+: the row behind the last record (the next step's first record, or x_closed[N]); mpc_advance_hold_kernel reads it there
+  // x+: the row behind the last record (the next step's first record, or x_closed[N]); mpc_advance_kernel reads it there
   ASLR_UNROLL for (int p = 0; p < NX / 2; ++p)
     *reinterpret_cast<double2 *>(x_o + (size_t)hold * B * NX + 2 * p) = make_double2(x[2 * p], x[2 * p + 1]);
   if (pa.closed_cost) pa.closed_cost[b] = failed_here ? NAN : J; // (NaN stays NaN through the sums of the later steps)

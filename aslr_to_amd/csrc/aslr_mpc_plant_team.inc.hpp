@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(64) mpc_plant_team_kernel(KArgs a, ModelLimits
   }
   wave_sync(); // the state behind the last applied knot is written
   if (!on) return;
-  // x+: the row behind the last record (the next step's first record, or x_closed[N]); mpc_advance_hold_kernel reads it there
+  // x+: the row behind the last record (the next step's first record, or x_closed[N]); mpc_advance_kernel reads it there
   store_x(hold);
   if (c == 0) {
     if (pa.closed_cost) pa.closed_cost[b] = failed_here ? NAN : J; // (NaN stays NaN through the sums of the later steps)

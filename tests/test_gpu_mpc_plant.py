@@ -1,5 +1,6 @@
 """aslr_mpc_run_plant on the GPU (include/aslr_to_amd_mpc_plant.h; mpc_plant_kernel, csrc/aslr_mpc_plant.inc.hpp;
-mpc_advance_hold_kernel, csrc/aslr_abi.hip) against tests/_mpc_plant.py.
+mpc_advance_kernel, csrc/aslr_abi.hip) against tests/_mpc_plant.py; the assertion bodies shared with
+tests/test_gpu_mpc_plant_team.py are tests/_mpc_plant_gpu.py's.
 
 The oracle's solve returns no gains, so the call is held to its definition by induction: ONE control step against the
 definition (a twin handle's plain solve gives the plan and the gains; the plant phase is a numpy loop over the oracle's
@@ -12,7 +13,7 @@ import pytest
 import _ext_call as ext
 import _gpu_case as gc
 import _mpc_plant as mp
-import _parity
+import _mpc_plant_gpu as mg
 import _policy as pol
 import _ref_path
 import test_mpc_host as H
@@ -102,25 +103,7 @@ def test_one_control_step_is_the_definition(oracle, monkeypatch, key):
     if opt.get("plants_win"):   # the plants given on top of the table are what the kernel used, not the table's rows
         table = [mp.plant_phase(oracle, low, b, X[:, b], U[:, b], K[:, b], hold, None, None, dist[:, b], clamp) for b in range(B)]
         assert gc.relerr(np.stack([r["x"] for r in table], axis=1), want_x) > 1e-6
-    ext.same(got["x"][0], X[0], "x_closed[0] is XS[0]")
-    if not clamp:
-        ext.same(got["u"][0], U[0], "u_closed[0] is US[0]")
-    # the shift, exactly: rows of the twin's plan, the last one repeated; x+ in xs[0], X0 and x_closed[N]
-    xs_want, us_want = mp.shifted(X, U, hold, got["x"][hold])
-    XS, US = gc.to_np(e.region(_abi.R_XS)), gc.to_np(e.region(_abi.R_US))
-    ext.same(XS[1:], xs_want[1:], "XS after the shift, away from row 0")
-    ext.same(US, us_want, "US after the shift")
-    ext.same(XS[0], got["x"][hold], "xs[0] = x_closed[N]")
-    ext.same(gc.to_np(e.region(_abi.R_X0)), got["x"][hold], "X0 = x_closed[N]")
-    for rid in (_abi.R_KFF, _abi.R_GAPS, _abi.R_VXXF):
-        assert not gc.to_np(e.region(rid)).view(np.int64).any(), "region %d is not all zero" % rid
-    tf, ti = gc.to_np(twin.region(_abi.R_TRAJ_F)), gc.to_np(twin.region(_abi.R_TRAJ_I))
-    for i, row in enumerate((_abi.TF_COST, _abi.TF_STOP, _abi.TF_XREG, _abi.TF_STEP)):
-        ext.same(got["stat_f"][0, i], tf[row], "stat_f[%d]" % i)
-    ext.same(got["stat_i"][0, 0], ti[_abi.TI_ITER], "iterations")
-    ext.same(got["stat_i"][0, 1], ti[_abi.TI_STATUS], "status")
-    if getattr(low, "ref_path", None) is not None:
-        assert e.reference_row == row_before + hold
+    mg.one_step_leaves_the_shifted_plan(e, twin, low, got, X, U, hold, clamp, row_before)
 
 
 # ---- 2. the loop is its own step, bit for bit ----
@@ -132,27 +115,8 @@ def test_the_loop_is_its_own_step_bit_for_bit():
     sp = scenarios.solver_params(sc, solver="SolverFDDP", maxiter=400)
     pk, pb = mp.plants(low, seed=21, rng_range=0.3)
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n * hold, B, low.nx))
-    dev, twin = ext.fresh(low), ext.fresh(low)
-    one = _raw(dev, sp, n, first, per, hold, pk, pb, dist)
-    parts = [_raw(twin, sp, 1, first if s == 0 else per, per, hold, pk, pb, dist[s * hold:(s + 1) * hold]) for s in range(n)]
-    for s, p in enumerate(parts):
-        ext.same(one["x"][s * hold:(s + 1) * hold + 1], p["x"], "x_closed of step %d" % s)
-        ext.same(one["u"][s * hold:(s + 1) * hold], p["u"], "u_closed of step %d" % s)
-        ext.same(one["stat_f"][s], p["stat_f"][0], "stat_f of step %d" % s)
-        ext.same(one["stat_i"][s], p["stat_i"][0], "stat_i of step %d" % s)
-        assert (p["failed"] == -1).all()
-    assert (one["failed"] == -1).all()
-    for rid in ext.MPC_REGIONS:
-        gc.same_bits(dev.region(rid), twin.region(rid), "region %d" % rid)
+    dev, twin = mg.the_loop_is_its_own_step(_raw, low, sp, n, hold, first, per, pk, pb, dist, "two_dof_sea")
     assert dev.reference_row == twin.reference_row == n * hold
-    total = np.zeros(B)
-    for p in parts:
-        total = total + p["cost"]
-    err = np.abs(one["cost"] - total).max() / np.abs(total).max()
-    print("closed cost against the in-order sum of the four steps: %.2e relative" % err)
-    assert (np.abs(one["cost"] - total) <= 1e-12 * np.abs(total)).all()
-    assert np.abs(one["x"][1:] - one["x"][:-1]).max() > 0.0           # the states move
-    assert (one["stat_i"][:, 0].max(axis=1) >= 1).all()                # every step iterates on some trajectory
 
 
 def test_a_failing_trajectory_fails_alone_and_is_counted_in_applied_knots():
@@ -168,19 +132,10 @@ def test_a_failing_trajectory_fails_alone_and_is_counted_in_applied_knots():
     pk, pb = mp.plants(low, seed=21, rng_range=0.3)
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n * hold, 5, low.nx))
     base = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb, dist)
-    assert (base["failed"] == -1).all() and np.isfinite(base["cost"]).all()
     pushed, pb0 = np.array(dist), np.array(pb)
     pushed[0, 1], pushed[1, 3], pb0[4] = 1e31, 1e31, 0.0
     got = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb0, pushed)
-    np.testing.assert_array_equal(got["failed"], [-1, 1, -1, 2, 0])
-    assert np.isnan(got["cost"][[1, 3, 4]]).all()
-    ok = [0, 2]
-    for k in ("x", "u"):
-        ext.same(got[k][:, ok], base[k][:, ok], "%s of the other trajectories" % k)
-    for k in ("stat_f", "stat_i"):
-        ext.same(got[k][:, :, ok], base[k][:, :, ok], "%s of the other trajectories" % k)
-    ext.same(got["cost"][ok], base["cost"][ok], "closed cost of the other trajectories")
-    ext.same(got["x"][:2, 3], base["x"][:2, 3], "trajectory 3 before its push")   # (and up to its failure a trajectory is what it was)
+    mg.a_failing_trajectory_fails_alone(base, got, [-1, 1, -1, 2, 0], before=(2, 3))
 
 
 # ---- 3. the oracle loop at hold = 1 on a mismatched plant ----
@@ -188,25 +143,8 @@ def test_a_failing_trajectory_fails_alone_and_is_counted_in_applied_knots():
 def test_hold_one_matches_the_oracle_loop_on_a_mismatched_plant(oracle, row):
     """the rows tests/test_mpc_plant_host.py holds to the stability criterion; the bounds of
     test_gpu_mpc.test_closed_loop_matches_the_oracle_loop: iteration counts and status words exactly, states, controls and
-    the final plan within 1e-6 of the trajectory's scale, step costs within 1e-4 of max(1, |cost|)"""
-    ref, pk, pb = mp.loop_reference(oracle, row, H)
-    sc, sp, dist = H.parity_case(*row)
-    e = ext.fresh(scenarios.lower(sc))
-    r = e.mpc_run_plant(sp, H.N_STEPS, H.FIRST_MAXITER, H.ITERS_PER_STEP, 1, pk, pb, np.ascontiguousarray(dist.transpose(1, 0, 2)))
-    xc, uc = gc.to_np(r.xs_closed).transpose(1, 0, 2), gc.to_np(e.pad_u(r.us_closed)).transpose(1, 0, 2)
-    for s in range(H.N_STEPS):
-        np.testing.assert_array_equal(gc.to_np(r.iters)[:, s], ref["iters"][s], err_msg="iterations of step %d" % s)
-        _parity.assert_status_words_match(gc.to_np(r.status)[:, s], ref["status"][s])
-    scale = np.maximum(1.0, np.maximum(np.abs(ref["x_closed"]).max(axis=(0, 2)), np.abs(ref["u_closed"]).max(axis=(0, 2))))
-    dx = (np.abs(xc - ref["x_closed"]).max(axis=(0, 2)) / scale).max()
-    du = (np.abs(uc - ref["u_closed"]).max(axis=(0, 2)) / scale).max()
-    dc = (np.abs(gc.to_np(r.cost).T - ref["cost"]) / np.maximum(1.0, np.abs(ref["cost"]))).max()
-    dp = (np.abs(gc.to_np(e.region(_abi.R_XS)) - ref["xs"]).max(axis=(0, 2)) / scale).max()
-    dj = gc.relerr(gc.to_np(r.closed_cost), ref["closed_cost"])
-    print("%s %s: max rel |dx| %.2e |du| %.2e |dcost| %.2e, final plan %.2e, closed cost %.2e" % (row[0], row[1], dx, du, dc, dp, dj))
-    assert dx < 1e-6 and du < 1e-6 and dp < 1e-6, (dx, du, dp)
-    assert dc < 1e-4 and dj < 1e-4, (dc, dj)
-    assert (gc.to_np(r.failed_knot) == -1).all()
+    the final plan within 1e-6 of the trajectory's scale, step costs and the closed cost within 1e-4 of max(1, |cost|)"""
+    mg.hold_one_matches_the_oracle_loop(oracle, row, H)
 
 
 # ---- 4. delegation and neutrality ----
@@ -224,21 +162,7 @@ def test_defaults_are_aslr_mpc_run_bit_for_bit():
     sc = _table_case()
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc, maxiter=400)
-    n, first, per = 4, 6, 2
-    dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n, low.B, low.nx))
-    a, b = ext.fresh(low), ext.fresh(low)
-    got = _raw(a, sp, n, first, per, 1, None, None, dist, False, cost=False, failed=False)
-    r = b.mpc_run(sp, n, first, per, np.ascontiguousarray(dist.transpose(1, 0, 2)))
-    gc.sync()
-    ext.same(got["x"], gc.to_np(r.xs_closed).transpose(1, 0, 2), "x_closed")
-    ext.same(got["u"], gc.to_np(r.us_closed).transpose(1, 0, 2), "u_closed")
-    for i, k in enumerate(("cost", "stop", "x_reg", "step")):
-        ext.same(got["stat_f"][:, i], gc.to_np(getattr(r, k)).T, k)
-    ext.same(got["stat_i"][:, 0], gc.to_np(r.iters).T, "iters")
-    ext.same(got["stat_i"][:, 1], gc.to_np(r.status).T, "status")
-    for rid in ext.MPC_REGIONS:
-        gc.same_bits(a.region(rid), b.region(rid), "region %d" % rid)
-    assert int(r.iters[:, 0].min()) >= 1
+    mg.defaults_are_aslr_mpc_run(_raw, low, sp, 4, 6, 2)
 
 
 @pytest.mark.parametrize("case", ["sea", "vsa_table"])
@@ -249,20 +173,7 @@ def test_the_nominal_plant_is_neutral_and_a_plant_off_is_not(case):
     sc = _sea(65, 6) if case == "sea" else _table_case()
     low = scenarios.lower(sc)
     sp = scenarios.solver_params(sc, solver="SolverFDDP" if case == "sea" else "SolverBoxDDP", maxiter=400)
-    dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (1, low.B, low.nx))
-    nom = lambda f: np.array([pol.nominal_diag(low, b, f) for b in range(low.B)])
-    kn, bn = (nom("K") if low.dam == _abi.DAM_SEA else None), nom("B")
-    base = ext.fresh(low).mpc_run(sp, 1, 6, 2, np.ascontiguousarray(dist.transpose(1, 0, 2)))
-    want = gc.to_np(base.xs_closed).transpose(1, 0, 2)
-    got = _raw(ext.fresh(low), sp, 1, 6, 2, 1, kn, bn, dist)
-    scale = np.maximum(1.0, np.abs(want).max(axis=(0, 2)))
-    err = (np.abs(got["x"][1] - want[1]).max(axis=1) / scale).max()
-    print("%s: x_closed[1] with the nominal plant given against aslr_mpc_run: %.2e of scale" % (case, err))
-    assert err < 1e-11
-    ext.same(got["x"][0], want[0], "x_closed[0]")
-    assert np.isfinite(got["cost"]).all() and (got["failed"] == -1).all()
-    off = _raw(ext.fresh(low), sp, 1, 6, 2, 1, None if kn is None else 1.2 * kn, 1.2 * bn, dist)
-    assert np.abs(off["x"][1] - want[1]).max() > 1e-6
+    mg.the_nominal_plant_is_neutral_and_a_plant_off_is_not(_raw, low, sp, 6, 2, case)
 
 
 # ---- 5. schedule independence ----
@@ -273,19 +184,11 @@ def test_results_do_not_depend_on_subshards_or_batch():
     n, hold, first, per = 3, 2, 6, 2
     pk, pb = mp.plants(low, seed=21, rng_range=0.3)
     dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n * hold, 65, low.nx))
-    e1, e2 = ext.fresh(low), ext.fresh(low, 2)
-    r1, r2 = (_raw(e, sp, n, first, per, hold, pk, pb, dist) for e in (e1, e2))
-    ext.same(r1, r2, "two sub-shards")
-    for rid in ext.MPC_REGIONS:
-        gc.same_bits(e1.region(rid), e2.region(rid), "region %d with two sub-shards" % rid)
+    e1, r1 = mg.two_subshards_give_the_same_bits(_raw, low, sp, n, first, per, hold, pk, pb, dist)
     five = dict(sc, x0=sc["x0"][:5], frame_refs=sc["frame_refs"][:5])
     e3 = ext.fresh(scenarios.lower(five))
     r3 = _raw(e3, sp, n, first, per, hold, pk[:5], pb[:5], dist[:, :5])
-    cut = {k: (v[:5] if k in ("cost", "failed") else v[:, :5] if k in ("x", "u") else v[:, :, :5]) for k, v in r1.items()}
-    ext.same(cut, r3, "trajectories 0..4 of 65 in a batch of 5")
-    for rid in (_abi.R_XS, _abi.R_US):
-        gc.same_bits(e1.region(rid)[:, :5], e3.region(rid), "region %d of the first five trajectories" % rid)
-    assert (r1["stat_i"][:, 0].max(axis=1) >= 1).all()
+    mg.the_head_of_a_batch_is_a_batch_of_its_own(e1, r1, e3, r3, 5)
 
 
 # ---- 6. refusals ----

@@ -16,8 +16,8 @@ import pytest
 import _ext_call as ext
 import _gpu_case as gc
 import _mpc_plant as mp
+import _mpc_plant_gpu as mg
 import _mpc_plant_team as mt
-import _parity
 import _policy as pol
 import _policy_team as pt
 import _traj_oracle
@@ -80,25 +80,7 @@ def test_one_control_step_is_the_definition(oracle, key):
     if c["table"] and c["arrays"]:   # the plants given on top of the table are what the kernel used, not the table's rows
         table = mt.reference(oracle, c, X, U[..., :low.nu], K[..., :low.nu, :], plants=False)
         assert gc.relerr(table["x"], want["x"]) > 1e-6
-    ext.same(got["x"][0], X[0], "x_closed[0] is XS[0]")
-    if not clamp:
-        ext.same(got["u"][0], U[0], "u_closed[0] is US[0]")
-    # the shift, exactly: rows of the twin's plan, the last one repeated; x+ in xs[0], X0 and x_closed[N]
-    xs_want, us_want = mp.shifted(X, U, hold, got["x"][hold])
-    XS, US = gc.to_np(e.region(_abi.R_XS)), gc.to_np(e.region(_abi.R_US))
-    ext.same(XS[1:], xs_want[1:], "XS after the shift, away from row 0")
-    ext.same(US, us_want, "US after the shift")
-    ext.same(XS[0], got["x"][hold], "xs[0] = x_closed[N]")
-    ext.same(gc.to_np(e.region(_abi.R_X0)), got["x"][hold], "X0 = x_closed[N]")
-    for rid in (_abi.R_KFF, _abi.R_GAPS, _abi.R_VXXF):
-        assert not gc.to_np(e.region(rid)).view(np.int64).any(), "region %d is not all zero" % rid
-    tf, ti = gc.to_np(twin.region(_abi.R_TRAJ_F)), gc.to_np(twin.region(_abi.R_TRAJ_I))
-    for i, row in enumerate((_abi.TF_COST, _abi.TF_STOP, _abi.TF_XREG, _abi.TF_STEP)):
-        ext.same(got["stat_f"][0, i], tf[row], "stat_f[%d]" % i)
-    ext.same(got["stat_i"][0, 0], ti[_abi.TI_ITER], "iterations")
-    ext.same(got["stat_i"][0, 1], ti[_abi.TI_STATUS], "status")
-    if getattr(low, "ref_path", None) is not None:
-        assert e.reference_row == row_before + hold
+    mg.one_step_leaves_the_shifted_plan(e, twin, low, got, X, U, hold, clamp, row_before)
 
 
 # ---- 2. the loop is its own step, bit for bit ----
@@ -108,26 +90,7 @@ def test_the_loop_is_its_own_step_bit_for_bit(name):
     n, hold, first, per = 3, 2, 3, 2
     sc, low, sp = _arm(name, 9, 6)
     pk, pb, dist = _plants_and_noise(low, n * hold)
-    dev, twin = ext.fresh(low), ext.fresh(low)
-    one = _raw(dev, sp, n, first, per, hold, pk, pb, dist)
-    parts = [_raw(twin, sp, 1, first if s == 0 else per, per, hold, pk, pb, dist[s * hold:(s + 1) * hold]) for s in range(n)]
-    for s, p in enumerate(parts):
-        ext.same(one["x"][s * hold:(s + 1) * hold + 1], p["x"], "x_closed of step %d" % s)
-        ext.same(one["u"][s * hold:(s + 1) * hold], p["u"], "u_closed of step %d" % s)
-        ext.same(one["stat_f"][s], p["stat_f"][0], "stat_f of step %d" % s)
-        ext.same(one["stat_i"][s], p["stat_i"][0], "stat_i of step %d" % s)
-        assert (p["failed"] == -1).all()
-    assert (one["failed"] == -1).all()
-    for rid in ext.MPC_REGIONS:
-        gc.same_bits(dev.region(rid), twin.region(rid), "region %d" % rid)
-    total = np.zeros(low.B)
-    for p in parts:
-        total = total + p["cost"]
-    err = np.abs(one["cost"] - total).max() / np.abs(total).max()
-    print("%s: closed cost against the in-order sum of the three steps: %.2e relative" % (name, err))
-    assert (np.abs(one["cost"] - total) <= 1e-12 * np.abs(total)).all()
-    assert np.abs(one["x"][1:] - one["x"][:-1]).max() > 0.0           # the states move
-    assert (one["stat_i"][:, 0].max(axis=1) >= 1).all()                # every step iterates on some trajectory
+    mg.the_loop_is_its_own_step(_raw, low, sp, n, hold, first, per, pk, pb, dist, name)
 
 
 # ---- 3. the oracle loop at hold = 1 on a mismatched plant ----
@@ -136,45 +99,14 @@ def test_hold_one_matches_the_oracle_loop_on_a_mismatched_plant(oracle, row):
     """the rows tests/test_mpc_plant_team_host.py holds to the stability criterion; the bounds of
     test_gpu_mpc_plant's test of the same name: iteration counts and status words exactly, states, controls and the final
     plan within 1e-6 of the trajectory's scale, step costs and the closed cost within 1e-4 of max(1, |cost|)"""
-    ref, pk, pb = mp.loop_reference(oracle, row, H)
-    sc, sp, dist = H.parity_case(*row)
-    e = ext.fresh(scenarios.lower(sc))
-    r = e.mpc_run_plant(sp, H.N_STEPS, H.FIRST_MAXITER, H.ITERS_PER_STEP, 1, pk, pb, np.ascontiguousarray(dist.transpose(1, 0, 2)))
-    xc, uc = gc.to_np(r.xs_closed).transpose(1, 0, 2), gc.to_np(e.pad_u(r.us_closed)).transpose(1, 0, 2)
-    for s in range(H.N_STEPS):
-        np.testing.assert_array_equal(gc.to_np(r.iters)[:, s], ref["iters"][s], err_msg="iterations of step %d" % s)
-        _parity.assert_status_words_match(gc.to_np(r.status)[:, s], ref["status"][s])
-    scale = np.maximum(1.0, np.maximum(np.abs(ref["x_closed"]).max(axis=(0, 2)), np.abs(ref["u_closed"]).max(axis=(0, 2))))
-    dx = (np.abs(xc - ref["x_closed"]).max(axis=(0, 2)) / scale).max()
-    du = (np.abs(uc - ref["u_closed"]).max(axis=(0, 2)) / scale).max()
-    dc = (np.abs(gc.to_np(r.cost).T - ref["cost"]) / np.maximum(1.0, np.abs(ref["cost"]))).max()
-    dp = (np.abs(gc.to_np(e.region(_abi.R_XS)) - ref["xs"]).max(axis=(0, 2)) / scale).max()
-    dj = (np.abs(gc.to_np(r.closed_cost) - ref["closed_cost"]) / np.maximum(1.0, np.abs(ref["closed_cost"]))).max()
-    print("%s %s: max rel |dx| %.2e |du| %.2e |dcost| %.2e, final plan %.2e, closed cost %.2e" % (row[0], row[1], dx, du, dc, dp, dj))
-    assert dx < 1e-6 and du < 1e-6 and dp < 1e-6, (dx, du, dp)
-    assert dc < 1e-4 and dj < 1e-4, (dc, dj)
-    assert (gc.to_np(r.failed_knot) == -1).all()
+    mg.hold_one_matches_the_oracle_loop(oracle, row, H)
 
 
 # ---- 4. delegation and neutrality ----
 def test_defaults_are_aslr_mpc_run_bit_for_bit():
     """hold = 1 and nothing asked of the plant on a 7-joint handle: records, statistics and the regions of aslr_mpc_run"""
     sc, low, sp = _arm("talos_arm_sea", 9, 6)
-    n, first, per = 3, 3, 2
-    dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (n, low.B, low.nx))
-    a, b = ext.fresh(low), ext.fresh(low)
-    got = _raw(a, sp, n, first, per, 1, None, None, dist, False, cost=False, failed=False)
-    r = b.mpc_run(sp, n, first, per, np.ascontiguousarray(dist.transpose(1, 0, 2)))
-    gc.sync()
-    ext.same(got["x"], gc.to_np(r.xs_closed).transpose(1, 0, 2), "x_closed")
-    ext.same(got["u"], gc.to_np(b.pad_u(r.us_closed)).transpose(1, 0, 2), "u_closed")
-    for i, k in enumerate(("cost", "stop", "x_reg", "step")):
-        ext.same(got["stat_f"][:, i], gc.to_np(getattr(r, k)).T, k)
-    ext.same(got["stat_i"][:, 0], gc.to_np(r.iters).T, "iters")
-    ext.same(got["stat_i"][:, 1], gc.to_np(r.status).T, "status")
-    for rid in ext.MPC_REGIONS:
-        gc.same_bits(a.region(rid), b.region(rid), "region %d" % rid)
-    assert int(r.iters[:, 0].min()) >= 1
+    mg.defaults_are_aslr_mpc_run(_raw, low, sp, 3, 3, 2)
 
 
 @pytest.mark.parametrize("name", ["talos_arm_sea", "talos_arm_vsa"])
@@ -183,20 +115,7 @@ def test_the_nominal_plant_is_neutral_and_a_plant_off_is_not(name):
     the trajectory's scale of aslr_mpc_run's (the calc and the plant kernels need not share bits); with the plant 20 % off
     it moves by more than 1e-6."""
     sc, low, sp = _arm(name, 9, 6)
-    dist = np.random.default_rng(7).uniform(-1e-3, 1e-3, (1, low.B, low.nx))
-    nom = lambda f: np.array([pol.nominal_diag(low, b, f) for b in range(low.B)])
-    kn, bn = (nom("K") if low.dam == _abi.DAM_SEA else None), nom("B")
-    base = ext.fresh(low).mpc_run(sp, 1, 3, 2, np.ascontiguousarray(dist.transpose(1, 0, 2)))
-    want = gc.to_np(base.xs_closed).transpose(1, 0, 2)
-    got = _raw(ext.fresh(low), sp, 1, 3, 2, 1, kn, bn, dist)
-    scale = np.maximum(1.0, np.abs(want).max(axis=(0, 2)))
-    err = (np.abs(got["x"][1] - want[1]).max(axis=1) / scale).max()
-    print("%s: x_closed[1] with the nominal plant given against aslr_mpc_run: %.2e of scale" % (name, err))
-    assert err < 1e-11
-    ext.same(got["x"][0], want[0], "x_closed[0]")
-    assert np.isfinite(got["cost"]).all() and (got["failed"] == -1).all()
-    off = _raw(ext.fresh(low), sp, 1, 3, 2, 1, None if kn is None else 1.2 * kn, 1.2 * bn, dist)
-    assert np.abs(off["x"][1] - want[1]).max() > 1e-6
+    mg.the_nominal_plant_is_neutral_and_a_plant_off_is_not(_raw, low, sp, 3, 2, name)
 
 
 # ---- 5. schedule and position independence ----
@@ -206,11 +125,7 @@ def test_results_do_not_depend_on_subshards_or_batch():
     n, hold, first, per = 2, 2, 3, 2
     sc, low, sp = _arm("talos_arm_sea", 65, 4)
     pk, pb, dist = _plants_and_noise(low, n * hold)
-    e1, e2 = ext.fresh(low), ext.fresh(low, 2)
-    r1, r2 = (_raw(e, sp, n, first, per, hold, pk, pb, dist) for e in (e1, e2))
-    ext.same(r1, r2, "two sub-shards")
-    for rid in ext.MPC_REGIONS:
-        gc.same_bits(e1.region(rid), e2.region(rid), "region %d with two sub-shards" % rid)
+    mg.two_subshards_give_the_same_bits(_raw, low, sp, n, first, per, hold, pk, pb, dist)
     sc9, low9, _ = _arm("talos_arm_sea", 9, 4)
     pk9, pb9, dist9 = _plants_and_noise(low9, n * hold)
     e9 = ext.fresh(low9)
@@ -218,11 +133,7 @@ def test_results_do_not_depend_on_subshards_or_batch():
     three = dict(sc9, x0=sc9["x0"][:3], frame_refs=sc9["frame_refs"][:3])
     e3 = ext.fresh(scenarios.lower(three))
     r3 = _raw(e3, sp, n, first, per, hold, pk9[:3], pb9[:3], dist9[:, :3])
-    cut = {k: (v[:3] if k in ("cost", "failed") else v[:, :3] if k in ("x", "u") else v[:, :, :3]) for k, v in r9.items()}
-    ext.same(cut, r3, "trajectories 0..2 of 9 in a batch of 3")
-    for rid in (_abi.R_XS, _abi.R_US):
-        gc.same_bits(e9.region(rid)[:, :3], e3.region(rid), "region %d of the first three trajectories" % rid)
-    assert (r9["stat_i"][:, 0].max(axis=1) >= 1).all()
+    mg.the_head_of_a_batch_is_a_batch_of_its_own(e9, r9, e3, r3, 3)
 
 
 # ---- 6. a trajectory fails alone ----
@@ -237,19 +148,10 @@ def test_a_failing_trajectory_fails_alone_and_is_counted_in_applied_knots(name):
     sc, low, sp = _arm(name, 9, 4)
     pk, pb, dist = _plants_and_noise(low, n * hold)
     base = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb, dist)
-    assert (base["failed"] == -1).all() and np.isfinite(base["cost"]).all()
     pushed, pb0 = np.array(dist), np.array(pb)
     pushed[2, 2], pb0[4] = 1e31, 0.0
     got = _raw(ext.fresh(low), sp, n, 3, 2, hold, pk, pb0, pushed)
-    np.testing.assert_array_equal(got["failed"], [-1, -1, 3, -1, 0, -1, -1, -1, -1])
-    assert np.isnan(got["cost"][[2, 4]]).all()
-    ok = [0, 1, 3, 5, 6, 7, 8]
-    for k in ("x", "u"):
-        ext.same(got[k][:, ok], base[k][:, ok], "%s of the other trajectories" % k)
-    for k in ("stat_f", "stat_i"):
-        ext.same(got[k][:, :, ok], base[k][:, :, ok], "%s of the other trajectories" % k)
-    ext.same(got["cost"][ok], base["cost"][ok], "closed cost of the other trajectories")
-    ext.same(got["x"][:3, 2], base["x"][:3, 2], "trajectory 2 before its push")   # (and up to its failure a trajectory is what it was)
+    mg.a_failing_trajectory_fails_alone(base, got, [-1, -1, 3, -1, 0, -1, -1, -1, -1], before=(3, 2))
 
 
 # ---- 7. against the other kernel ----

@@ -12,7 +12,7 @@ With a sixth argument `plant` the comparison is instead between aslr_mpc_run and
 (include/aslr_to_amd_mpc_plant.h), alternating per repetition:
   (a) mpc:          Engine.mpc_run, n_steps control steps (the one-knot calc launch + mpc_advance_kernel between solves);
   (c) plant hold=1: Engine.mpc_run_plant with the motor-inertia plant given (within +-20 % of the model's) and the closed cost
-                    requested, n_steps control steps (mpc_plant_kernel + mpc_advance_hold_kernel between solves);
+                    requested, n_steps control steps (mpc_plant_kernel + mpc_advance_kernel between solves);
   (d) plant hold=4: the same with hold = 4 and n_steps / 4 control steps, reported per control step and per APPLIED KNOT.
 usage: python tools/time_mpc.py 4096 100 48 3 7 plant"""
 import json

@@ -9,7 +9,7 @@ synchronisation, median and spread of `reps` (default 7):
                     This is existing code; with the argument `mpc-only` the tool times nothing else, which is how the
                     baseline on an earlier commit is taken (the tool needs nothing newer than Engine.mpc_run then);
   (b) plant hold=1: Engine.mpc_run_plant with the motor-inertia plant given (within +-20 % of the model's) and the closed
-                    cost requested (mpc_plant_team_kernel + mpc_advance_hold_kernel between solves);
+                    cost requested (mpc_plant_team_kernel + mpc_advance_kernel between solves);
   (b0) the same with the model's own inertia as the plant: the closed loop and the solver's work of (a), so the difference
                     to (a) is the plant phase alone;
   (c) plant hold=4: the same with hold = 4 and n_steps / 4 control steps, per control step and per APPLIED KNOT.
