@@ -228,6 +228,7 @@ PROTOTYPES = {
     "aslr_to_amd_pool_params.h": {
         "aslr_solve_pool_params": (C.c_int, [_vp, _sp, C.POINTER(Pool), C.POINTER(PoolParams), _i, _i, _vp, C.POINTER(_i)])},
     "aslr_to_amd_cov.h": {"aslr_policy_covariance": (C.c_int, [_vp] * 9)},
+    "aslr_to_amd_lqg.h": {"aslr_policy_lqg": (C.c_int, [_vp, _i, C.POINTER(_i)] + [_vp] * 11)},
     "aslr_to_amd_plant_sens.h": {"aslr_policy_plant_sensitivity": (C.c_int, [_vp] * 12)},
     "aslr_to_amd_design.h": {"aslr_design_descent": (C.c_int, [_vp, _sp, C.POINTER(Design), _vp])},
     "aslr_to_amd_policy_all.h": {"aslr_policy_rollout_all": (C.c_int, _rollout)},
@@ -241,7 +242,7 @@ PROTOTYPES = {
 SYMBOL_LISTS = {
     "aslr_to_amd.h": "EXPORTED_SYMBOLS", "aslr_to_amd_sens.h": "EXTENSION_SYMBOLS", "aslr_to_amd_policy.h": "POLICY_SYMBOLS",
     "aslr_to_amd_mpc_plant.h": "MPC_PLANT_SYMBOLS", "aslr_to_amd_pool_params.h": "POOL_PARAMS_SYMBOLS",
-    "aslr_to_amd_cov.h": "COV_SYMBOLS", "aslr_to_amd_plant_sens.h": "PLANT_SENS_SYMBOLS",
+    "aslr_to_amd_cov.h": "COV_SYMBOLS", "aslr_to_amd_lqg.h": "LQG_SYMBOLS", "aslr_to_amd_plant_sens.h": "PLANT_SENS_SYMBOLS",
     "aslr_to_amd_design.h": "DESIGN_SYMBOLS", "aslr_to_amd_policy_all.h": "POLICY_ALL_SYMBOLS",
     "aslr_to_amd_mpc_plant_all.h": "MPC_PLANT_ALL_SYMBOLS", "aslr_to_amd_policy_noise.h": "POLICY_NOISE_SYMBOLS",
     "aslr_to_amd_identify.h": "IDENTIFY_SYMBOLS",

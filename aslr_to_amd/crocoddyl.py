@@ -300,6 +300,19 @@ class ShootingProblem(object):
             raise ValueError("policy_covariance: give xs, us and K together (or none of them: the engine's own policy)")
         return self._with_policy(xs, us, K, lambda: e.policy_covariance(sigma0, noise_var, keep_cov))
 
+    def policy_lqg(self, xs, us, K, meas_var, measured=None, sigma0=None, noise_var=None, keep_gains=False):
+        """First-order state and control covariance under output feedback, u_t = us_t - K_t eh_t with eh_t the estimate of the
+        Kalman filter for the measured state entries (Engine.policy_lqg; aslr_policy_lqg): xs, us, K as policy_rollout
+        takes them, all three None: the policy the engine holds.  The engine's own XS / US / KGAIN are put back afterwards.
+        -> engine.LqgResult.  This shard's trajectories only."""
+        e = self.engine
+        run = lambda: e.policy_lqg(meas_var, measured, sigma0, noise_var, keep_gains)
+        if xs is None and us is None and K is None:
+            return run()
+        if xs is None or us is None or K is None:
+            raise ValueError("policy_lqg: give xs, us and K together (or none of them: the engine's own policy)")
+        return self._with_policy(xs, us, K, run)
+
     def policy_plant_sensitivity(self, xs, us, K, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
         """First-order sensitivity of the closed loop under the policy u_t = us_t - K_t (x_t - xs_t) to the plant's spring
         stiffness and motor inertia (Engine.policy_plant_sensitivity; aslr_policy_plant_sensitivity): xs, us, K as
@@ -659,6 +672,17 @@ class SolverDDP(object):
         keep_cov.  Every model size, the 7-joint arms included.  One calcDiff sweep and one forward sweep on the device
         (aslr_policy_covariance, include/aslr_to_amd_cov.h); the box is not applied."""
         return self.problem.engine.policy_covariance(sigma0, noise_var, keep_cov)
+
+    def policy_lqg(self, meas_var, measured=None, sigma0=None, noise_var=None, keep_gains=False):
+        """policy_covariance for an arm that does not see its whole state: the state entries `measured` (None: the positions
+        q_l, q_m -- two encoders per joint) are read at every knot with noise of variance meas_var (a scalar, [ny] or [B, ny],
+        > 0), a time-varying Kalman filter linearised about the plan estimates the rest, and the Riccati gains of the last
+        solve act on the estimate.  sigma0 and noise_var as in policy_covariance.  -> engine.LqgResult: x_var [B, T+1, nx],
+        u_var [B, T, nu], est_var [B, T+1, nx] (what the filter does not know after each measurement), cov_final and
+        est_cov_final [B, nx, nx], cost_increase [B] and, with keep_gains, kalman_gain [B, T+1, nx, ny].  Every model size.
+        One calcDiff sweep and one forward sweep on the device (aslr_policy_lqg, include/aslr_to_amd_lqg.h); the box is not
+        applied."""
+        return self.problem.engine.policy_lqg(meas_var, measured, sigma0, noise_var, keep_gains)
 
     def policy_plant_sensitivity(self, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
         """Where the policy of the last solve (its xs, us and Riccati gains K) ends up on an arm whose springs or motors are

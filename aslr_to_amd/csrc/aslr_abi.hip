@@ -13,6 +13,7 @@
 #include "../../include/aslr_to_amd_mpc_plant.h"
 #include "../../include/aslr_to_amd_pool_params.h"
 #include "../../include/aslr_to_amd_cov.h"
+#include "../../include/aslr_to_amd_lqg.h"
 #include "../../include/aslr_to_amd_plant_sens.h"
 #include "../../include/aslr_to_amd_policy_all.h"
 #include "../../include/aslr_to_amd_policy_noise.h"
@@ -600,10 +601,10 @@ template <int NJ, int DAM, bool TP = false>
 constexpr KernelSet kernel_set() {
   constexpr KernelSet ks = {NJ, DAM, TP, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM, TP>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
                             launch_quasi_static<NJ, DAM, TP>, launch_forward<NJ, DAM, TP>, launch_backward<NJ, DAM, TP>, launch_adjoint<NJ, DAM>, launch_covariance<NJ, DAM>,
-                            launch_plant_sens<NJ, DAM>, policy_launcher<NJ, DAM, PolicyArgs>(), policy_launcher<NJ, DAM, PolicyNoiseArgs>(), mpc_plant_launcher<NJ, DAM>(),
+                            launch_lqg<NJ, DAM>, launch_plant_sens<NJ, DAM>, policy_launcher<NJ, DAM, PolicyArgs>(), policy_launcher<NJ, DAM, PolicyNoiseArgs>(), mpc_plant_launcher<NJ, DAM>(),
                             launch_identify_normal<NJ, DAM>, launch_identify_step<NJ, DAM>};
   static_assert(ks.calc && ks.dam_eval && ks.dam_residuals && ks.frame_placement && ks.quasi_static && ks.forward && ks.backward && ks.adjoint && ks.covariance &&
-                ks.plant_sens && ks.policy_rollout && ks.policy_rollout_noise && ks.mpc_plant && ks.identify_normal && ks.identify_step, "a row of kKernelSets lacks a launcher");
+                ks.lqg && ks.plant_sens && ks.policy_rollout && ks.policy_rollout_noise && ks.mpc_plant && ks.identify_normal && ks.identify_step, "a row of kKernelSets lacks a launcher");
   return ks;
 }
 constexpr KernelSet kKernelSets[] = {
@@ -1175,6 +1176,37 @@ int aslr_policy_covariance(aslr_problem_t *p, const double *sigma0, const double
   a.x_var = x_var; a.u_var = u_var; a.cov_final = cov_final; a.cov = cov; a.cost_increase = cost_increase;
   a.B = k.B; a.T = k.T;
   return p->ks->covariance(a, st);
+}
+
+int aslr_policy_lqg(aslr_problem_t *p, int32_t ny, const int32_t *meas_idx, const double *meas_var, const double *sigma0,
+                    const double *noise_var, double *x_var, double *u_var, double *est_var, double *cov_final,
+                    double *est_cov_final, double *kalman_gain, double *cost_increase, void *stream) {
+  if (!p) return no_handle("aslr_policy_lqg");
+  const KArgs &k = p->k;
+  const int nx = 4 * p->nj;
+  if (ny < 1 || ny > nx) return fail(ASLR_E_INVALID, "aslr_policy_lqg: ny is %d, must lie in [1, nx = %d]", ny, nx);
+  LqgArgs a;
+  memset(&a, 0, sizeof a);
+  for (int i = 0; i < ny; ++i) {
+    const int m = meas_idx ? meas_idx[i] : i;
+    if (m < 0 || m >= nx) return fail(ASLR_E_INVALID, "aslr_policy_lqg: meas_idx[%d] is %d, outside [0, nx = %d)", i, m, nx);
+    for (int l = 0; l < i; ++l)
+      if (a.meas[l] == m) return fail(ASLR_E_INVALID, "aslr_policy_lqg: meas_idx[%d] repeats index %d of meas_idx[%d]", i, m, l);
+    a.meas[i] = m;
+  }
+  if (!meas_var) return fail(ASLR_E_INVALID, "aslr_policy_lqg: meas_var is NULL");
+  if (!x_var && !u_var && !est_var && !cov_final && !est_cov_final && !kalman_gain && !cost_increase)
+    return fail(ASLR_E_INVALID, "aslr_policy_lqg: all seven outputs are NULL: nothing to compute");
+  if (!sigma0 && !noise_var)
+    return fail(ASLR_E_INVALID, "aslr_policy_lqg: sigma0 and noise_var are both NULL: nothing to propagate");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
+  a.deriv = k.deriv; a.kgain = k.kgain;
+  a.meas_var = meas_var; a.sigma0 = sigma0; a.noise_var = noise_var;
+  a.x_var = x_var; a.u_var = u_var; a.est_var = est_var; a.cov_final = cov_final; a.est_cov_final = est_cov_final;
+  a.kalman_gain = kalman_gain; a.cost_increase = cost_increase;
+  a.B = k.B; a.T = k.T; a.ny = ny;
+  return p->ks->lqg(a, st);
 }
 
 int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var, const double *motor_inertia_var,

@@ -155,7 +155,7 @@ struct SizeTraits {
   static constexpr bool boxddp_only = big_vsa;
   static constexpr int cost_tag = big_vsa ? 14 : NJ;      // instantiation tag of sum_cost_kernel / select_kernel
   static constexpr bool reg_column = !big_vsa;            // backward: the register-column kernel (ASLR_BWD_HS > 0) is built
-  // adjoint / covariance / tangent sweeps: one wave per block, a team of 8 (nx = 8) or 32 (nx = 28) lanes per trajectory
+  // adjoint / covariance / LQG / tangent sweeps: one wave per block, a team of 8 (nx = 8) or 32 (nx = 28) lanes per trajectory
   static constexpr int sweep_blocks(int B) { return NJ == 2 ? (B + 7) / 8 : (B + 1) / 2; }
 };
 
@@ -216,6 +216,19 @@ struct CovarianceArgs {
   int32_t B, T;
 };
 template <int NJ, int DAM> int launch_covariance(const CovarianceArgs &a, hipStream_t st);
+
+// Output-feedback covariance sweep (aslr_policy_lqg, aslr_lqg.inc.hpp): what lqg_kernel reads and writes, by value.  Like the
+// covariance sweep it reads no model constant: one launcher per size, shared by its two rows.
+struct LqgArgs {
+  const double *deriv, *kgain;
+  const double *meas_var;           // [B][ny]
+  const double *sigma0, *noise_var; // [B][nx][nx], [T][B][nx]; each nullable (zero)
+  double *x_var, *u_var, *est_var;  // [T+1][B][nx], [T][B][nu], [T+1][B][nx]; every output nullable
+  double *cov_final, *est_cov_final, *kalman_gain, *cost_increase; // [B][nx][nx], [B][nx][nx], [T+1][B][nx][ny], [B]
+  int32_t B, T, ny;
+  int32_t meas[ASLR_MAX_NX]; // the measured state entries: the first ny, distinct, each in [0, nx)
+};
+template <int NJ, int DAM> int launch_lqg(const LqgArgs &a, hipStream_t st);
 
 // Tangent sweep (aslr_policy_plant_sensitivity, aslr_plant_sens.inc.hpp): what plant_sens_kernel reads and writes, by value.
 // The parameters of a trajectory are taken as AdjointArgs has them, and the rows share the launcher in the same way.
@@ -348,6 +361,7 @@ struct KernelSet {
   decltype(&launch_backward<2, 0>) backward;
   decltype(&launch_adjoint<2, 0>) adjoint; // the extension calls: the TP rows share these with the plain rows
   decltype(&launch_covariance<2, 0>) covariance;
+  decltype(&launch_lqg<2, 0>) lqg;
   decltype(&launch_plant_sens<2, 0>) plant_sens;
   decltype(&launch_policy_rollout<2, 0, PolicyArgs>) policy_rollout;
   decltype(&launch_policy_rollout<2, 0, PolicyNoiseArgs>) policy_rollout_noise;

@@ -55,6 +55,14 @@ class PolicyCovarianceResult(_Result):
     cost_increase [B] and, when kept, cov [B, T+1, nx, nx] (every Sigma_t); cov is None otherwise."""
 
 
+class LqgResult(_Result):
+    """What Engine.policy_lqg returns: batch-major device tensors -- x_var [B, T+1, nx] (diagonal of Sigma_t = Xh_t + P_t), u_var
+    [B, T, nu] (diagonal of K Xh K^T; the models' own nu: padded controls are cut), est_var [B, T+1, nx] (diagonal of the
+    posterior error covariance P_t), cov_final [B, nx, nx] (Sigma_T), est_cov_final [B, nx, nx] (P_T), cost_increase [B] and,
+    when kept, kalman_gain [B, T+1, nx, ny] (L_t, columns in the order of `measured`; None otherwise); measured: the list of
+    measured state entries the call used."""
+
+
 class PlantSensitivityResult(_Result):
     """What Engine.policy_plant_sensitivity returns: batch-major device tensors -- dx_final_dstiffness,
     dx_final_dmotor_inertia [B, nx, nj] (dx_T/dK_j, dx_T/dB_j), dcost_dstiffness, dcost_dmotor_inertia [B, nj], x_var
@@ -503,6 +511,54 @@ class Engine(object):
         torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
         return PolicyCovarianceResult(x_var=xv.permute(1, 0, 2), u_var=self.cut_u(uv.permute(1, 0, 2)), cov_final=cf,
                                       cost_increase=ci, cov=None if cov is None else cov.permute(1, 0, 2, 3))
+
+    def policy_lqg(self, meas_var, measured=None, sigma0=None, noise_var=None, keep_gains=False):
+        """First-order state and control covariance under OUTPUT feedback: the policy in XS / US / KGAIN fed the estimate of
+        the time-varying Kalman filter for "the state entries `measured` are read at every knot with noise variance
+        meas_var", u_t = us_t - K_t eh_t, by one calcDiff sweep and one forward sweep (aslr_policy_lqg,
+        include/aslr_to_amd_lqg.h, which gives the recursion).  measured: distinct state indices in any order (None: the
+        nx / 2 positions q_l, q_m); meas_var: a scalar, [ny] or [B, ny], > 0, in the order of `measured`; sigma0 and noise_var
+        as policy_covariance takes them, at least one of the two.  -> LqgResult.  Side effects: those of calc_diff.  Before any
+        backward sweep K = 0: the filter is the same, the loop is open; the control box is not applied."""
+        torch = _torch()
+        B, T, nx, nu = self.B, self.T, self.nx, self.nu
+        if measured is None:
+            measured = range(nx // 2)
+        try:
+            m = [int(i) for i in measured]
+            whole = all(i == v for i, v in zip(m, measured))
+        except (TypeError, ValueError):
+            raise ValueError("measured must be a list of state indices")
+        if not whole or not 1 <= len(m) <= nx or min(m) < 0 or max(m) >= nx or len(set(m)) != len(m):
+            raise ValueError("measured must hold between 1 and nx = %d distinct state indices in [0, %d), not %s" % (nx, nx, list(measured)))
+        ny = len(m)
+        with torch.cuda.device(self.device):
+            r = self._bcast(meas_var, (B, ny), ((), (1,)), None,
+                            "meas_var must be a scalar or have shape [ny=%d] or [B=%d, ny], not {}" % (ny, B), say_given=True)
+            if r is None:
+                raise ValueError("meas_var is required: a scalar, [ny] or [B, ny]")
+            if not bool((r > 0).all()):
+                raise ValueError("meas_var must be positive")
+            s0 = self._bcast(sigma0, (B, nx, nx), ((1, 2),), None,
+                             "sigma0 must have shape [B=%d, nx=%d, nx] or [nx, nx], not {}" % (B, nx))
+            if s0 is not None:
+                if not torch.equal(s0, s0.transpose(1, 2)):
+                    raise ValueError("sigma0 must be symmetric")
+                if bool((torch.diagonal(s0, dim1=1, dim2=2) < 0).any()):
+                    raise ValueError("sigma0 has a negative variance on its diagonal")
+            w = self._bcast(noise_var, (B, T, nx), ((2,), (0, 2)), (1, 0, 2),
+                            "noise_var must have shape [B=%d, T=%d, nx=%d], [B, nx] or [nx], not {}" % (B, T, nx),
+                            nonneg="noise_var has a negative variance")
+        zeros = self._zeros
+        xv, uv, ev = zeros(T + 1, B, nx), zeros(T, B, nu), zeros(T + 1, B, nx)
+        cf, ef, ci = zeros(B, nx, nx), zeros(B, nx, nx), zeros(B)
+        kg = zeros(T + 1, B, nx, ny) if keep_gains else None
+        self._call("aslr_policy_lqg", ny, (C.c_int32 * ny)(*m), _ptr(r), _ptr(s0), _ptr(w), _ptr(xv), _ptr(uv), _ptr(ev), _ptr(cf),
+                   _ptr(ef), _ptr(kg), _ptr(ci), self._stream())
+        torch.cuda.synchronize(self.device)  # (the device copies of the inputs die on return)
+        return LqgResult(x_var=xv.permute(1, 0, 2), u_var=self.cut_u(uv.permute(1, 0, 2)), est_var=ev.permute(1, 0, 2),
+                         cov_final=cf, est_cov_final=ef, cost_increase=ci,
+                         kalman_gain=None if kg is None else kg.permute(1, 0, 2, 3), measured=m)
 
     def policy_plant_sensitivity(self, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
         """First-order sensitivity of the closed loop under the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), to
