@@ -13,7 +13,7 @@ import pytest
 import _covariance as cv
 import _ext_call as ext
 import _gpu_case as gc
-import _traj_oracle
+import _sweep_gpu as sw
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
@@ -36,23 +36,22 @@ def _raw(e, sigma0, noise_var, which=FIELDS, expect=_abi.OK):
     return ext.call(e, "aslr_policy_covariance", args, outs, expect)
 
 
+def _call(c, b=None):
+    """_raw with the case's sigma0 and noise_var bound (b: cut to trajectory b)"""
+    cut = slice(None) if b is None else slice(b, b + 1)
+    return lambda e, **kw: _raw(e, c["sigma0"][cut], c["noise_var"][cut], **kw)
+
+
 @pytest.fixture(scope="module")
 def cases(oracle):
     """the seeded inputs of every case, built once (the open-loop candidate comes from the oracle) and never changed"""
-    return {key: cv.case(oracle, key) for key in cv.CASES}
+    return sw.make_cases(oracle, cv.CASES)
 
 
 @pytest.fixture(scope="module")
 def loaded(cases):
-    """key -> (engine with the candidate and its gains in place, the device's K), made on first use and shared: the call
-    under test changes nothing it reads"""
-    made = {}
-
-    def get(key):
-        if key not in made:
-            made[key] = ext.with_gains(cases[key])
-        return made[key]
-    return get
+    """key -> (engine with the candidate and its gains in place, the device's K): tests/_sweep_gpu.make_loaded"""
+    return sw.make_loaded(cases)
 
 
 @pytest.mark.parametrize("which", sorted(cv.COMBOS))
@@ -63,20 +62,12 @@ def test_kernel_matches_the_definition(oracle, cases, loaded, key, which):
     s0, w = cv.combo(c, which)
     got = _raw(e, s0, w)
     want = cv.expected(oracle, c["low"], c["xs"], c["us"], K, s0, w)
-    for k in FIELDS:
-        assert got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
-        err = cv.traj_relerr(got[k], want[k])
-        print("%s %s %s: %.2e (max |reference| %.2e)" % (key, which, k, err, np.abs(want[k]).max()))
-        assert err < 1e-9, (k, err)
+    sw.matches(got, want, FIELDS, "%s %s" % (key, which))
     assert np.abs(want["cost_increase"]).min() > 1e-6
     if not (c["low"].T == 1 and s0 is None):   # (T = 1 without sigma0: Sigma_0 = 0, so U_0 = 0 on both sides)
         assert np.abs(want["u_var"]).max() > 1e-6
-    if key in ("vsa_box", "arm_vsa"):   # gains after a BoxDDP backward sweep: some rows are zero, and so is their variance
-        zero = np.abs(K).max(axis=-1) == 0.0
-        assert zero.any() and not zero.all()
-        assert (got["u_var"].transpose(1, 0, 2)[zero] == 0.0).all()
-    if key == "nu1":
-        assert (got["u_var"][..., 1] == 0.0).all()   # the padded control
+    sw.zero_gain_rows(key, K, got)
+    sw.padded_control(key, got)
     if getattr(c["low"], "ref_path", None) is not None:   # ... and the path is what the records were evaluated against
         plain = scenarios.lower(dict(c["sc"], ref_path=None))
         assert cv.traj_relerr(cv.expected(oracle, plain, c["xs"], c["us"], K, s0, w)["cost_increase"], want["cost_increase"]) > 1e-6
@@ -88,26 +79,17 @@ def test_every_output_is_optional(cases, loaded, key):
     c = cases[key]
     e, _ = loaded(key)
     full = _raw(e, c["sigma0"], c["noise_var"])
-    for k in FIELDS:
-        ext.same(_raw(e, c["sigma0"], c["noise_var"], which=(k,)), {k: full[k]}, "alone")
+    sw.each_output_alone(lambda **kw: _call(c)(e, **kw), full)
     pair = _raw(e, c["sigma0"], c["noise_var"], which=("x_var", "cov_final"))   # (no control terms: the other kernel branch)
     ext.same(pair, {k: full[k] for k in pair}, "states only")
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_sea"])
 def test_a_trajectory_does_not_depend_on_where_it_sits(cases, loaded, key):
-    """trajectory B - 1 of the batch (the one behind the last full wave of teams) against the same trajectory alone in a
-    B = 1 engine (tests/_traj_oracle.single: its row of the table in the models) with the batch's gains uploaded: bit for
-    bit"""
+    """trajectory B - 1 of the batch against the same trajectory alone in a B = 1 engine, bit for bit (sw.trajectory_alone)"""
     c = cases[key]
-    low = c["low"]
     e, K = loaded(key)
-    batch = _raw(e, c["sigma0"], c["noise_var"])
-    b = low.B - 1
-    e1 = gc.engine(_traj_oracle.single(low, b))
-    gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
-    alone = _raw(e1, c["sigma0"][b:b + 1], c["noise_var"][b:b + 1])
-    ext.same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
+    sw.trajectory_alone(c, e, K, _call(c), lambda b: _call(c, b))
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_vsa"])
@@ -139,20 +121,7 @@ def test_the_outputs_are_consistent_with_each_other(oracle, cases, loaded, key):
 def test_the_call_has_the_side_effects_of_calc_diff(cases):
     """3 iterations, the call (all inputs, all outputs), 3 more iterations: XS, US, TRAJ_F and TRAJ_I are, bit for bit, those
     of 3 iterations, aslr_calc_diff, 3 iterations on a fresh engine"""
-    c = cases["vsa_box"]
-    low, sp = c["low"], c["sp"]
-    runs = []
-    for call in (lambda e: _raw(e, c["sigma0"], c["noise_var"]), lambda e: e.calc_diff()):
-        e = gc.engine(low)
-        e.set_candidate(None, None)
-        e.iterate_n(sp, True, 3)
-        call(e)
-        e.iterate_n(sp, False, 3)
-        gc.sync()
-        runs.append(gc.solution(e))
-    assert (runs[1]["traj_i"][_abi.TI_ITER] > 3).any()
-    for k in runs[0]:
-        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)
+    sw.side_effects_of_calc_diff(cases["vsa_box"], _call(cases["vsa_box"]))
 
 
 def test_refusals_write_nothing_and_leave_a_live_handle(cases, loaded):
@@ -197,13 +166,7 @@ def test_python_facade(cases):
         gc.same_bits(getattr(one, k), getattr(tiled, k), "broadcast [nx, nx] and [nx]: %s" % k)
         gc.same_bits(getattr(per_b, k), getattr(tiled_b, k), "broadcast [B, nx]: %s" % k)
     # ... at a stored policy, through the problem: the same bits, and the engine's own policy is back afterwards
-    xs, us, K = (e.region(r).clone() for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN))
-    for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
-        e.region(r).fill_(0.25)
-    again = problem.policy_covariance(xs.permute(1, 0, 2), us.permute(1, 0, 2), K.permute(1, 0, 2, 3), s0, w)
-    gc.same_bits(again.cost_increase, res.cost_increase, "the stored policy given explicitly")
-    for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
-        assert (e.region(r) == 0.25).all()
+    sw.stored_policy_round_trip(problem, e, lambda p, *policy: p.policy_covariance(*policy, s0, w), {"cost_increase": res.cost_increase})
     # refusals of the facade
     skew = np.array(s0)
     skew[1, 2, 5] += 1e-9
@@ -216,10 +179,4 @@ def test_python_facade(cases):
     with pytest.raises(_abi.AslrError, match="aslr_policy_covariance:"):
         solver.policy_covariance()
     # padded controls are cut
-    psc = cases["nu1"]["sc"]
-    pp = crocoddyl.ShootingProblem(psc["x0"], psc["running"], psc["terminal"], frame_refs=psc["frame_refs"])
-    ps = crocoddyl.SolverDDP(pp)
-    ps.solve([], [], 3)
-    r1 = ps.policy_covariance(np.eye(8))
-    gc.sync()
-    assert tuple(r1.u_var.shape) == (3, cases["nu1"]["low"].T, 1) and tuple(r1.x_var.shape) == (3, cases["nu1"]["low"].T + 1, 8)
+    sw.padded_controls_are_cut(cases, lambda solver: solver.policy_covariance(np.eye(8)))

@@ -15,7 +15,7 @@ import _covariance as cv
 import _ext_call as ext
 import _gpu_case as gc
 import _lqg as lq
-import _traj_oracle
+import _sweep_gpu as sw
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
@@ -44,31 +44,27 @@ def _raw(e, m, r, sigma0, noise_var, which=FIELDS, expect=_abi.OK, ny=None, null
 def cases(oracle):
     """the seeded inputs of every case, built once (the open-loop candidate and its records come from the oracle) and never
     changed"""
-    made = {}
-    for key in cv.CASES:
-        c = cv.case(oracle, key)
-        c["deriv"] = cv.records(oracle, c["low"], c["xs"], c["us"])
-        made[key] = c
-    return made
+    return sw.make_cases(oracle, cv.CASES, lambda c: c.update(deriv=cv.records(oracle, c["low"], c["xs"], c["us"])))
 
 
 @pytest.fixture(scope="module")
 def loaded(cases):
-    """key -> (engine with the candidate and its gains in place, the device's K), made on first use and shared: the call
-    under test changes nothing it reads"""
-    made = {}
-
-    def get(key):
-        if key not in made:
-            made[key] = ext.with_gains(cases[key])
-        return made[key]
-    return get
+    """key -> (engine with the candidate and its gains in place, the device's K): tests/_sweep_gpu.make_loaded"""
+    return sw.make_loaded(cases)
 
 
 def _inputs(c, which="default"):
     """-> the measured entries of the set, the seeded meas_var for them"""
     m = lq.measured(c["low"].nx, which)
     return m, lq.meas_var(c["low"].B, len(m), c["key"])
+
+
+def _call(c, b=None, which="default"):
+    """_raw with the measured entries of the set `which`, their meas_var and the case's sigma0 and noise_var bound (b: cut
+    to trajectory b)"""
+    cut = slice(None) if b is None else slice(b, b + 1)
+    m, r = _inputs(c, which)
+    return lambda e, **kw: _raw(e, m, r[cut], c["sigma0"][cut], c["noise_var"][cut], **kw)
 
 
 @pytest.mark.parametrize("which", lq.SETS)
@@ -82,21 +78,13 @@ def test_kernel_matches_the_definition(cases, loaded, key, which):
         s0, w = cv.combo(c, combo)
         got = _raw(e, m, r, s0, w)
         want = lq.propagate(low, c["deriv"], K, m, r, s0, w)
-        for k in FIELDS:
-            assert got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
-            err = cv.traj_relerr(got[k], want[k])
-            print("%s %s %s %s: %.2e (max |reference| %.2e)" % (key, which, combo, k, err, np.abs(want[k]).max()))
-            assert err < 1e-9, (k, err)
+        sw.matches(got, want, FIELDS, "%s %s %s" % (key, which, combo))
         assert np.abs(want["cost_increase"]).min() > 1e-6 and np.abs(want["est_var"]).max() > 1e-6
         assert np.abs(want["kalman_gain"][:, 1:]).max() > 1e-6
         if s0 is not None:   # (without sigma0 Xh_0 = 0, and at T = 1 that is the only knot with a control)
             assert np.abs(want["u_var"]).max() > 1e-6
-        if key in ("vsa_box", "arm_vsa"):   # gains after a BoxDDP backward sweep: some rows are zero, and so is their variance
-            zero = np.abs(K).max(axis=-1) == 0.0
-            assert zero.any() and not zero.all()
-            assert (got["u_var"].transpose(1, 0, 2)[zero] == 0.0).all()
-        if key == "nu1":
-            assert (got["u_var"][..., 1] == 0.0).all()   # the padded control
+        sw.zero_gain_rows(key, K, got)
+        sw.padded_control(key, got)
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_vsa"])
@@ -107,8 +95,7 @@ def test_every_output_is_optional(cases, loaded, key):
     e, _ = loaded(key)
     m, r = _inputs(c, "odd")
     full = _raw(e, m, r, c["sigma0"], c["noise_var"])
-    for k in FIELDS:
-        ext.same(_raw(e, m, r, c["sigma0"], c["noise_var"], which=(k,)), {k: full[k]}, "alone")
+    sw.each_output_alone(lambda **kw: _call(c, which="odd")(e, **kw), full)
     for pair in (("est_var", "kalman_gain"), ("x_var", "cov_final")):
         got = _raw(e, m, r, c["sigma0"], c["noise_var"], which=pair)
         ext.same(got, {k: full[k] for k in pair}, "a pair without the control terms")
@@ -116,19 +103,10 @@ def test_every_output_is_optional(cases, loaded, key):
 
 @pytest.mark.parametrize("key", ["sea", "arm_sea"])
 def test_a_trajectory_does_not_depend_on_where_it_sits(cases, loaded, key):
-    """trajectory B - 1 of the batch (the one behind the last full wave of teams) against the same trajectory alone in a
-    B = 1 engine (tests/_traj_oracle.single: its row of the table in the models) with the batch's gains uploaded: bit for
-    bit"""
+    """trajectory B - 1 of the batch against the same trajectory alone in a B = 1 engine, bit for bit (sw.trajectory_alone)"""
     c = cases[key]
-    low = c["low"]
     e, K = loaded(key)
-    m, r = _inputs(c)
-    batch = _raw(e, m, r, c["sigma0"], c["noise_var"])
-    b = low.B - 1
-    e1 = gc.engine(_traj_oracle.single(low, b))
-    gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
-    alone = _raw(e1, m, r[b:b + 1], c["sigma0"][b:b + 1], c["noise_var"][b:b + 1])
-    ext.same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
+    sw.trajectory_alone(c, e, K, _call(c), lambda b: _call(c, b))
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_vsa"])
@@ -182,21 +160,7 @@ def test_the_stored_matrices_are_symmetric_bit_for_bit(cases, loaded, key):
 def test_the_call_has_the_side_effects_of_calc_diff(cases):
     """3 iterations, the call (all inputs, all outputs), 3 more iterations: XS, US, TRAJ_F and TRAJ_I are, bit for bit, those
     of 3 iterations, aslr_calc_diff, 3 iterations on a fresh engine"""
-    c = cases["vsa_box"]
-    low, sp = c["low"], c["sp"]
-    m, r = _inputs(c)
-    runs = []
-    for call in (lambda e: _raw(e, m, r, c["sigma0"], c["noise_var"]), lambda e: e.calc_diff()):
-        e = gc.engine(low)
-        e.set_candidate(None, None)
-        e.iterate_n(sp, True, 3)
-        call(e)
-        e.iterate_n(sp, False, 3)
-        gc.sync()
-        runs.append(gc.solution(e))
-    assert (runs[1]["traj_i"][_abi.TI_ITER] > 3).any()
-    for k in runs[0]:
-        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)
+    sw.side_effects_of_calc_diff(cases["vsa_box"], _call(cases["vsa_box"]))
 
 
 def test_refusals_write_nothing_and_leave_a_live_handle(cases, loaded):
@@ -263,13 +227,7 @@ def test_python_facade(cases):
         for k in fields:
             gc.same_bits(getattr(short, k), getattr(tiled, k), "broadcast %s: %s" % (what, k))
     # ... at a stored policy, through the problem: the same bits, and the engine's own policy is back afterwards
-    xs, us, K = (e.region(rid).clone() for rid in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN))
-    for rid in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
-        e.region(rid).fill_(0.25)
-    again = problem.policy_lqg(xs.permute(1, 0, 2), us.permute(1, 0, 2), K.permute(1, 0, 2, 3), r, m, s0, w)
-    gc.same_bits(again.cost_increase, res.cost_increase, "the stored policy given explicitly")
-    for rid in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
-        assert (e.region(rid) == 0.25).all()
+    sw.stored_policy_round_trip(problem, e, lambda p, *policy: p.policy_lqg(*policy, r, m, s0, w), {"cost_increase": res.cost_increase})
     # refusals of the facade
     skew = np.array(s0)
     skew[1, 2, 5] += 1e-9
@@ -288,10 +246,4 @@ def test_python_facade(cases):
     with pytest.raises(_abi.AslrError, match="aslr_policy_lqg:"):
         solver.policy_lqg(r, m)
     # padded controls are cut
-    psc = cases["nu1"]["sc"]
-    pp = crocoddyl.ShootingProblem(psc["x0"], psc["running"], psc["terminal"], frame_refs=psc["frame_refs"])
-    ps = crocoddyl.SolverDDP(pp)
-    ps.solve([], [], 3)
-    r1 = ps.policy_lqg(0.5, sigma0=np.eye(8))
-    gc.sync()
-    assert tuple(r1.u_var.shape) == (3, cases["nu1"]["low"].T, 1) and tuple(r1.x_var.shape) == (3, cases["nu1"]["low"].T + 1, 8)
+    sw.padded_controls_are_cut(cases, lambda solver: solver.policy_lqg(0.5, sigma0=np.eye(8)))

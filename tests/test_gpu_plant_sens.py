@@ -16,6 +16,7 @@ import _gpu_case as gc
 import _plant_sens as ps
 import _policy as pol
 import _sensitivity as sens
+import _sweep_gpu as sw
 import _traj_oracle
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
@@ -50,28 +51,24 @@ def _raw(e, stiffness_var, motor_inertia_var, which=None, expect=_abi.OK):
     return ext.call(e, "aslr_policy_plant_sensitivity", args + [outs.get(k) for k in FIELDS] + [e._stream()], outs, expect)
 
 
+def _call(c, b=None):
+    """_raw with the case's two variances bound (b: cut to trajectory b)"""
+    cut = slice(None) if b is None else slice(b, b + 1)
+    vk, vb = c["var"]
+    return lambda e, **kw: _raw(e, None if vk is None else vk[cut], vb[cut], **kw)
+
+
 @pytest.fixture(scope="module")
 def cases(oracle):
     """the seeded inputs of every case, built once (the open-loop candidate comes from the oracle) and never changed; var:
     the seeded variances (stiffness or None, motor inertia)"""
-    made = {}
-    for key in ps.CASES:
-        made[key] = cv.case(oracle, key)
-        made[key]["var"] = ps.variances(made[key]["low"], VAR_SEED)
-    return made
+    return sw.make_cases(oracle, ps.CASES, lambda c: c.update(var=ps.variances(c["low"], VAR_SEED)))
 
 
 @pytest.fixture(scope="module")
 def loaded(cases):
-    """key -> (engine with the candidate and its gains in place, the device's K), made on first use and shared: the call
-    under test changes nothing it reads"""
-    made = {}
-
-    def get(key):
-        if key not in made:
-            made[key] = ext.with_gains(cases[key])
-        return made[key]
-    return get
+    """key -> (engine with the candidate and its gains in place, the device's K): tests/_sweep_gpu.make_loaded"""
+    return sw.make_loaded(cases)
 
 
 @pytest.mark.parametrize("key", sorted(ps.CASES))
@@ -83,22 +80,14 @@ def test_kernel_matches_the_definition(oracle, cases, loaded, key):
     got = _raw(e, vk, vb)
     want = ps.expected(oracle, low, c["xs"], c["us"], K, vk, vb)
     assert set(got) == set(_fields(low))
-    for k in got:
-        assert got[k].shape == want[k].shape, (k, got[k].shape, want[k].shape)
-        err = cv.traj_relerr(got[k], want[k])   # (a trajectory whose reference is all zero must match exactly)
-        print("%s %s: %.2e (max |reference| %.2e)" % (key, k, err, np.abs(want[k]).max()))
-        assert err < 1e-9, (k, err)
+    sw.matches(got, want, _fields(low), key)
     assert np.abs(want["dxT_dmotor_inertia"]).max() > 1e-3 and np.abs(want["x_var"]).max() > 1e-6
     if low.T > 1:
         assert np.abs(want["u_var"]).max() > 1e-6 and np.abs(want["dcost_dmotor_inertia"]).max() > 1e-3
     else:   # T = 1: S_0 = 0, so V_0 = 0 on both sides
         assert (got["u_var"] == 0.0).all()
-    if key in ("vsa_box", "arm_vsa"):   # gains after a BoxDDP backward sweep: some rows are zero, and so is their variance
-        zero = np.abs(K).max(axis=-1) == 0.0
-        assert zero.any() and not zero.all()
-        assert (got["u_var"].transpose(1, 0, 2)[zero] == 0.0).all()
-    if key == "nu1":
-        assert (got["u_var"][..., 1] == 0.0).all()   # the padded control
+    sw.zero_gain_rows(key, K, got)
+    sw.padded_control(key, got)
     if getattr(low, "ref_path", None) is not None:   # ... and the path is what the records were evaluated against
         plain = scenarios.lower(dict(c["sc"], ref_path=None))
         other = ps.expected(oracle, plain, c["xs"], c["us"], K, vk, vb)
@@ -114,8 +103,7 @@ def test_every_output_is_optional(cases, loaded, key):
     e, _ = loaded(key)
     vk, vb = c["var"]
     full = _raw(e, vk, vb)
-    for k in full:
-        ext.same(_raw(e, vk, vb, which=(k,)), {k: full[k]}, "alone")
+    sw.each_output_alone(lambda **kw: _call(c)(e, **kw), full)
     ext.same(_raw(e, None, vb, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia only")
     if vk is not None:
         ext.same(_raw(e, vk, None, which=MOTOR), {k: full[k] for k in MOTOR}, "motor inertia outputs, stiffness variance")
@@ -128,19 +116,10 @@ def test_every_output_is_optional(cases, loaded, key):
 
 @pytest.mark.parametrize("key", ["sea", "arm_sea", "arm_vsa"])
 def test_a_trajectory_does_not_depend_on_where_it_sits(cases, loaded, key):
-    """trajectory B - 1 of the batch (the one behind the last full wave of teams) against the same trajectory alone in a
-    B = 1 engine (tests/_traj_oracle.single: its row of the table in the models) with the batch's gains uploaded: bit for
-    bit"""
+    """trajectory B - 1 of the batch against the same trajectory alone in a B = 1 engine, bit for bit (sw.trajectory_alone)"""
     c = cases[key]
-    low = c["low"]
     e, K = loaded(key)
-    vk, vb = c["var"]
-    batch = _raw(e, vk, vb)
-    b = low.B - 1
-    e1 = gc.engine(_traj_oracle.single(low, b))
-    gc._upload(e1, XS=c["xs"][:, b:b + 1], US=c["us"][:, b:b + 1], KGAIN=K[:, b:b + 1])
-    alone = _raw(e1, None if vk is None else vk[b:b + 1], vb[b:b + 1])
-    ext.same({k: v[0] for k, v in alone.items()}, {k: v[b] for k, v in batch.items()}, "trajectory %d" % b)
+    sw.trajectory_alone(c, e, K, _call(c), lambda b: _call(c, b))
 
 
 @pytest.mark.parametrize("key", ["sea", "arm_vsa"])
@@ -210,20 +189,7 @@ def test_the_sweep_agrees_with_sampled_plants(cases, loaded):
 def test_the_call_has_the_side_effects_of_calc_diff(cases):
     """3 iterations, the call (both variances, all outputs), 3 more iterations: XS, US, TRAJ_F and TRAJ_I are, bit for bit,
     those of 3 iterations, aslr_calc_diff, 3 iterations on a fresh engine"""
-    c = cases["vsa_box"]
-    low, sp = c["low"], c["sp"]
-    runs = []
-    for call in (lambda e: _raw(e, *c["var"]), lambda e: e.calc_diff()):
-        e = gc.engine(low)
-        e.set_candidate(None, None)
-        e.iterate_n(sp, True, 3)
-        call(e)
-        e.iterate_n(sp, False, 3)
-        gc.sync()
-        runs.append(gc.solution(e))
-    assert (runs[1]["traj_i"][_abi.TI_ITER] > 3).any()
-    for k in runs[0]:
-        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)
+    sw.side_effects_of_calc_diff(cases["vsa_box"], _call(cases["vsa_box"]))
 
 
 def _refused(e, vk, vb, which, *words):
@@ -321,14 +287,8 @@ def test_python_facade(cases):
     for k in ("x_var", "u_var"):
         gc.same_bits(getattr(one, k), getattr(tiled, k), "broadcast [nj]: %s" % k)
     # ... at a stored policy, through the problem: the same bits, and the engine's own policy is back afterwards
-    xs, us, K = (e.region(r).clone() for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN))
-    for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
-        e.region(r).fill_(0.25)
-    again = problem.policy_plant_sensitivity(xs.permute(1, 0, 2), us.permute(1, 0, 2), K.permute(1, 0, 2, 3), vk, vb)
-    gc.same_bits(again.x_var, res.x_var, "the stored policy given explicitly")
-    gc.same_bits(again.dcost_dstiffness, res.dcost_dstiffness, "the stored policy given explicitly")
-    for r in (_abi.R_XS, _abi.R_US, _abi.R_KGAIN):
-        assert (e.region(r) == 0.25).all()
+    xs, _, _ = sw.stored_policy_round_trip(problem, e, lambda p, *policy: p.policy_plant_sensitivity(*policy, vk, vb),
+                                           {"x_var": res.x_var, "dcost_dstiffness": res.dcost_dstiffness})
     # refusals of the facade
     neg = np.array(vb)
     neg[2, 1] = -1e-3
@@ -350,10 +310,4 @@ def test_python_facade(cases):
     with pytest.raises(ValueError, match="VSA"):
         vs.policy_plant_sensitivity(stiffness_var=vb[0])
     # padded controls are cut
-    psc = cases["nu1"]["sc"]
-    pp = crocoddyl.ShootingProblem(psc["x0"], psc["running"], psc["terminal"], frame_refs=psc["frame_refs"])
-    psolver = crocoddyl.SolverDDP(pp)
-    psolver.solve([], [], 3)
-    r1 = psolver.policy_plant_sensitivity(motor_inertia_var=np.ones(2))
-    gc.sync()
-    assert tuple(r1.u_var.shape) == (3, cases["nu1"]["low"].T, 1) and tuple(r1.x_var.shape) == (3, cases["nu1"]["low"].T + 1, 8)
+    sw.padded_controls_are_cut(cases, lambda solver: solver.policy_plant_sensitivity(motor_inertia_var=np.ones(2)))

@@ -12,6 +12,7 @@ import _ext_call as ext
 import _gpu_case as gc
 import _ref_path
 import _sensitivity as sens
+import _sweep_gpu as sw
 from aslr_to_amd import _abi, crocoddyl, scenarios
 
 pytestmark = pytest.mark.gpu
@@ -122,11 +123,7 @@ def test_every_output_is_optional(name, B, T):
     """each output alone: the bits of the call with all four, and nothing written past any buffer (_raw checks the guards)"""
     sc, low, xs, us = _case(name, True, B, T, False)
     e = _loaded(low, xs, us)
-    full = _raw(e)
-    for k in FIELDS:
-        alone = _raw(e, which=(k,))
-        assert list(alone) == [k]
-        np.testing.assert_array_equal(alone[k].view(np.uint64), full[k].view(np.uint64), err_msg=k)
+    sw.each_output_alone(lambda **kw: _raw(e, **kw), _raw(e))
 
 
 def test_refusals_leave_a_live_handle_that_still_solves():

@@ -11,53 +11,20 @@ nu = 7 and 14).  Per shape, the median over `repeats` (default 20) of
                     covariance_kernel alone;
   backward          aslr_backward_pass of the same handle on the same records (existing code, for comparison).
 The candidate and the gains are what five solver iterations from a cold start leave."""
-import ctypes as C
-import os
-import statistics
 import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from aslr_to_amd import _abi, scenarios
-from aslr_to_amd.engine import Engine
-
-SHAPES = {"two_dof_vsa_boxddp": lambda: scenarios.two_dof_vsa_boxddp(B=4096, T=100, seed=0),
-          "talos_arm_sea": lambda: scenarios.talos_arm_sea(B=512, T=150, seed=0),
-          "talos_arm_vsa": lambda: scenarios.talos_arm_vsa(B=512, T=150, seed=0)}
-
-
-def timed(fn, repeats):
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        t1.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return statistics.median(ms)
+from _timing import STANDARD_SHAPES, planned, ptr, seeded_spread, timed
 
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    for name, make in SHAPES.items():
-        sc = make()
-        low = scenarios.lower(sc)
-        sp = scenarios.solver_params(sc)
-        e = Engine(low)
-        e.set_candidate(None, None)
-        e.iterate_n(sp, True, 5)
-        e.finalize()
-        torch.cuda.synchronize()
-        gen = torch.Generator(device="cpu").manual_seed(0)
-        m = torch.rand((e.B, e.nx, e.nx), generator=gen, dtype=torch.float64) * 2 - 1
-        s0 = (m @ m.transpose(1, 2) + 0.1 * torch.eye(e.nx, dtype=torch.float64)).to(e.device)
-        w = (0.1 + 0.9 * torch.rand((e.T, e.B, e.nx), generator=gen, dtype=torch.float64)).to(e.device)
+    for name, make in STANDARD_SHAPES.items():
+        e, sp = planned(make, 5)
+        s0, w, _ = seeded_spread(e)
         new = lambda *s: torch.zeros(s, dtype=torch.float64, device=e.device)
         xv, uv, cf, ci = new(e.T + 1, e.B, e.nx), new(e.T, e.B, e.nu), new(e.B, e.nx, e.nx), new(e.B)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         cov = lambda: e._call("aslr_policy_covariance", ptr(s0), ptr(w), ptr(xv), ptr(uv), ptr(cf), None, ptr(ci), e._stream())
         states = lambda: e._call("aslr_policy_covariance", ptr(s0), ptr(w), ptr(xv), None, ptr(cf), None, None, e._stream())
         for fn in (e.calc_diff, cov, states, lambda: e.backward_pass(sp)):  # warm-up: code objects loaded, records in place

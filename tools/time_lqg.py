@@ -15,62 +15,26 @@ The candidate and the gains are what five solver iterations from a cold start le
 talos_arm_sea: there that solve has diverged on some trajectories by the last knots (|Fx| up to 6e28, |K| up to 1e16), which
 is past the call's limit of validity (include/aslr_to_amd_lqg.h), so its plan is the empty candidate with the gains of one
 backward sweep on it.  Every output of every form is checked to be finite."""
-import ctypes as C
-import os
-import statistics
 import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from aslr_to_amd import scenarios
-from aslr_to_amd.engine import Engine
+from _timing import STANDARD_SHAPES, planned, ptr, seeded_spread, timed
 
-# name -> (scenario, solver iterations from a cold start that make the plan; 0: the empty candidate and one backward sweep)
-SHAPES = {"two_dof_vsa_boxddp": (lambda: scenarios.two_dof_vsa_boxddp(B=4096, T=100, seed=0), 5),
-          "talos_arm_sea": (lambda: scenarios.talos_arm_sea(B=512, T=150, seed=0), 0),
-          "talos_arm_vsa": (lambda: scenarios.talos_arm_vsa(B=512, T=150, seed=0), 5)}
-
-
-def timed(fn, repeats):
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        t1.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return statistics.median(ms)
+# solver iterations from a cold start that make the plan; 0: the empty candidate and one backward sweep
+ITERATIONS = {"two_dof_vsa_boxddp": 5, "talos_arm_sea": 0, "talos_arm_vsa": 5}
 
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    for name, (make, iterations) in SHAPES.items():
-        sc = make()
-        low = scenarios.lower(sc)
-        sp = scenarios.solver_params(sc)
-        e = Engine(low)
-        e.set_candidate(None, None)
-        if iterations:
-            e.iterate_n(sp, True, iterations)
-            e.finalize()
-        else:
-            e.calc_diff()
-            e.backward_pass(sp)
-        torch.cuda.synchronize()
-        gen = torch.Generator(device="cpu").manual_seed(0)
-        m = torch.rand((e.B, e.nx, e.nx), generator=gen, dtype=torch.float64) * 2 - 1
-        s0 = (m @ m.transpose(1, 2) + 0.1 * torch.eye(e.nx, dtype=torch.float64)).to(e.device)
-        w = (0.1 + 0.9 * torch.rand((e.T, e.B, e.nx), generator=gen, dtype=torch.float64)).to(e.device)
-        r = (0.1 + 0.9 * torch.rand((e.B, e.nx), generator=gen, dtype=torch.float64)).to(e.device)   # [B][ny] for ny = nx
+    for name, make in STANDARD_SHAPES.items():
+        e, sp = planned(make, ITERATIONS[name])
+        s0, w, r = seeded_spread(e)   # r: [B][ny] for ny = nx
         rh = r[:, :e.nx // 2].contiguous()
         new = lambda *s: torch.zeros(s, dtype=torch.float64, device=e.device)
         xv, uv, ev, ci = new(e.T + 1, e.B, e.nx), new(e.T, e.B, e.nu), new(e.T + 1, e.B, e.nx), new(e.B)
         cf, ef, kg = new(e.B, e.nx, e.nx), new(e.B, e.nx, e.nx), new(e.T + 1, e.B, e.nx, e.nx // 2)
         outputs = (xv, uv, ev, cf, ef, ci, kg)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         cov = lambda: e._call("aslr_policy_covariance", ptr(s0), ptr(w), ptr(xv), ptr(uv), ptr(cf), None, ptr(ci), e._stream())
         lqg = lambda: e._call("aslr_policy_lqg", e.nx // 2, None, ptr(rh), ptr(s0), ptr(w), ptr(xv), ptr(uv), ptr(ev), ptr(cf), ptr(ef),
                               None, ptr(ci), e._stream())

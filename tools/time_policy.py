@@ -11,42 +11,17 @@ leave.  Median over `repeats` (default 20) of
                     (B / 4) * (S / 16) waves; per wave = time * CUs * 4 SIMDs / waves when the waves outnumber the SIMDs,
                     else the time itself;
   policy S kept     the same with xs_closed and us_closed written."""
-import ctypes as C
-import os
-import statistics
 import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from aslr_to_amd import scenarios
-from aslr_to_amd.engine import Engine
-
-
-def timed(fn, repeats):
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        t1.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return statistics.median(ms)
+from _timing import STANDARD_SHAPES, planned, ptr, timed
 
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 20
-    B, T = 4096, 100
-    sc = scenarios.two_dof_vsa_boxddp(B=B, T=T, seed=0)
-    low = scenarios.lower(sc)
-    sp = scenarios.solver_params(sc)
-    e = Engine(low)
-    e.set_candidate(None, None)
-    e.iterate_n(sp, True, 5)
-    e.finalize()
-    torch.cuda.synchronize()
+    e, sp = planned(STANDARD_SHAPES["two_dof_vsa_boxddp"], 5)
+    B, T = e.B, e.T
     simds = torch.cuda.get_device_properties(e.device).multi_processor_count * 4
     fwd = lambda: e.forward_pass(sp)
     fwd()
@@ -56,7 +31,6 @@ def main():
           % (t_fwd, B // 4, simds))
     gen = torch.Generator(device=e.device).manual_seed(1)
     rnd = lambda lo, hi, *shape: lo + (hi - lo) * torch.rand(shape, dtype=torch.float64, device=e.device, generator=gen)
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
     for S in (16, 64, 256):
         pb = 1e-3 * rnd(0.7, 1.3, 2, S, B)
         dx0, w = rnd(-1e-2, 1e-2, S, B, 8), rnd(-1e-3, 1e-3, S, T, B, 8)

@@ -14,53 +14,27 @@ and, once (wall clock, not a median: it takes seconds),
 Then, on the two-joint shape only, the noise call at growing S with `cost` as its only output: the array form's disturbance
 alone would be 8 S T B nx bytes there."""
 import ctypes as C
-import os
-import statistics
 import sys
 import time
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import numpy as np
 import torch
 
-from aslr_to_amd import _abi, scenarios
-from aslr_to_amd.engine import Engine
+from _timing import STANDARD_SHAPES, planned, ptr, timed
+from aslr_to_amd import _abi
 
-SHAPES = {"two_dof_vsa_boxddp": lambda: scenarios.two_dof_vsa_boxddp(B=4096, T=100, seed=0),
-          "talos_arm_sea": lambda: scenarios.talos_arm_sea(B=512, T=150, seed=0),
-          "talos_arm_vsa": lambda: scenarios.talos_arm_vsa(B=512, T=150, seed=0)}
 NOISE_STD, DX0_STD, PLANT_REL_STD = 3e-4, 3e-3, 0.05
 LARGE_S = (1024, 8192, 65536)
 SEED = 2026
 
 
-def timed(fn, repeats):
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        t1.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return statistics.median(ms)
-
-
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     S = int(sys.argv[2]) if len(sys.argv) > 2 else 64
-    for name, make in SHAPES.items():
-        sc = make()
-        low = scenarios.lower(sc)
-        sp = scenarios.solver_params(sc)
-        e = Engine(low)
-        e.set_candidate(None, None)
-        e.iterate_n(sp, True, 5)
-        e.finalize()
-        torch.cuda.synchronize()
+    for name, make in STANDARD_SHAPES.items():
+        e, sp = planned(make, 5)
         B, T, nx, nu, nj = e.B, e.T, e.nx, e.nu, e.nx // 4
-        sea = low.dam == _abi.DAM_SEA
+        sea = e.low.dam == _abi.DAM_SEA
         clamp = 1 if sp.solver == _abi.SOLVER_BOXDDP else 0
         new = lambda dt, *s: torch.zeros(s, dtype=dt, device=e.device)
         full = lambda v, n: torch.full((B, n), v, dtype=torch.float64, device=e.device)
@@ -68,7 +42,6 @@ def main():
         cost, failed, xf = new(torch.float64, S, B), new(torch.int32, S, B), new(torch.float64, S, B, nx)
         pk, pb = (new(torch.float64, nj, S, B) if sea else None), new(torch.float64, nj, S, B)
         d0, w = new(torch.float64, S, B, nx), new(torch.float64, S, T, B, nx)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         noise = lambda n, outs, drawn: e._call("aslr_policy_rollout_noise", n, 0, 0, C.c_uint64(SEED), ptr(sw), ptr(s0), ptr(sk), ptr(sb), clamp,
                                                *[ptr(t) for t in outs], *[ptr(t) for t in drawn], e._stream())
         old = "aslr_policy_rollout" if nj == 2 else "aslr_policy_rollout_all"

@@ -13,47 +13,23 @@ Per shape, the median over `repeats` (default 20), after a warm-up of every call
 Per-knot figures: time / T per launch (all teams run at once when they fit the device), and time / (S B T) resp.
 time / (10 B T) per (sample or step length, trajectory, knot).  The candidate and the gains are what five solver iterations
 from a cold start leave; the plants are the trajectories' own within +-30 %, |dx0| <= 1e-2, |w| <= 1e-3."""
-import ctypes as C
-import os
-import statistics
 import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from aslr_to_amd import _abi, scenarios
-from aslr_to_amd.engine import Engine
+from _timing import STANDARD_SHAPES, planned, ptr, timed
+from aslr_to_amd import _abi
 
-SHAPES = {"talos_arm_sea": lambda: scenarios.talos_arm_sea(B=512, T=150, seed=0),
-          "talos_arm_vsa": lambda: scenarios.talos_arm_vsa(B=512, T=150, seed=0)}
+SHAPES = {name: STANDARD_SHAPES[name] for name in ("talos_arm_sea", "talos_arm_vsa")}
 NALPHA = 10
-
-
-def timed(fn, repeats):
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        t1.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return statistics.median(ms)
 
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     S = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     for name, make in SHAPES.items():
-        sc = make()
-        low = scenarios.lower(sc)
-        sp = scenarios.solver_params(sc)
-        e = Engine(low)
-        e.set_candidate(None, None)
-        e.iterate_n(sp, True, 5)
-        e.finalize()
-        torch.cuda.synchronize()
+        e, sp = planned(make, 5)
+        low = e.low
         B, T, nx, nu, nj = e.B, e.T, e.nx, e.nu, e.nx // 4
         sea = low.dam == _abi.DAM_SEA
         gen = torch.Generator(device="cpu").manual_seed(0)
@@ -66,7 +42,6 @@ def main():
         new = lambda dt, *s: torch.zeros(s, dtype=dt, device=e.device)
         cost, failed, xf = new(torch.float64, S, B), new(torch.int32, S, B), new(torch.float64, S, B, nx)
         xs, us = new(torch.float64, S, T + 1, B, nx), new(torch.float64, S, T, B, nu)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         call = lambda ins, outs: e._call("aslr_policy_rollout_all", S, *[ptr(t) for t in ins], 0, *[ptr(t) for t in outs], e._stream())
         lean = lambda: call((pk, pb, d0, w), (cost, failed, xf, None, None))
         full = lambda: call((pk, pb, d0, w), (cost, failed, xf, xs, us))

@@ -9,49 +9,23 @@ Per shape, the median over `repeats` (default 20) of
   adjoint           sensitivity - calc_diff: the C ABI has no entry point that launches adjoint_kernel alone;
   backward          aslr_backward_pass of the same handle on the same records (existing code, for comparison).
 The candidate is what five solver iterations from a cold start leave, so that the backward sweep factors every knot."""
-import ctypes as C
-import statistics
 import sys
-
-import os
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from aslr_to_amd import _abi, scenarios
-from aslr_to_amd.engine import Engine
+from _timing import STANDARD_SHAPES, planned, ptr, timed
+from aslr_to_amd import _abi
 
-SHAPES = {"C3": lambda: scenarios.two_dof_vsa_boxddp(B=4096, T=100, seed=0),
-          "C5": lambda: scenarios.talos_arm_sea(B=512, T=150, seed=0)}
-
-
-def timed(fn, repeats):
-    ms = []
-    for _ in range(repeats):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
-        fn()
-        t1.record()
-        t1.synchronize()
-        ms.append(t0.elapsed_time(t1))
-    return statistics.median(ms)
+SHAPES = {"C3": STANDARD_SHAPES["two_dof_vsa_boxddp"], "C5": STANDARD_SHAPES["talos_arm_sea"]}
 
 
 def main():
     repeats = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     for name, make in SHAPES.items():
-        sc = make()
-        low = scenarios.lower(sc)
-        sp = scenarios.solver_params(sc)
-        e = Engine(low)
-        e.set_candidate(None, None)
-        e.iterate_n(sp, True, 5)
-        e.finalize()
-        torch.cuda.synchronize()
-        nj, vsa = e.nx // 4, low.dam == _abi.DAM_VSA
+        e, sp = planned(make, 5)
+        nj, vsa = e.nx // 4, e.low.dam == _abi.DAM_VSA
         new = lambda *s: torch.zeros(s, dtype=torch.float64, device=e.device)
         dk, db, dx0, lam = (None if vsa else new(nj, e.B)), new(nj, e.B), new(e.nx, e.B), new(e.T + 1, e.B, e.nx)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         sens = lambda: e._call("aslr_cost_sensitivity", ptr(dk), ptr(db), ptr(dx0), ptr(lam), e._stream())
         for fn in (e.calc_diff, sens, lambda: e.backward_pass(sp)):  # warm-up: code objects loaded, records in place
             fn()
