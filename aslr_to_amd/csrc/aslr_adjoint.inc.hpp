@@ -9,23 +9,21 @@
 // -delta_j / K_j, so no rigid-body term is evaluated again: the sweep reads Fx and Lx of every
 // record and four words of XS / XNEXT per knot.
 //
-// Decomposition: one team of lanes per trajectory, lane j owns column j of Fx and entry j of lambda.  nx = 8: 8 lanes,
-// 8 trajectories per wave; nx = 28: 32 lanes (28 at work), 2 per wave.  Column reads coalesce (row i of Fx is nx
-// consecutive words, one per lane).  (Fx^T lambda)[j] is ONE fma chain over i = 0 .. nx-1, ascending; lambda[i] reaches
-// the team through a cross-lane shuffle, never through memory.  The parameter terms are local to lane nj + j once that
-// product exists and accumulate there in t order.  Every lane of the wave stays alive on clamped indices (the shuffle
-// sources are always valid) and only the stores are guarded, so a trajectory's arithmetic is the same instruction stream
-// whatever its position in the batch: results do not depend on B, bit for bit.
+// Decomposition: one team of lanes per trajectory (aslr_sweep_team.hpp), lane j owns column j of Fx and entry j of
+// lambda.  Column reads coalesce (row i of Fx is nx consecutive words, one per lane).  (Fx^T lambda)[j] is ONE fma chain
+// over i = 0 .. nx-1, ascending; lambda[i] reaches the team through a cross-lane shuffle, never through memory.  The
+// parameter terms are local to lane nj + j once that product exists and accumulate there in t order.  The clamped
+// indices keep every shuffle source valid.
 //
 // Latency-bound like the other serial sweeps: knot t-1 is loaded while knot t is reduced.
 #pragma once
-#include "aslr_common.hpp"
+#include "aslr_sweep_team.hpp"
 
 namespace aslr {
 
 template <int NX, int NU>
 __global__ void __launch_bounds__(64) adjoint_kernel(AdjointArgs a) {
-  constexpr int NJ = NX / 4, TEAM = NX == 8 ? 8 : 32, TPW = 64 / TEAM;
+  constexpr int NJ = SweepTeam<NX>::NJ, TEAM = SweepTeam<NX>::TEAM, TPW = SweepTeam<NX>::TPW;
   using L = RecLayout<NJ, NU>;
   const int lane = threadIdx.x, jr = lane % TEAM;
   const int br = blockIdx.x * TPW + lane / TEAM;
@@ -91,9 +89,7 @@ __global__ void __launch_bounds__(64) adjoint_kernel(AdjointArgs a) {
 
 template <int NJ, int DAM>
 int launch_adjoint(const AdjointArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL((adjoint_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
-  HIP_TRY(hipGetLastError());
-  return ASLR_OK;
+  return launch_sweep<NJ, DAM>(adjoint_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>, a, st);
 }
 
 } // namespace aslr

@@ -5,12 +5,11 @@
 //
 // No model evaluation: the sweep reads Fx, Fu (and Lxx, Lxu, Luu for the control terms) of every record and KGAIN.
 //
-// Decomposition: one team of lanes per trajectory, as in the adjoint sweep -- nx = 8: 8 lanes, 8 trajectories per wave;
-// nx = 28: 32 lanes (28 at work), 2 per wave; one wave per block.  Lane j owns row j of A_t and column j of Sigma_t (its
-// registers); row j of Fx and of Fu are contiguous words of the record.  What a team shares -- K_t, the columns of Sigma_t,
-// the rows of A_t, G_t -- is staged per team in LDS and read back at team-uniform addresses (broadcast reads, two
-// operands per 16-byte read): a lane needs ALL of Sigma and ALL of A every knot, nx^2 operands each, which as cross-lane
-// shuffles would be 2 nx^2 two-dword permutes per knot against nx^2 / 2 wide reads.  One knot:
+// Decomposition: one team of lanes per trajectory (aslr_sweep_team.hpp).  Lane j owns row j of A_t and column j of
+// Sigma_t (its registers); row j of Fx and of Fu are contiguous words of the record.  What a team shares -- K_t, the
+// columns of Sigma_t, the rows of A_t, G_t -- is staged per team in LDS and read back at team-uniform addresses (broadcast
+// reads, two operands per 16-byte read): a lane needs ALL of Sigma and ALL of A every knot, nx^2 operands each, which as
+// cross-lane shuffles would be 2 nx^2 two-dword permutes per knot against nx^2 / 2 wide reads.  One knot:
 //   stage   K_t (the team's lanes load nu nx / TEAM words each), column j of Sigma, row j of Fu -> LDS            | barrier
 //   1       a_j[c]   = Fx[j][c] - sum_k Fu[j][k] K[k][c]            -> LDS, transposed (At[c][j])
 //   (ctrl)  G[k][j]  = sum_i K[k][i] Sigma[i][j]                    -> LDS                                        | barrier
@@ -25,24 +24,20 @@
 // word in LDS, because an entry of a register array cannot be picked by a loop counter.  Unrolled in full, the 2 nx^2
 // independent chains of a knot let the scheduler hoist every LDS read, and the nx = 28 kernels spilled 11 KB per lane.
 // The control terms (ctrl) are computed only when u_var or cost_increase is asked for; they do not enter Sigma, so every
-// output has the same bits whichever others are asked for.  Every lane of the wave stays alive on clamped indices and
-// only the stores (to memory and to LDS) are guarded, so a trajectory's arithmetic is the same instruction stream
-// whatever its position in the batch: results do not depend on B, bit for bit.
+// output has the same bits whichever others are asked for.
 //
 // Arithmetic: 2 nx^2 + nu nx fma per lane and knot (+ 2 nu nx with the control terms) on a serial chain of T knots; the records
 // of knot t + 1 are loaded while knot t is reduced.  Measured (profiles/covariance/README.md), the sweep is bound by the
 // LDS round trips of that chain -- write, barrier, broadcast reads that the fma of the same trip wait for -- at the one or
 // two waves per CU these batch sizes give, not by the fma rate.
 #pragma once
-#include "aslr_common.hpp"
+#include "aslr_sweep_team.hpp"
 
 namespace aslr {
 
-#define ASLR_COV_LOOP _Pragma("unroll 2")
-
 template <int NX, int NU>
 __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
-  constexpr int NJ = NX / 4, TEAM = NX == 8 ? 8 : 32, TPW = 64 / TEAM;
+  constexpr int NJ = SweepTeam<NX>::NJ, TEAM = SweepTeam<NX>::TEAM, TPW = SweepTeam<NX>::TPW;
   constexpr int NK = NU * NX, KP = (NK + TEAM - 1) / TEAM; // words of K_t, and how many of them one lane of the team loads
   using L = RecLayout<NJ, NU>;
   // a team's LDS: S [TEAM][nx] a row per lane: its column of Sigma, then its row of Y;  At [nx][nx] A transposed;  K, G [nu][nx];
@@ -121,7 +116,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
     { // 1: row j of A_t
       double av[NX];
       ASLR_UNROLL for (int c = 0; c < NX; ++c) av[c] = cur.fx[c];
-      ASLR_COV_LOOP for (int k = 0; k < NU; ++k) {
+      ASLR_SWEEP_LOOP for (int k = 0; k < NU; ++k) {
         const double fk = -my_f[k];
         ASLR_UNROLL for (int c = 0; c < NX; ++c) av[c] = fma(fk, tm[oK + k * NX + c], av[c]);
       }
@@ -130,7 +125,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
       }
     }
     if (ctrl) { // column j of G_t
-      ASLR_COV_LOOP for (int k = 0; k < NU; ++k) {
+      ASLR_SWEEP_LOOP for (int k = 0; k < NU; ++k) {
         double g = 0.0;
         ASLR_UNROLL for (int i = 0; i < NX; ++i) g = fma(tm[oK + k * NX + i], s[i], g);
         if (work) tm[oG + k * NX + j] = g;
@@ -140,7 +135,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
 
     double y[NX]; // 2: row j of A_t Sigma_t
     ASLR_UNROLL for (int c = 0; c < NX; ++c) y[c] = 0.0;
-    ASLR_COV_LOOP for (int i = 0; i < NX; ++i) {
+    ASLR_SWEEP_LOOP for (int i = 0; i < NX; ++i) {
       const double ai = tm[oAt + i * NX + j];
       ASLR_UNROLL for (int c = 0; c < NX; ++c) y[c] = fma(ai, tm[oS + i * NX + c], y[c]);
     }
@@ -155,7 +150,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
     // 3: row j of Sigma_{t+1} before the noise, and its entry j
     ASLR_UNROLL for (int c = 0; c < NX; ++c) s[c] = 0.0;
     d = 0.0;
-    ASLR_COV_LOOP for (int i = 0; i < NX; ++i) {
+    ASLR_SWEEP_LOOP for (int i = 0; i < NX; ++i) {
       const double yi = my_s[i];
       ASLR_UNROLL for (int c = 0; c < NX; ++c) s[c] = fma(yi, tm[oAt + i * NX + c], s[c]);
       d = fma(yi, tm[oAt + i * NX + j], d);
@@ -164,7 +159,7 @@ __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
       double gr[NX]; // row ku of G_t
       ASLR_UNROLL for (int c = 0; c < NX; ++c) gr[c] = tm[oG + ku * NX + c];
       double uk = 0.0;
-      ASLR_COV_LOOP for (int l = 0; l < NU; ++l) {
+      ASLR_SWEEP_LOOP for (int l = 0; l < NU; ++l) {
         double v = 0.0; // U[ku][l]
         ASLR_UNROLL for (int c = 0; c < NX; ++c) v = fma(gr[c], tm[oK + l * NX + c], v);
         if (l == ku) uk = v;
@@ -200,13 +195,9 @@ __global__ void __launch_bounds__(64) covariance_kernel(CovarianceArgs a) {
   }
 }
 
-#undef ASLR_COV_LOOP
-
 template <int NJ, int DAM>
 int launch_covariance(const CovarianceArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL((covariance_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
-  HIP_TRY(hipGetLastError());
-  return ASLR_OK;
+  return launch_sweep<NJ, DAM>(covariance_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>, a, st);
 }
 
 } // namespace aslr

@@ -11,8 +11,7 @@
 // With E_t = [Jz_t | r_t] ([nx][np + 1]) all three are entries of ONE packed lower matrix M = sum_t E_t^T W E_t of order np + 1:
 // H is its leading block (same packed index), -g its last row, sse its last entry.  NE = (np + 1)(np + 2) / 2 entries: 6 .. 120.
 //
-// Decomposition: one team of lanes per trajectory as in the adjoint and tangent sweeps -- nx = 8: 8 lanes, 8 trajectories per
-// wave; nx = 28: 32 lanes (28 of them stage a row), 2 per wave; one wave per block.  Per knot lane j stages row j of E_t and of
+// Decomposition: one team of lanes per trajectory (aslr_sweep_team.hpp).  Per knot lane j stages row j of E_t and of
 // W E_t in the team's LDS (two buffers used in turn: one barrier per knot), then every lane of the team continues the sums of
 // the entries it owns -- entry e of M belongs to lane e % TEAM, at most 4 per lane:
 //   M[c][d] = fma(w_i E[i][c], E[i][d], M[c][d])        i = 0 .. nx-1 within the knot, knots in ascending order
@@ -21,8 +20,6 @@
 // beyond that sum (nothing of knot t feeds knot t + 1; the loads of knot t + 1 are in flight while knot t is reduced).
 // The kernel reads, per knot: columns nj .. 2nj-1 of the lane's row of Fx (STIFF only), xs_t[0 .. 2nj-1] (STIFF only),
 // xs_t[3nj+c] and xnext_t[3nj+c] of the lane's joint, xs_{t+1}[j] and xnext_t[j].  It reads no K and no B.
-// Every lane of the wave stays alive on clamped indices and only the stores (to LDS and to memory) are guarded: a trajectory's
-// arithmetic is the same instruction stream whatever its position in the batch, and its bits do not depend on B.
 // The rows of E are indexed at run time in LDS only; the accumulators are registers with compile-time indices: no scratch.
 //
 // ---- identify_step_kernel ----
@@ -31,13 +28,13 @@
 // every product, sum and quotient is an explicitly rounded intrinsic and the unit is compiled with -ffp-contract=off (the
 // fma calls of the kernel above are explicit and unaffected).
 #pragma once
-#include "aslr_common.hpp"
+#include "aslr_sweep_team.hpp"
 
 namespace aslr {
 
 template <int NX, int NU, bool STIFF>
 __global__ void __launch_bounds__(64) identify_normal_kernel(IdentifyNormalArgs a) {
-  constexpr int NJ = NX / 4, TEAM = NX == 8 ? 8 : 32, TPW = 64 / TEAM;
+  constexpr int NJ = SweepTeam<NX>::NJ, TEAM = SweepTeam<NX>::TEAM, TPW = SweepTeam<NX>::TPW;
   constexpr int NP = STIFF ? 2 * NJ : NJ, P0 = NP - NJ, NC = NP + 1; // columns of Jz; the first motor-inertia column; columns of E
   constexpr int NE = NC * (NC + 1) / 2, SL = (NE + TEAM - 1) / TEAM;  // entries of M, and how many of them one lane sums
   constexpr int NF = STIFF ? NJ : 1;
@@ -82,7 +79,7 @@ __global__ void __launch_bounds__(64) identify_normal_kernel(IdentifyNormalArgs 
     Knot nxt;
     load(nxt, t + 1 < T ? t + 1 : T - 1); // in flight while knot t is reduced (t = T-1: a repeat, dropped)
     double *bf = tm + (t & 1) * BUF;
-    const int mi = ((const int32_t __attribute__((address_space(4))) *)(a.node_model))[t];
+    const int mi = knot_model(a.node_model, t);
     double dt = a.dt[0];
     ASLR_UNROLL for (int m = 1; m < ASLR_MAX_MODELS; ++m)
       if (mi == m) dt = a.dt[m];
@@ -122,15 +119,9 @@ __global__ void __launch_bounds__(64) identify_normal_kernel(IdentifyNormalArgs 
   }
 }
 
-// a.stiff: the stiffness columns are computed.  The STIFF kernels are built for the SEA sizes alone, as the tangent sweep's
 template <int NJ, int DAM>
 int launch_identify_normal(const IdentifyNormalArgs &a, hipStream_t st) {
-  const auto go = [&](auto STIFF) {
-    hipLaunchKernelGGL((identify_normal_kernel<4 * NJ, ModelDims<NJ, DAM>::nu, decltype(STIFF)::value>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
-  };
-  if constexpr (DAM == ASLR_DAM_SEA) with_bool(a.stiff != 0, go); else go(std::false_type{});
-  HIP_TRY(hipGetLastError());
-  return ASLR_OK;
+  return launch_sweep_stiff<NJ, DAM>([](auto STIFF) { return identify_normal_kernel<4 * NJ, ModelDims<NJ, DAM>::nu, decltype(STIFF)::value>; }, a, st);
 }
 
 // NPMAX: the most parameters a trajectory of the size can have (2 nj on SEA, nj on VSA): the size of the LDS arrays

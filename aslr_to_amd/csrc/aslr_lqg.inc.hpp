@@ -6,10 +6,9 @@
 //   predict   Pm' = Fx P Fx^T + diag(w_t),   Xm' = A Xh A^T,  A = Fx - Fu K                                        (t < T)
 //   cost_increase = 1/2 sum_t [tr(Lxx_t Sigma_t) - 2 tr(Lxu_t K_t Xh_t) + tr(Luu_t U_t)] + 1/2 tr(Lxx_T Sigma_T)
 //
-// Decomposition: that of covariance_kernel (aslr_covariance.inc.hpp) -- one team of lanes per trajectory (nx = 8: 8 lanes,
-// 8 trajectories per wave; nx = 28: 32 lanes, 28 at work, 2 per wave), one wave per block.  Lane j owns column j of Pm / P
-// and column j of Xm / Xh (its registers), row j of L, row j of Fx, Fu and A.  What a team shares is staged per team in LDS
-// and read back at team-uniform addresses (broadcast reads).  The team's LDS, in doubles:
+// Decomposition: that of covariance_kernel (aslr_covariance.inc.hpp; the team: aslr_sweep_team.hpp).  Lane j owns column j
+// of Pm / P and column j of Xm / Xh (its registers), row j of L, row j of Fx, Fu and A.  What a team shares is staged per
+// team in LDS and read back at team-uniform addresses (broadcast reads).  The team's LDS, in doubles:
 //   SP [TEAM][nx]  a row per lane: its column of Pm (update), then of P, then its row of Fx P
 //   SX [TEAM][nx]  a row per lane: its row of the gain -- g, then z, then L[j][:] (update) -- then its column of Xh, then
 //                  its row of A Xh
@@ -35,22 +34,18 @@
 // in aslr_covariance.inc.hpp (unrolled in full they spill), and the sums over the measured set are loops because ny is a
 // run-time number.  The filter -- P, L -- reads neither K nor Fu.  The Xh half is computed only when an output needs it
 // (x_var, u_var, cov_final, cost_increase), the control terms only for u_var or cost_increase; neither enters P, and the
-// control terms do not enter Xh, so every output has the same bits whichever others are asked for.  Every lane stays alive
-// on clamped indices and only stores are guarded: a trajectory's arithmetic is the same instruction stream wherever it
-// sits in the batch.
+// control terms do not enter Xh, so every output has the same bits whichever others are asked for.
 //
 // Arithmetic per lane and knot: 4 nx^2 + nu nx fma for the two congruence products and A, ny nx for D, ny^2 for the two
 // solves and ny^2 / 2 (twice: the lane's entry and the diagonal) for the factor -- the last two on one serial chain each.
 #pragma once
-#include "aslr_common.hpp"
+#include "aslr_sweep_team.hpp"
 
 namespace aslr {
 
-#define ASLR_LQG_LOOP _Pragma("unroll 2")
-
 template <int NX, int NU>
 __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
-  constexpr int NJ = NX / 4, TEAM = NX == 8 ? 8 : 32, TPW = 64 / TEAM;
+  constexpr int NJ = SweepTeam<NX>::NJ, TEAM = SweepTeam<NX>::TEAM, TPW = SweepTeam<NX>::TPW;
   constexpr int NK = NU * NX, KP = (NK + TEAM - 1) / TEAM; // words of K_t, and how many of them one lane of the team loads
   using L = RecLayout<NJ, NU>;
   constexpr int oSP = 0, oSX = oSP + TEAM * NX, oAt = oSX + TEAM * NX, oK = oAt + NX * NX, oG = oK + NK, oF = oG + NK,
@@ -136,7 +131,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
     { // row j of D = L G^T;  P = Pm - D,  Xh = Xm + D
       double d[NX];
       ASLR_UNROLL for (int c = 0; c < NX; ++c) d[c] = 0.0;
-      ASLR_LQG_LOOP for (int i = 0; i < ny; ++i) {
+      ASLR_SWEEP_LOOP for (int i = 0; i < ny; ++i) {
         const double li = my_x[i];
         const double *g = tm + oSP + meas[i] * NX;
         ASLR_UNROLL for (int c = 0; c < NX; ++c) d[c] = fma(li, g[c], d[c]);
@@ -187,7 +182,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
       { // row j of A_t
         double av[NX];
         ASLR_UNROLL for (int c = 0; c < NX; ++c) av[c] = cur.fx[c];
-        ASLR_LQG_LOOP for (int k = 0; k < NU; ++k) {
+        ASLR_SWEEP_LOOP for (int k = 0; k < NU; ++k) {
           const double fk = -my_f[k];
           ASLR_UNROLL for (int c = 0; c < NX; ++c) av[c] = fma(fk, tm[oK + k * NX + c], av[c]);
         }
@@ -197,7 +192,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
       }
       double pxx = 0.0, pxu = 0.0;
       if (ctrl) { // column j of G_t = K_t Xh_t;  the lane's part of tr(Lxx Sigma)
-        ASLR_LQG_LOOP for (int k = 0; k < NU; ++k) {
+        ASLR_SWEEP_LOOP for (int k = 0; k < NU; ++k) {
           double g = 0.0;
           ASLR_UNROLL for (int i = 0; i < NX; ++i) g = fma(tm[oK + k * NX + i], xm[i], g);
           if (work) tm[oG + k * NX + j] = g;
@@ -212,7 +207,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
 
       double y[NX]; // row j of A_t Xh_t
       ASLR_UNROLL for (int c = 0; c < NX; ++c) y[c] = 0.0;
-      ASLR_LQG_LOOP for (int i = 0; i < NX; ++i) {
+      ASLR_SWEEP_LOOP for (int i = 0; i < NX; ++i) {
         const double ai = tm[oAt + i * NX + j];
         ASLR_UNROLL for (int c = 0; c < NX; ++c) y[c] = fma(ai, tm[oSX + i * NX + c], y[c]);
       }
@@ -222,7 +217,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
       __syncthreads(); // (every lane has read the columns of Xh)
       ASLR_UNROLL for (int c = 0; c < NX; ++c) my_x[c] = y[c];
       ASLR_UNROLL for (int c = 0; c < NX; ++c) xm[c] = 0.0; // row j of Xm_{t+1}, taken as the lane's column by symmetry
-      ASLR_LQG_LOOP for (int i = 0; i < NX; ++i) {
+      ASLR_SWEEP_LOOP for (int i = 0; i < NX; ++i) {
         const double yi = my_x[i];
         ASLR_UNROLL for (int c = 0; c < NX; ++c) xm[c] = fma(yi, tm[oAt + i * NX + c], xm[c]);
       }
@@ -230,7 +225,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
         double gr[NX]; // row ku of G_t
         ASLR_UNROLL for (int c = 0; c < NX; ++c) gr[c] = tm[oG + ku * NX + c];
         double uk = 0.0;
-        ASLR_LQG_LOOP for (int l = 0; l < NU; ++l) {
+        ASLR_SWEEP_LOOP for (int l = 0; l < NU; ++l) {
           double v = 0.0; // U[ku][l]
           ASLR_UNROLL for (int c = 0; c < NX; ++c) v = fma(gr[c], tm[oK + l * NX + c], v);
           if (l == ku) uk = v;
@@ -261,7 +256,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
     {
       double y[NX]; // row j of Fx_t P_t
       ASLR_UNROLL for (int c = 0; c < NX; ++c) y[c] = 0.0;
-      ASLR_LQG_LOOP for (int i = 0; i < NX; ++i) {
+      ASLR_SWEEP_LOOP for (int i = 0; i < NX; ++i) {
         const double fi = tm[oAt + i * NX + j];
         ASLR_UNROLL for (int c = 0; c < NX; ++c) y[c] = fma(fi, tm[oSP + i * NX + c], y[c]);
       }
@@ -269,7 +264,7 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
       ASLR_UNROLL for (int c = 0; c < NX; ++c) my_p[c] = y[c];
     }
     ASLR_UNROLL for (int c = 0; c < NX; ++c) pm[c] = 0.0;
-    ASLR_LQG_LOOP for (int i = 0; i < NX; ++i) {
+    ASLR_SWEEP_LOOP for (int i = 0; i < NX; ++i) {
       const double yi = my_p[i];
       ASLR_UNROLL for (int c = 0; c < NX; ++c) pm[c] = fma(yi, tm[oAt + i * NX + c], pm[c]);
     }
@@ -297,13 +292,9 @@ __global__ void __launch_bounds__(64) lqg_kernel(LqgArgs a) {
   }
 }
 
-#undef ASLR_LQG_LOOP
-
 template <int NJ, int DAM>
 int launch_lqg(const LqgArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL((lqg_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
-  HIP_TRY(hipGetLastError());
-  return ASLR_OK;
+  return launch_sweep<NJ, DAM>(lqg_kernel<4 * NJ, ModelDims<NJ, DAM>::nu>, a, st);
 }
 
 } // namespace aslr

@@ -12,8 +12,7 @@
 // is asked for): np = 2 nj with them (stiffness first), nj without, and a motor-inertia column goes through the same
 // operations on the same operands in both.
 //
-// Decomposition: one team of lanes per trajectory, as in the adjoint and covariance sweeps -- nx = 8: 8 lanes, 8
-// trajectories per wave; nx = 28: 32 lanes (28 at work), 2 per wave; one wave per block.  Lane j owns row j of S_t (np <= 14
+// Decomposition: one team of lanes per trajectory (aslr_sweep_team.hpp).  Lane j owns row j of S_t (np <= 14
 // registers) and holds rows j of Fx_t and Fu_t.  What the team shares is staged in its LDS, two buffers used in turn so that
 // a knot needs two barriers, not three.  One knot:
 //   stage   K_t (nu nx / TEAM words per lane), row j of S, Lx[j], Lu[k]; lane nj + c: -(delta_c / K_c), -(D_c / B_c)   | barrier
@@ -26,22 +25,18 @@
 // with Fx[j][i] / Fu[j][k] read from the lane's own words in LDS, as in the covariance sweep and for its reason: unrolled
 // in full over register operands, the scheduler hoisted the LDS reads of all (nx + nu) np chains and the nx = 28 kernels
 // spilled 1 to 3 KB per lane.  As built no kernel uses scratch.  The outputs that do not feed S (x_var, u_var, dcost) are computed only when asked for, so every
-// output has the same bits whichever others are asked for.  Every lane of the wave stays alive on clamped indices and only
-// the stores (to memory and to LDS) are guarded, so a trajectory's arithmetic is the same instruction stream whatever its
-// position in the batch: results do not depend on B, bit for bit.
+// output has the same bits whichever others are asked for.
 //
 // Arithmetic: (nx + nu) np fma per lane and knot for S', nu np nx / TEAM for V: about a third of the covariance sweep's.  A
 // serial chain of T knots; the records of knot t + 1 are loaded while knot t is reduced.
 #pragma once
-#include "aslr_common.hpp"
+#include "aslr_sweep_team.hpp"
 
 namespace aslr {
 
-#define ASLR_PS_LOOP _Pragma("unroll 2")
-
 template <int NX, int NU, bool STIFF>
 __global__ void __launch_bounds__(64) plant_sens_kernel(PlantSensArgs a) {
-  constexpr int NJ = NX / 4, TEAM = NX == 8 ? 8 : 32, TPW = 64 / TEAM;
+  constexpr int NJ = SweepTeam<NX>::NJ, TEAM = SweepTeam<NX>::TEAM, TPW = SweepTeam<NX>::TPW;
   constexpr int NP = STIFF ? 2 * NJ : NJ, P0 = NP - NJ;     // columns of S; the first motor-inertia column
   constexpr int NK = NU * NX, KP = (NK + TEAM - 1) / TEAM;  // words of K_t, and how many of them one lane of the team loads
   constexpr int NV = NU * NP, VP = (NV + TEAM - 1) / TEAM;  // entries of V_t, and how many of them one lane reduces
@@ -143,7 +138,7 @@ __global__ void __launch_bounds__(64) plant_sens_kernel(PlantSensArgs a) {
     load(nxt, t + 1 < T ? t + 1 : T - 1); // in flight while knot t is reduced (t = T-1: a repeat, dropped)
     double *bf = tm + (t & 1) * BUF;
     store(s, t);
-    const int mi = ((const int32_t __attribute__((address_space(4))) *)(a.node_model))[t];
+    const int mi = knot_model(a.node_model, t);
     double dt = a.plant.dt[0], rkm = rk[0], bim = bi[0];
     ASLR_UNROLL for (int m = 1; m < ASLR_MAX_MODELS; ++m)
       if (mi == m) { dt = a.plant.dt[m]; rkm = rk[m]; bim = bi[m]; }
@@ -173,11 +168,11 @@ __global__ void __launch_bounds__(64) plant_sens_kernel(PlantSensArgs a) {
 
     double sn[NP]; // 2: row j of S_{t+1}
     ASLR_UNROLL for (int p = 0; p < NP; ++p) sn[p] = 0.0;
-    ASLR_PS_LOOP for (int i = 0; i < NX; ++i) {
+    ASLR_SWEEP_LOOP for (int i = 0; i < NX; ++i) {
       const double f = my_f[i];
       ASLR_UNROLL for (int p = 0; p < NP; ++p) sn[p] = fma(f, bf[oS + i * NP + p], sn[p]);
     }
-    ASLR_PS_LOOP for (int k = 0; k < NU; ++k) {
+    ASLR_SWEEP_LOOP for (int k = 0; k < NU; ++k) {
       const double f = -my_f[NX + k];
       ASLR_UNROLL for (int p = 0; p < NP; ++p) sn[p] = fma(f, bf[oV + k * NP + p], sn[p]);
     }
@@ -225,18 +220,9 @@ __global__ void __launch_bounds__(64) plant_sens_kernel(PlantSensArgs a) {
   }
 }
 
-#undef ASLR_PS_LOOP
-
-// a.stiff: the stiffness columns are wanted.  The STIFF kernels are built for the SEA sizes alone: a VSA model takes its
-// stiffness from u, and aslr_policy_plant_sensitivity refuses every stiffness argument on one, so a.stiff is 0 there
 template <int NJ, int DAM>
 int launch_plant_sens(const PlantSensArgs &a, hipStream_t st) {
-  const auto go = [&](auto STIFF) {
-    hipLaunchKernelGGL((plant_sens_kernel<4 * NJ, ModelDims<NJ, DAM>::nu, decltype(STIFF)::value>), dim3(SizeTraits<NJ, DAM>::sweep_blocks(a.B)), dim3(64), 0, st, a);
-  };
-  if constexpr (DAM == ASLR_DAM_SEA) with_bool(a.stiff != 0, go); else go(std::false_type{});
-  HIP_TRY(hipGetLastError());
-  return ASLR_OK;
+  return launch_sweep_stiff<NJ, DAM>([](auto STIFF) { return plant_sens_kernel<4 * NJ, ModelDims<NJ, DAM>::nu, decltype(STIFF)::value>; }, a, st);
 }
 
 } // namespace aslr

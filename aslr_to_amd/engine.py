@@ -484,6 +484,23 @@ class Engine(object):
                            disturbance=back(dw, 2, 0, 1, 3))
         return r
 
+    def _spread(self, sigma0, noise_var):
+        """-> sigma0 [B, nx, nx] and noise_var [T, B, nx] on the device (None stays None), as policy_covariance and policy_lqg
+        take them: broadcast, sigma0 symmetric, no negative variance.  Called under the engine's device."""
+        torch = _torch()
+        B, T, nx = self.B, self.T, self.nx
+        s0 = self._bcast(sigma0, (B, nx, nx), ((1, 2),), None,
+                         "sigma0 must have shape [B=%d, nx=%d, nx] or [nx, nx], not {}" % (B, nx))
+        if s0 is not None:
+            if not torch.equal(s0, s0.transpose(1, 2)):
+                raise ValueError("sigma0 must be symmetric")
+            if bool((torch.diagonal(s0, dim1=1, dim2=2) < 0).any()):
+                raise ValueError("sigma0 has a negative variance on its diagonal")
+        w = self._bcast(noise_var, (B, T, nx), ((2,), (0, 2)), (1, 0, 2),
+                        "noise_var must have shape [B=%d, T=%d, nx=%d], [B, nx] or [nx], not {}" % (B, T, nx),
+                        nonneg="noise_var has a negative variance")
+        return s0, w
+
     def policy_covariance(self, sigma0=None, noise_var=None, keep_cov=False):
         """First-order state and control covariance under the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), by
         one calcDiff sweep and one forward sweep (aslr_policy_covariance, include/aslr_to_amd_cov.h): Sigma_{t+1} =
@@ -494,16 +511,7 @@ class Engine(object):
         torch = _torch()
         B, T, nx, nu = self.B, self.T, self.nx, self.nu
         with torch.cuda.device(self.device):
-            s0 = self._bcast(sigma0, (B, nx, nx), ((1, 2),), None,
-                             "sigma0 must have shape [B=%d, nx=%d, nx] or [nx, nx], not {}" % (B, nx))
-            if s0 is not None:
-                if not torch.equal(s0, s0.transpose(1, 2)):
-                    raise ValueError("sigma0 must be symmetric")
-                if bool((torch.diagonal(s0, dim1=1, dim2=2) < 0).any()):
-                    raise ValueError("sigma0 has a negative variance on its diagonal")
-            w = self._bcast(noise_var, (B, T, nx), ((2,), (0, 2)), (1, 0, 2),
-                            "noise_var must have shape [B=%d, T=%d, nx=%d], [B, nx] or [nx], not {}" % (B, T, nx),
-                            nonneg="noise_var has a negative variance")
+            s0, w = self._spread(sigma0, noise_var)
         zeros = self._zeros
         xv, uv, cf, ci = zeros(T + 1, B, nx), zeros(T, B, nu), zeros(B, nx, nx), zeros(B)
         cov = zeros(T + 1, B, nx, nx) if keep_cov else None
@@ -539,16 +547,7 @@ class Engine(object):
                 raise ValueError("meas_var is required: a scalar, [ny] or [B, ny]")
             if not bool((r > 0).all()):
                 raise ValueError("meas_var must be positive")
-            s0 = self._bcast(sigma0, (B, nx, nx), ((1, 2),), None,
-                             "sigma0 must have shape [B=%d, nx=%d, nx] or [nx, nx], not {}" % (B, nx))
-            if s0 is not None:
-                if not torch.equal(s0, s0.transpose(1, 2)):
-                    raise ValueError("sigma0 must be symmetric")
-                if bool((torch.diagonal(s0, dim1=1, dim2=2) < 0).any()):
-                    raise ValueError("sigma0 has a negative variance on its diagonal")
-            w = self._bcast(noise_var, (B, T, nx), ((2,), (0, 2)), (1, 0, 2),
-                            "noise_var must have shape [B=%d, T=%d, nx=%d], [B, nx] or [nx], not {}" % (B, T, nx),
-                            nonneg="noise_var has a negative variance")
+            s0, w = self._spread(sigma0, noise_var)
         zeros = self._zeros
         xv, uv, ev = zeros(T + 1, B, nx), zeros(T, B, nu), zeros(T + 1, B, nx)
         cf, ef, ci = zeros(B, nx, nx), zeros(B, nx, nx), zeros(B)
