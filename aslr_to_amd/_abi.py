@@ -236,6 +236,7 @@ PROTOTYPES = {
     "aslr_to_amd_policy_noise.h": {
         "aslr_policy_rollout_noise": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_int] + [_vp] * 10)},
     "aslr_to_amd_identify.h": {"aslr_plant_identify": (C.c_int, [_vp, C.POINTER(Identify), _vp])},
+    "aslr_to_amd_smooth.h": {"aslr_state_smooth": (C.c_int, [_vp, _i, C.POINTER(_i)] + [_vp] * 5 + [_i, C.c_double] + [_vp] * 8)},
 }
 
 # header -> the module attribute that lists what it declares (EXPORTED_SYMBOLS: the base header's)
@@ -245,7 +246,7 @@ SYMBOL_LISTS = {
     "aslr_to_amd_cov.h": "COV_SYMBOLS", "aslr_to_amd_lqg.h": "LQG_SYMBOLS", "aslr_to_amd_plant_sens.h": "PLANT_SENS_SYMBOLS",
     "aslr_to_amd_design.h": "DESIGN_SYMBOLS", "aslr_to_amd_policy_all.h": "POLICY_ALL_SYMBOLS",
     "aslr_to_amd_mpc_plant_all.h": "MPC_PLANT_ALL_SYMBOLS", "aslr_to_amd_policy_noise.h": "POLICY_NOISE_SYMBOLS",
-    "aslr_to_amd_identify.h": "IDENTIFY_SYMBOLS",
+    "aslr_to_amd_identify.h": "IDENTIFY_SYMBOLS", "aslr_to_amd_smooth.h": "SMOOTH_SYMBOLS",
 }
 globals().update((attr, list(PROTOTYPES[header])) for header, attr in SYMBOL_LISTS.items())
 

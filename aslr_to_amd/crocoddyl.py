@@ -313,6 +313,32 @@ class ShootingProblem(object):
             raise ValueError("policy_lqg: give xs, us and K together (or none of them: the engine's own policy)")
         return self._with_policy(xs, us, K, run)
 
+    def estimate_states(self, ys, us, meas_var, measured=None, xs_init=None, x0_mean=None, sigma0=None, noise_var=None,
+                        n_iters=5, relax=1.0, keep_filter=False):
+        """The full states of a recorded run from its encoder samples (Engine.estimate_states; aslr_state_smooth): ys
+        [B, T+1, ny] the samples of the state entries `measured` (None: the nx / 2 positions q_l, q_m) read with noise of
+        variance meas_var (a scalar, [ny] or [B, ny]), us [B, T, nu] the applied controls.  n_iters iterations of the extended
+        Kalman smoother on the problem's model (with the parameters the problem holds), from the nominal xs_init
+        [B, T+1, nx]; None, with the default `measured` only: the positions from ys and the velocities by forward differences
+        of ys over the models' dt, the last row repeated.  x0_mean [B, nx]: the prior mean of x_0 (None: xs_init at knot 0)
+        with covariance sigma0; noise_var: the process noise; both as policy_lqg takes them, at least one of the two.
+        -> engine.SmoothResult: xs [B, T+1, nx], neg_log_lik and step_norm [B, n_iters] and, with keep_filter, x_filt,
+        est_var [B, T+1, nx] and nis [B, T+1].  result.xs goes into identify_plant(xs, us, ...) as it is.  The engine's
+        candidate is left on the estimate.  This shard's trajectories only."""
+        import torch
+        e = self.engine
+        if xs_init is None:
+            if measured is not None and [int(i) for i in measured] != list(range(e.nx // 2)):
+                raise ValueError("estimate_states: xs_init is required when `measured` is not the positions")
+            y = e._f64(ys)
+            if y.dim() != 3 or tuple(y.shape[1:]) != (self.T + 1, e.nx // 2):
+                raise ValueError("ys must have shape [B=%d, T+1=%d, ny=%d]" % (self.batch, self.T + 1, e.nx // 2))
+            dt = torch.as_tensor([float(m.dt) for m in self.runningModels], dtype=torch.float64, device=y.device)
+            v = (y[:, 1:] - y[:, :-1]) / dt[None, :, None]
+            xs_init = torch.cat([y, torch.cat([v, v[:, -1:]], dim=1)], dim=2)
+        e.set_candidate(xs_init, us)
+        return e.estimate_states(ys, meas_var, measured, x0_mean, sigma0, noise_var, n_iters, relax, keep_filter)
+
     def policy_plant_sensitivity(self, xs, us, K, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
         """First-order sensitivity of the closed loop under the policy u_t = us_t - K_t (x_t - xs_t) to the plant's spring
         stiffness and motor inertia (Engine.policy_plant_sensitivity; aslr_policy_plant_sensitivity): xs, us, K as

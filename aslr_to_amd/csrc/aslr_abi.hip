@@ -20,6 +20,7 @@
 #include "../../include/aslr_to_amd_mpc_plant_all.h"
 #include "../../include/aslr_to_amd_design.h"
 #include "../../include/aslr_to_amd_identify.h"
+#include "../../include/aslr_to_amd_smooth.h"
 
 using namespace aslr;
 
@@ -602,9 +603,9 @@ constexpr KernelSet kernel_set() {
   constexpr KernelSet ks = {NJ, DAM, TP, SizeTraits<NJ, DAM>::boxddp_only, launch_calc<NJ, DAM, TP>, launch_dam_eval<NJ, DAM>, launch_dam_residuals<NJ, DAM>, launch_frame_placement<NJ>,
                             launch_quasi_static<NJ, DAM, TP>, launch_forward<NJ, DAM, TP>, launch_backward<NJ, DAM, TP>, launch_adjoint<NJ, DAM>, launch_covariance<NJ, DAM>,
                             launch_lqg<NJ, DAM>, launch_plant_sens<NJ, DAM>, policy_launcher<NJ, DAM, PolicyArgs>(), policy_launcher<NJ, DAM, PolicyNoiseArgs>(), mpc_plant_launcher<NJ, DAM>(),
-                            launch_identify_normal<NJ, DAM>, launch_identify_step<NJ, DAM>};
+                            launch_identify_normal<NJ, DAM>, launch_identify_step<NJ, DAM>, launch_smooth_filter<NJ, DAM>, launch_smooth_adjoint<NJ, DAM>};
   static_assert(ks.calc && ks.dam_eval && ks.dam_residuals && ks.frame_placement && ks.quasi_static && ks.forward && ks.backward && ks.adjoint && ks.covariance &&
-                ks.lqg && ks.plant_sens && ks.policy_rollout && ks.policy_rollout_noise && ks.mpc_plant && ks.identify_normal && ks.identify_step, "a row of kKernelSets lacks a launcher");
+                ks.lqg && ks.plant_sens && ks.policy_rollout && ks.policy_rollout_noise && ks.mpc_plant && ks.identify_normal && ks.identify_step && ks.smooth_filter && ks.smooth_adjoint, "a row of kKernelSets lacks a launcher");
   return ks;
 }
 constexpr KernelSet kKernelSets[] = {
@@ -1207,6 +1208,51 @@ int aslr_policy_lqg(aslr_problem_t *p, int32_t ny, const int32_t *meas_idx, cons
   a.kalman_gain = kalman_gain; a.cost_increase = cost_increase;
   a.B = k.B; a.T = k.T; a.ny = ny;
   return p->ks->lqg(a, st);
+}
+
+// aslr_state_smooth (include/aslr_to_amd_smooth.h): per iteration the calcDiff sweep at (XS, US),
+// smooth_filter_kernel and smooth_adjoint_kernel (aslr_smooth.inc.hpp), all on the caller's stream.  It only enqueues.
+int aslr_state_smooth(aslr_problem_t *p, int32_t ny, const int32_t *meas_idx, const double *ys, const double *meas_var,
+                      const double *x0_mean, const double *sigma0, const double *noise_var, int32_t n_iters, double relax,
+                      double *work, double *xs_smooth, double *x_filt, double *est_var, double *nis, double *neg_log_lik,
+                      double *step_norm, void *stream) {
+  const char *fn = "aslr_state_smooth";
+  if (!p) return no_handle(fn);
+  const KArgs &k = p->k;
+  const int nx = 4 * p->nj;
+  if (ny < 1 || ny > nx) return fail(ASLR_E_INVALID, "%s: ny is %d, must lie in [1, nx = %d]", fn, ny, nx);
+  SmoothArgs a;
+  memset(&a, 0, sizeof a);
+  for (int i = 0; i < nx; ++i) a.slot[i] = -1;
+  for (int i = 0; i < ny; ++i) {
+    const int m = meas_idx ? meas_idx[i] : i;
+    if (m < 0 || m >= nx) return fail(ASLR_E_INVALID, "%s: meas_idx[%d] is %d, outside [0, nx = %d)", fn, i, m, nx);
+    if (a.slot[m] >= 0) return fail(ASLR_E_INVALID, "%s: meas_idx[%d] repeats index %d of meas_idx[%d]", fn, i, m, a.slot[m]);
+    a.meas[i] = m;
+    a.slot[m] = i;
+  }
+  const struct { const void *ptr; const char *name; } required[] = {{ys, "ys"}, {meas_var, "meas_var"}, {x0_mean, "x0_mean"}, {work, "work"}};
+  for (const auto &r : required)
+    if (!r.ptr) return fail(ASLR_E_INVALID, "%s: %s is NULL", fn, r.name);
+  if (!xs_smooth && !x_filt && !est_var && !nis && !neg_log_lik && !step_norm)
+    return fail(ASLR_E_INVALID, "%s: all six outputs are NULL: nothing to compute", fn);
+  if (!sigma0 && !noise_var) return fail(ASLR_E_INVALID, "%s: sigma0 and noise_var are both NULL: nothing to propagate", fn);
+  if (n_iters < 1) return fail(ASLR_E_INVALID, "%s: n_iters is %d, must be at least 1", fn, n_iters);
+  if (!(relax > 0.0 && relax <= 1.0)) return fail(ASLR_E_INVALID, "%s: relax is %g, must lie in (0, 1]", fn, relax);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  a.deriv = k.deriv; a.xnext = k.xnext; a.xs = k.xs;
+  a.ys = ys; a.meas_var = meas_var; a.x0_mean = x0_mean; a.sigma0 = sigma0; a.noise_var = noise_var;
+  a.work = work; a.relax = relax;
+  a.B = k.B; a.T = k.T; a.ny = ny;
+  for (int s = 0; s < n_iters; ++s) {
+    if (s == n_iters - 1) { a.xs_smooth = xs_smooth; a.x_filt = x_filt; a.est_var = est_var; a.nis = nis; }
+    a.neg_log_lik = neg_log_lik ? neg_log_lik + (size_t)s * k.B : nullptr;
+    a.step_norm = step_norm ? step_norm + (size_t)s * k.B : nullptr;
+    if (int rc = p->ks->calc(p->k, true, diff_mode(p, p->k, 0, true), -1.0, st)) return rc;
+    if (int rc = p->ks->smooth_filter(a, st)) return rc;
+    if (int rc = p->ks->smooth_adjoint(a, st)) return rc;
+  }
+  return ASLR_OK;
 }
 
 int aslr_policy_plant_sensitivity(aslr_problem_t *p, const double *stiffness_var, const double *motor_inertia_var,

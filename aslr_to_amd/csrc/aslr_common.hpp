@@ -155,7 +155,7 @@ struct SizeTraits {
   static constexpr bool boxddp_only = big_vsa;
   static constexpr int cost_tag = big_vsa ? 14 : NJ;      // instantiation tag of sum_cost_kernel / select_kernel
   static constexpr bool reg_column = !big_vsa;            // backward: the register-column kernel (ASLR_BWD_HS > 0) is built
-  // adjoint / covariance / LQG / tangent sweeps: one wave per block, a team of 8 (nx = 8) or 32 (nx = 28) lanes per trajectory
+  // adjoint / covariance / LQG / tangent / smoother sweeps: one wave per block, a team of 8 (nx = 8) or 32 (nx = 28) lanes per trajectory
   static constexpr int sweep_blocks(int B) { return NJ == 2 ? (B + 7) / 8 : (B + 1) / 2; }
 };
 
@@ -347,6 +347,26 @@ struct IdentifyStepArgs {
 };
 template <int NJ, int DAM> int launch_identify_step(const IdentifyStepArgs &a, hipStream_t st);
 
+// aslr_state_smooth (aslr_smooth.inc.hpp; include/aslr_to_amd_smooth.h): what smooth_filter_kernel and smooth_adjoint_kernel
+// read and write in one iteration, by value.  Like the LQG sweep they read no model constant: one pair of launchers per size,
+// shared by its two rows.  The caller's scratch `work` holds, time-major with N = (T+1) B knots of trajectories:
+//   Pm [N][nx][nx] (word [c][j]: lane j's entry c) | L^T [N][ny][nx] | m^- [N][nx] | w [N][ny]
+struct SmoothArgs {
+  const double *deriv, *xnext;
+  double *xs;                                  // XS of the handle: the nominal (both kernels read it), then the relaxed estimate
+  const double *ys, *meas_var, *x0_mean;       // [T+1][B][ny], [B][ny], [B][nx]
+  const double *sigma0, *noise_var;            // [B][nx][nx], [T][B][nx]; each nullable (zero)
+  double *work;
+  double *xs_smooth, *x_filt, *est_var, *nis;  // [T+1][B][nx] x 3, [T+1][B]; every output nullable (set in the last iteration)
+  double *neg_log_lik, *step_norm;             // [B] of this iteration, each nullable
+  double relax;
+  int32_t B, T, ny;
+  int32_t meas[ASLR_MAX_NX]; // the measured state entries: the first ny, distinct, each in [0, nx)
+  int32_t slot[ASLR_MAX_NX]; // slot[i]: where state entry i stands in meas, or -1 (not measured)
+};
+template <int NJ, int DAM> int launch_smooth_filter(const SmoothArgs &a, hipStream_t st);
+template <int NJ, int DAM> int launch_smooth_adjoint(const SmoothArgs &a, hipStream_t st);
+
 // the launchers of one supported size: a row of the table in aslr_abi.hip, looked up once by aslr_problem_create
 struct KernelSet {
   int nj, dam;
@@ -368,6 +388,8 @@ struct KernelSet {
   decltype(&launch_mpc_plant<2, 0>) mpc_plant;
   decltype(&launch_identify_normal<2, 0>) identify_normal;
   decltype(&launch_identify_step<2, 0>) identify_step;
+  decltype(&launch_smooth_filter<2, 0>) smooth_filter;
+  decltype(&launch_smooth_adjoint<2, 0>) smooth_adjoint;
 };
 
 #ifdef ASLR_BWD_PROFILE

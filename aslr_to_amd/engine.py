@@ -63,6 +63,14 @@ class LqgResult(_Result):
     measured state entries the call used."""
 
 
+class SmoothResult(_Result):
+    """What Engine.estimate_states returns: batch-major device tensors -- xs [B, T+1, nx] (the smoothed states of the last
+    iteration, before relax), neg_log_lik and step_norm [B, n_iters] (the filter's negative log-likelihood and max |xs - nominal|
+    of every iteration) and, when the filter is kept, x_filt [B, T+1, nx] (the filter's posterior mean m_t), est_var
+    [B, T+1, nx] (diagonal of P_t) and nis [B, T+1] (the normalised innovation squared), all of the last iteration (None
+    otherwise); measured: the list of measured state entries the call used."""
+
+
 class PlantSensitivityResult(_Result):
     """What Engine.policy_plant_sensitivity returns: batch-major device tensors -- dx_final_dstiffness,
     dx_final_dmotor_inertia [B, nx, nj] (dx_T/dK_j, dx_T/dB_j), dcost_dstiffness, dcost_dmotor_inertia [B, nj], x_var
@@ -501,6 +509,30 @@ class Engine(object):
                         nonneg="noise_var has a negative variance")
         return s0, w
 
+    def _measured(self, measured, meas_var):
+        """-> the list of measured state entries (None: the nx / 2 positions) and meas_var [B, ny] on the device, as policy_lqg
+        and estimate_states take them: distinct indices in [0, nx); a scalar, [ny] or [B, ny], positive"""
+        torch = _torch()
+        B, nx = self.B, self.nx
+        if measured is None:
+            measured = range(nx // 2)
+        try:
+            m = [int(i) for i in measured]
+            whole = all(i == v for i, v in zip(m, measured))
+        except (TypeError, ValueError):
+            raise ValueError("measured must be a list of state indices")
+        if not whole or not 1 <= len(m) <= nx or min(m) < 0 or max(m) >= nx or len(set(m)) != len(m):
+            raise ValueError("measured must hold between 1 and nx = %d distinct state indices in [0, %d), not %s" % (nx, nx, list(measured)))
+        ny = len(m)
+        with torch.cuda.device(self.device):
+            r = self._bcast(meas_var, (B, ny), ((), (1,)), None,
+                            "meas_var must be a scalar or have shape [ny=%d] or [B=%d, ny], not {}" % (ny, B), say_given=True)
+            if r is None:
+                raise ValueError("meas_var is required: a scalar, [ny] or [B, ny]")
+            if not bool((r > 0).all()):
+                raise ValueError("meas_var must be positive")
+        return m, r
+
     def policy_covariance(self, sigma0=None, noise_var=None, keep_cov=False):
         """First-order state and control covariance under the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), by
         one calcDiff sweep and one forward sweep (aslr_policy_covariance, include/aslr_to_amd_cov.h): Sigma_{t+1} =
@@ -530,23 +562,9 @@ class Engine(object):
         backward sweep K = 0: the filter is the same, the loop is open; the control box is not applied."""
         torch = _torch()
         B, T, nx, nu = self.B, self.T, self.nx, self.nu
-        if measured is None:
-            measured = range(nx // 2)
-        try:
-            m = [int(i) for i in measured]
-            whole = all(i == v for i, v in zip(m, measured))
-        except (TypeError, ValueError):
-            raise ValueError("measured must be a list of state indices")
-        if not whole or not 1 <= len(m) <= nx or min(m) < 0 or max(m) >= nx or len(set(m)) != len(m):
-            raise ValueError("measured must hold between 1 and nx = %d distinct state indices in [0, %d), not %s" % (nx, nx, list(measured)))
+        m, r = self._measured(measured, meas_var)
         ny = len(m)
         with torch.cuda.device(self.device):
-            r = self._bcast(meas_var, (B, ny), ((), (1,)), None,
-                            "meas_var must be a scalar or have shape [ny=%d] or [B=%d, ny], not {}" % (ny, B), say_given=True)
-            if r is None:
-                raise ValueError("meas_var is required: a scalar, [ny] or [B, ny]")
-            if not bool((r > 0).all()):
-                raise ValueError("meas_var must be positive")
             s0, w = self._spread(sigma0, noise_var)
         zeros = self._zeros
         xv, uv, ev = zeros(T + 1, B, nx), zeros(T, B, nu), zeros(T + 1, B, nx)
@@ -558,6 +576,41 @@ class Engine(object):
         return LqgResult(x_var=xv.permute(1, 0, 2), u_var=self.cut_u(uv.permute(1, 0, 2)), est_var=ev.permute(1, 0, 2),
                          cov_final=cf, est_cov_final=ef, cost_increase=ci,
                          kalman_gain=None if kg is None else kg.permute(1, 0, 2, 3), measured=m)
+
+    def estimate_states(self, ys, meas_var, measured=None, x0_mean=None, sigma0=None, noise_var=None, n_iters=5, relax=1.0,
+                        keep_filter=False):
+        """The states of a recorded run from its measurements: n_iters iterations of the extended Kalman smoother
+        (Gauss-Newton on the MAP estimate) about the nominal trajectory in XS with the applied controls in US, all on the
+        device in one call (aslr_state_smooth, include/aslr_to_amd_smooth.h, which gives the recursion).  ys [B, T+1, ny]: the
+        state entries `measured` at every knot, read with noise of variance meas_var; measured, meas_var, sigma0 and noise_var
+        as policy_lqg takes them; x0_mean [B, nx] or [nx]: the prior mean of x_0 (None: XS at knot 0); relax in (0, 1]: the
+        part of every step taken.  -> SmoothResult.  Side effects: those of calc_diff, and XS holds the (relaxed) estimate."""
+        torch = _torch()
+        B, T, nx = self.B, self.T, self.nx
+        m, r = self._measured(measured, meas_var)
+        ny = len(m)
+        n_iters = int(n_iters)
+        if n_iters < 1:
+            raise ValueError("n_iters must be at least 1")
+        with torch.cuda.device(self.device):
+            y = self._dev(ys, (B, T + 1, ny), (1, 0, 2), "ys")
+            if y is None:
+                raise ValueError("ys is required: [B, T+1, ny]")
+            s0, w = self._spread(sigma0, noise_var)
+            if x0_mean is None:
+                x0 = self.region(_abi.R_XS)[0].clone()
+            else:
+                x0 = self._bcast(x0_mean, (B, nx), ((1,),), None, "x0_mean must have shape [B=%d, nx=%d] or [nx], not {}" % (B, nx))
+        zeros = self._zeros
+        work = zeros((T + 1) * B * (nx * nx + nx * ny + nx + ny))
+        xs, nll, step = zeros(T + 1, B, nx), zeros(n_iters, B), zeros(n_iters, B)
+        xf, ev, nis = (zeros(T + 1, B, nx), zeros(T + 1, B, nx), zeros(T + 1, B)) if keep_filter else (None, None, None)
+        self._call("aslr_state_smooth", ny, (C.c_int32 * ny)(*m), _ptr(y), _ptr(r), _ptr(x0), _ptr(s0), _ptr(w), n_iters,
+                   float(relax), _ptr(work), _ptr(xs), _ptr(xf), _ptr(ev), _ptr(nis), _ptr(nll), _ptr(step), self._stream())
+        torch.cuda.synchronize(self.device)  # (the device copies of the inputs and the scratch die on return)
+        back = lambda t: None if t is None else t.permute(1, 0, 2)
+        return SmoothResult(xs=back(xs), neg_log_lik=nll.permute(1, 0), step_norm=step.permute(1, 0), x_filt=back(xf),
+                            est_var=back(ev), nis=None if nis is None else nis.permute(1, 0), measured=m)
 
     def policy_plant_sensitivity(self, stiffness_var=None, motor_inertia_var=None, keep_trajectories=False):
         """First-order sensitivity of the closed loop under the policy in XS / US / KGAIN, u_t = us_t - K_t (x_t - xs_t), to
